@@ -1,17 +1,24 @@
 #!/usr/bin/env python3
 """Headline benchmark: optimiser iterations/sec of the style-transfer hot loop on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--size S | WxH] [--no-cpu-baseline] [--no-extra]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--size S | WxH] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] [--no-extra] [--no-pmc]]
 
 One "step" = one full iteration of reference style_transfer.py:479-486 (VGG-19 forward, 7-term loss,
 backward to the pixels, Adam, clamp, EMA), synthetic seeded content/style images and seeded synthetic
 VGG-19 weights (no network, no pretrained file in this image).  All inputs are resident in HBM before the
 timed region.
 
+A plain run sets up, runs W warm-up steps, times K steps (`value`, `ms_per_step`), writes the last timed step's
+outputs when --dump-outputs is given, and prints its line.  Everything else the benchmark measures runs only with
+--full: two more K-step regions (`value_regions`, `value_best_of_3`), the profiled steps of `roofline` /
+`roofline_hbm`, and at N = 1 the items below.
+
 * N = 1 (default): a 512 x 512 image - the end scale of BASELINE.json configs[1], the config the metric is
-  quoted on.  The line also carries `extra_sizes` (short runs at 1024^2, 2048^2 and 2896x2172 on the same
-  GPU: the single-GPU points of configs[2..4]) and `cpu_baseline` (the unmodified reference's --devices cpu
-  path, staged by oracle/make_ref.py, timed with its own STIterate.time hook on this box's host cores).
+  quoted on.  With --full the line also carries `extra_sizes` (short runs at 1024^2, 2048^2 and 2896x2172 on the
+  same GPU: the single-GPU points of configs[2..4]), the other conv arithmetic modes, `config2_default_run` and
+  `cpu_baseline` (the unmodified reference's --devices cpu path, staged by oracle/make_ref.py, timed with its own
+  STIterate.time hook on the host cores).
 * N > 1: the driver launches one rank per GPU (torch.distributed, backend nccl = RCCL) and ONE 2048 x 2048 image
   (configs[3]; `--size` overrides) is cut into N row strips - halo exchange + Gram all-reduce, "scaling":
   "strong", `value` = iterations/s of that image.  The strong-scaling base is `extra_sizes["2048x2048"]` of the
@@ -19,6 +26,11 @@ timed region.
   sharded path fails the line says so with "value": null and the exit code is 1 - there is no silent fallback.
 
 Rank 0 prints ONE JSON line.
+
+--dump-outputs DIR: what a caller of the timed path receives after the last timed step - the image, its EMA, the two
+Adam moments and the 8 loss values (7 weighted terms + total) - as DIR/<name>.npy (float32), the strips of a sharded
+run joined into the whole image.  At most 64 MiB in all: above that, larger arrays are replaced by a fixed seeded
+sample of their elements.  The inputs are seeded, so two builds run with the same arguments can be compared file by file.
 """
 import argparse
 import json
@@ -178,6 +190,7 @@ def run_single(args, dev, rank, world, hw=None):
     def step():
         state['step'] += 1
         plan.step(image, m, v, ema, state['step'], 0.02)
+    step.outputs = lambda: {'image': image, 'image_ema': ema, 'adam_exp_avg': m, 'adam_exp_avg_sq': v, 'losses': plan.losses}
     return plan, step, (weights, content, style, image0), (lambda: float(plan.losses[7].item()))
 
 
@@ -225,6 +238,7 @@ def run_sharded(args, dev, rank, world, conservative=False, native=False):
         sharding.run_phases(plan, fabric)
         plan.apply_update(image, grad, m, v, ema, state['step'], 0.02)
     step.fabric = fabric
+    step.outputs = lambda: {'image': image, 'image_ema': ema, 'adam_exp_avg': m, 'adam_exp_avg_sq': v, 'losses': plan.losses}
     return plan, step, None, (lambda: float(plan.losses[7].item()))
 
 
@@ -299,7 +313,7 @@ def pmc_traffic_measured(args, prec, mode):
         for counter, sub in (('FETCH_SIZE', 'f'), ('WRITE_SIZE', 'w')):
             cmd = [exe, '--kernel-trace', '--pmc', counter, '-d', os.path.join(tmp, sub), '-o', sub, '--output-format', 'csv', '--',
                    sys.executable, os.path.abspath(__file__), '--size', size, '--steps', '3', '--warmup', '2', '--precision', prec,
-                   '--no-cpu-baseline', '--no-extra', '--no-pmc']
+                   '--no-cpu-baseline', '--no-extra', '--no-pmc', '--full']
             env = dict(os.environ, TMPDIR='/tmp', ST_BENCH_PMC_CHILD='1')
             try:
                 r = subprocess.run(cmd, cwd='/tmp', env=env, capture_output=True, text=True, timeout=150)
@@ -352,6 +366,50 @@ def timed_run(step, steps, warmup, dev):
         step()
     torch.cuda.synchronize(dev)
     return (time.perf_counter() - t0) / steps
+
+
+DUMP_LIMIT_BYTES = 64 * 2 ** 20
+
+
+def write_outputs(path, arrays, limit=DUMP_LIMIT_BYTES, seed=0):
+    """--dump-outputs: each array as path/<name>.npy, float32 (float64 stays float64).  When together they hold more than
+    `limit` bytes (npy headers included), the smaller arrays are written whole and every array larger than its share of
+    what is left becomes a fixed sample of its flattened elements: indices drawn by a numpy Generator seeded with `seed`,
+    in ascending order - the same elements from run to run.  Returns {name: (elements written, elements in the array)}."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64 if v.dtype == np.float64 else np.float32).reshape(v.shape)
+              for k, v in arrays.items()}
+    header = 4096                                     # bytes reserved per file for the npy header (<= 4 KiB when flattened)
+    budget = limit - header * len(arrays)
+    written = {}
+    order = sorted(arrays, key=lambda k: (arrays[k].nbytes, k))
+    for i, name in enumerate(order):
+        a = arrays[name]
+        share = budget // (len(order) - i)
+        if a.nbytes > share:
+            k = share // a.itemsize
+            idx = np.sort(np.random.default_rng(seed).choice(a.size, size=k, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + '.npy'), a)
+        budget -= a.nbytes
+        written[name] = (a.size, arrays[name].size)
+    return written
+
+
+def collect_outputs(step, mode, world):
+    """The last step's outputs on the host (every rank takes part; what rank 0 returns is what it writes).  Sharded runs:
+    each rank holds one row strip of the image and its state, joined here in rank order; the losses are the whole image's
+    on every rank."""
+    arrays = {k: t.detach().cpu().numpy() for k, t in step.outputs().items()}
+    if mode == 'shard' and world > 1:
+        import numpy as np
+        import torch.distributed as dist
+        parts = [None] * world
+        dist.all_gather_object(parts, {k: v for k, v in arrays.items() if k != 'losses'})
+        for k in parts[0]:
+            arrays[k] = np.concatenate([p[k] for p in parts], axis=2)
+    return arrays
 
 
 def extra_sizes(args, dev):
@@ -519,13 +577,21 @@ def main():
     ap.add_argument('--scaling', choices=['weak', 'strong'], default='strong',
                     help='N > 1, sharded: strong (default) = the fixed image cut into N strips, value = its it/s; '
                          'weak = one size x size strip per GPU (an image of size*N rows), value = N x image it/s')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-extra', action='store_true', help='skip extra_sizes / other arithmetic modes (N = 1)')
-    ap.add_argument('--no-pmc', action='store_true', help='do not measure roofline.traffic with rocprofv3 child runs (N = 1)')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline figure does not need: two more timed regions, the roofline '
+                         'profiles, and at N = 1 the other sizes and arithmetic modes, the PMC traffic and the CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32, at most 64 MiB in all)")
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip cpu_baseline (N = 1)')
+    ap.add_argument('--no-extra', action='store_true', help='with --full: skip extra_sizes / other arithmetic modes (N = 1)')
+    ap.add_argument('--no-pmc', action='store_true',
+                    help='with --full: do not measure roofline.traffic with rocprofv3 child runs (N = 1)')
     ap.add_argument('--dist-backend', default='nccl',
                     help="torch.distributed backend; 'gloo' + ST_BENCH_SAME_DEVICE=1 runs all ranks on cuda:0 "
                          "(functional check of the N > 1 path on a single-GPU box, not a measurement)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ and 'RANK' not in os.environ:
         sys.exit(self_launch(args.gpus))
@@ -629,46 +695,54 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     final_loss = read_loss()
-    # Two more K-step regions under the same protocol (a 20-step region is 48 ms on boxes that differ by
-    # 8 %): `value` stays the FIRST region's - the contract's - and the line also carries all three and the best of them.
+    if args.dump_outputs:
+        outputs = collect_outputs(step, mode, world)          # (the state after the last timed step, before any --full step)
+        if rank == 0:
+            write_outputs(args.dump_outputs, outputs)
+        del outputs
     regions = [elapsed]
-    for _ in range(2):
-        sync_all()
-        r0 = time.perf_counter()
-        for _ in range(args.steps):
-            step()
-        torch.cuda.synchronize(dev)
-        if world > 1:
-            dist.barrier()
-        r = time.perf_counter() - r0
-        if world > 1:
-            t = torch.tensor([r], device=dev, dtype=torch.float64)
-            dist.all_reduce(t, op=dist.ReduceOp.MAX)
-            r = float(t.item())
-        regions.append(r)
+    hbm = {}
+    if args.full:
+        # Two more K-step regions under the same protocol (a 20-step region is 48 ms on machines that differ
+        # by 8 %): `value` stays the FIRST region's - the contract's - and the line also carries all three and the best of them.
+        for _ in range(2):
+            sync_all()
+            r0 = time.perf_counter()
+            for _ in range(args.steps):
+                step()
+            torch.cuda.synchronize(dev)
+            if world > 1:
+                dist.barrier()
+            r = time.perf_counter() - r0
+            if world > 1:
+                t = torch.tensor([r], device=dev, dtype=torch.float64)
+                dist.all_reduce(t, op=dist.ReduceOp.MAX)
+                r = float(t.item())
+            regions.append(r)
 
-    # ---- roofline of the dominant kernel (MFMA implicit-GEMM conv), HIP events on its stream ----
-    plan.profile_enable(True)
-    prof_steps = 3
-    for _ in range(prof_steps):
-        step()
-    hbm = hbm_rooflines(plan, prof_steps) if mode in ('single', 'replicas') else {}
-    launches, ms, flops = plan.profile_read()
-    plan.profile_enable(False)
-    achieved = flops / (ms * 1e-3) / 1e12 if ms > 0 else 0.0
+        # ---- roofline of the dominant kernel (MFMA implicit-GEMM conv), HIP events on its stream ----
+        plan.profile_enable(True)
+        prof_steps = 3
+        for _ in range(prof_steps):
+            step()
+        hbm = hbm_rooflines(plan, prof_steps) if mode in ('single', 'replicas') else {}
+        launches, ms, flops = plan.profile_read()
+        plan.profile_enable(False)
+        achieved = flops / (ms * 1e-3) / 1e12 if ms > 0 else 0.0
 
     prec = args.precision
     if rank == 0:
-        # roofline.traffic: measured for THIS run where rocprofv3 is available (N = 1, not --no-extra / --no-pmc), else the
-        # figure replayed from the round's committed PMC passes - labelled either way
-        traffic = (None, 'skipped (--no-pmc / --no-extra)')
-        if world == 1 and mode == 'single' and not args.no_pmc and not args.no_extra:
-            traffic = pmc_traffic_measured(args, prec, mode)
-        if traffic[0] is None:
-            replay = pmc_traffic(args, prec, mode)
-            if replay[0] is not None:
-                replay[1]['in_run_measurement'] = traffic[1]
-            traffic = replay
+        if args.full:
+            # roofline.traffic: measured for THIS run where rocprofv3 is available (N = 1, not --no-extra / --no-pmc), else
+            # the figure replayed from the committed PMC passes - labelled either way
+            traffic = (None, 'skipped (--no-pmc / --no-extra)')
+            if world == 1 and mode == 'single' and not args.no_pmc and not args.no_extra:
+                traffic = pmc_traffic_measured(args, prec, mode)
+            if traffic[0] is None:
+                replay = pmc_traffic(args, prec, mode)
+                if replay[0] is not None:
+                    replay[1]['in_run_measurement'] = traffic[1]
+                traffic = replay
         height, width = args.height, args.width
         size = f'{width}x{height}'
         weak_shard = mode == 'shard' and args.scaling == 'weak' and world > 1
@@ -706,41 +780,44 @@ def main():
                                    f'1 style image {size}, VGG-19 synthetic weights, max pooling',
                        'image_wh': [width, height], 'parallelism': par},
             'final_loss': final_loss,
-            'value_regions': [jobs * args.steps / r for r in regions],      # the contract's region first, then two more
-            'value_best_of_3': jobs * args.steps / min(regions),
-            'roofline': {'bound': 'mfma',
-                         'kernel': ('conv_split_kernel / conv_pc_kernel / conv_fat_kernel' if prec == 'fp16x3' else
-                                    'conv_split_kernel' if prec != 'fp32' else 'conv_mfma_kernel') +
-                                   ' (the 3x3 trunk convolutions, forward + data gradient, split-K reduce passes included), rank 0',
-                         'achieved': achieved, 'peak': CONV_PEAK[prec], 'unit': 'TFLOP/s',
-                         'frac': achieved / CONV_PEAK[prec], 'traffic': traffic[0], 'traffic_source': traffic[1],
-                         # executed MFMA work against the dense 16-bit matrix peak: the direct kernels execute
-                         # exactly `products` MFMA MACs per algorithmic MAC, so this equals `frac`; a Winograd F(2x2, 3x3) form
-                         # would execute 16 / 36 of them (built and measured this round, slower: profiles/r06_winograd.md)
-                         'mfma_work_frac': (achieved * MFMA_PRODUCTS[prec] / PEAK_BF16_MFMA_TFLOPS) if prec in MFMA_PRODUCTS else None,
-                         'mfma_products_per_mac': MFMA_PRODUCTS.get(prec),
-                         'peak_note': 'algorithmic fp32-equivalent FLOPs; peak = dense MFMA peak of the mode / products per MAC '
-                                      'at the nominal 2.4 GHz; measured ceiling of an LDS-fed fp16x3 tile on this chip: 641-661 TF '
-                                      '(profiles/r02_mfma_sustained.md: matrix pipe alone 2.34 PF, with the tile\'s LDS operand '
-                                      'stream 1.92-1.98 PF); XL tile under load: 1.73 GHz, matrix pipes 71 % busy)',
-                         'traffic_algorithmic': conv_algorithmic_bytes_per_launch(height, width),
-                         'traffic_algorithmic_fused_path': conv_fused_path_bytes_per_launch(height, width),
-                         'traffic_algorithmic_note': 'traffic_algorithmic = operand + result + weights of a bare convolution; '
-                                                     '..._fused_path also counts the ReLU-mask and tap-gradient reads of the data-gradient '
-                                                     'epilogues and the pooled (+ 1 byte / window) writes of the four pooled layers',
-                         'launches_per_step': launches / prof_steps, 'avg_launch_ms': ms / max(launches, 1),
-                         'algorithmic_gflop_per_step': flops / prof_steps / 1e9,
-                         'whole_step_conv_tflops_per_gpu': conv_flops(height, width) * its / max(world, 1) / 1e12
-                         if mode != 'shard' or weak_shard else conv_flops(height, width) * its / world / 1e12,
-                         'fp32_mfma_peak': PEAK_FP32_MFMA_TFLOPS},
         }
+        if args.full:
+            out.update({
+                'value_regions': [jobs * args.steps / r for r in regions],      # the contract's region first, then two more
+                'value_best_of_3': jobs * args.steps / min(regions),
+                'roofline': {'bound': 'mfma',
+                             'kernel': ('conv_split_kernel / conv_pc_kernel / conv_fat_kernel' if prec == 'fp16x3' else
+                                        'conv_split_kernel' if prec != 'fp32' else 'conv_mfma_kernel') +
+                                       ' (the 3x3 trunk convolutions, forward + data gradient, split-K reduce passes included), rank 0',
+                             'achieved': achieved, 'peak': CONV_PEAK[prec], 'unit': 'TFLOP/s',
+                             'frac': achieved / CONV_PEAK[prec], 'traffic': traffic[0], 'traffic_source': traffic[1],
+                             # executed MFMA work against the dense 16-bit matrix peak: the direct kernels execute
+                             # exactly `products` MFMA MACs per algorithmic MAC, so this equals `frac`; a Winograd F(2x2, 3x3) form
+                             # would execute 16 / 36 of them (built and measured this round, slower: profiles/r06_winograd.md)
+                             'mfma_work_frac': (achieved * MFMA_PRODUCTS[prec] / PEAK_BF16_MFMA_TFLOPS) if prec in MFMA_PRODUCTS else None,
+                             'mfma_products_per_mac': MFMA_PRODUCTS.get(prec),
+                             'peak_note': 'algorithmic fp32-equivalent FLOPs; peak = dense MFMA peak of the mode / products per MAC '
+                                          'at the nominal 2.4 GHz; measured ceiling of an LDS-fed fp16x3 tile on this chip: 641-661 TF '
+                                          '(profiles/r02_mfma_sustained.md: matrix pipe alone 2.34 PF, with the tile\'s LDS operand '
+                                          'stream 1.92-1.98 PF); XL tile under load: 1.73 GHz, matrix pipes 71 % busy)',
+                             'traffic_algorithmic': conv_algorithmic_bytes_per_launch(height, width),
+                             'traffic_algorithmic_fused_path': conv_fused_path_bytes_per_launch(height, width),
+                             'traffic_algorithmic_note': 'traffic_algorithmic = operand + result + weights of a bare convolution; '
+                                                         '..._fused_path also counts the ReLU-mask and tap-gradient reads of the data-gradient '
+                                                         'epilogues and the pooled (+ 1 byte / window) writes of the four pooled layers',
+                             'launches_per_step': launches / prof_steps, 'avg_launch_ms': ms / max(launches, 1),
+                             'algorithmic_gflop_per_step': flops / prof_steps / 1e9,
+                             'whole_step_conv_tflops_per_gpu': conv_flops(height, width) * its / max(world, 1) / 1e12
+                             if mode != 'shard' or weak_shard else conv_flops(height, width) * its / world / 1e12,
+                             'fp32_mfma_peak': PEAK_FP32_MFMA_TFLOPS},
+            })
         if hbm:
             out['roofline_hbm'] = hbm
         if world > 1:
             out['multi_gpu_note'] = ('strong-scaling base = extra_sizes of the N = 1 line for the same image; the RCCL '
                                      'transport of this path had never run on hardware before this measurement '
                                      '(one GPU per gpurun box during development)')
-        if world == 1 and mode == 'single' and not args.no_extra:
+        if args.full and world == 1 and mode == 'single' and not args.no_extra:
             del plan, step
             torch.cuda.empty_cache()
             other = other_modes(args, dev, prec)
@@ -751,7 +828,7 @@ def main():
             out['extra_sizes'] = extra_sizes(args, dev)
             if (height, width) == (512, 512):
                 out['config2_default_run'] = config2_scales(args, dev, its)
-        if world == 1 and not args.no_cpu_baseline and height == width:
+        if args.full and world == 1 and not args.no_cpu_baseline and height == width:
             out['cpu_baseline'] = cpu_baseline(height)
             if out['cpu_baseline']['value']:
                 out['gpu_vs_cpu_baseline'] = its / out['cpu_baseline']['value']

@@ -41,3 +41,32 @@ def test_gpus_n_without_enough_devices_fails_loudly(tmp_path):
     assert r.returncode == 1, (r.stdout[-500:], r.stderr[-500:])
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][-1])
     assert d['value'] is None and d['n_gpus'] == 2 and 'FAILED' in d['config']['parallelism']
+
+
+def test_dump_outputs_are_float_bounded_and_sampled_the_same_way_every_time(tmp_path):
+    """bench.write_outputs (--dump-outputs): float32 / float64 .npy files, within the byte limit; arrays that fit are written
+    whole in their shape, the ones that do not become the same seeded sample of their elements on every call."""
+    import numpy as np
+    rng = np.random.default_rng(3)
+    small = {'image': rng.random((1, 3, 16, 16), dtype=np.float32), 'losses': np.arange(8, dtype=np.float32),
+             'f64': np.linspace(0, 1, 5)}
+    bench.write_outputs(tmp_path / 'small', small)
+    for name, a in small.items():
+        got = np.load(tmp_path / 'small' / (name + '.npy'))
+        assert got.dtype == a.dtype and np.array_equal(got, a), name
+
+    big = {'image': rng.random((1, 3, 256, 256), dtype=np.float32), 'ema': rng.random((1, 3, 256, 256)).astype(np.float16),
+           'losses': np.arange(8, dtype=np.float32)}
+    limit = 2 ** 20                                  # 1 MiB for 1.5 MiB of data
+    written = bench.write_outputs(tmp_path / 'a', big, limit=limit)
+    bench.write_outputs(tmp_path / 'b', big, limit=limit)
+    files = sorted(os.listdir(tmp_path / 'a'))
+    assert files == ['ema.npy', 'image.npy', 'losses.npy']
+    assert sum(os.path.getsize(tmp_path / 'a' / f) for f in files) <= limit
+    assert written['losses'] == (8, 8) and written['image'][0] < written['image'][1]
+    for f in files:
+        a, b = np.load(tmp_path / 'a' / f), np.load(tmp_path / 'b' / f)
+        assert a.dtype == np.float32 and np.array_equal(a, b), f
+    sample = np.load(tmp_path / 'a' / 'image.npy')
+    assert np.isin(sample, big['image'].reshape(-1)).all()
+    assert np.array_equal(np.load(tmp_path / 'a' / 'losses.npy'), big['losses'])

@@ -20,7 +20,7 @@ def _last_json(out):
 
 
 def test_single_gpu_line():
-    r = subprocess.run([sys.executable, 'bench.py', '--steps', '3', '--warmup', '1', '--no-cpu-baseline', '--no-extra'],
+    r = subprocess.run([sys.executable, 'bench.py', '--steps', '3', '--warmup', '1', '--full', '--no-cpu-baseline', '--no-extra'],
                        cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _last_json(r.stdout)
@@ -38,14 +38,14 @@ def test_single_gpu_line():
     assert abs(rf['frac'] - rf['achieved'] / rf['peak']) < 1e-9
 
 
-def test_two_rank_launch_contract():
+def test_two_rank_launch_contract(tmp_path):
     env = dict(os.environ, ST_BENCH_SAME_DEVICE='1')
     with socket.socket() as sock:
         sock.bind(('127.0.0.1', 0))
         port = sock.getsockname()[1]
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr',
            '127.0.0.1', '--master-port', str(port), 'bench.py', '--gpus', '2', '--steps', '2', '--warmup', '1',
-           '--dist-backend', 'gloo', '--size', '512']
+           '--dist-backend', 'gloo', '--size', '512', '--dump-outputs', str(tmp_path)]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-1500:])
     d = _last_json(r.stdout)
@@ -56,6 +56,11 @@ def test_two_rank_launch_contract():
     assert 'row strips' in par and 'strong' in par and 'FAILED' not in par, par
     assert '512x512' in d['config']['workload']
     assert 'cpu_baseline' not in d                    # rank 0 at N = 1 only
+    # --dump-outputs joins the two strips into the whole image
+    import numpy as np
+    image, losses = np.load(tmp_path / 'image.npy'), np.load(tmp_path / 'losses.npy')
+    assert image.shape == (1, 3, 512, 512) and np.isfinite(image).all() and 0 <= image.min() and image.max() <= 1
+    assert abs(float(losses[7]) - d['final_loss']) <= 1e-6 * abs(d['final_loss'])
 
 
 def test_plain_command_with_gpus_2_launches_two_ranks():
@@ -65,7 +70,7 @@ def test_plain_command_with_gpus_2_launches_two_ranks():
     for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT'):
         env.pop(k, None)
     r = subprocess.run([sys.executable, 'bench.py', '--gpus', '2', '--steps', '2', '--warmup', '1', '--dist-backend', 'gloo',
-                        '--size', '512'], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+                        '--size', '512', '--full'], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-1500:])
     d = _last_json(r.stdout)
     assert d['n_gpus'] == 2 and d['value'] > 0 and d['scaling'] == 'strong'
@@ -143,3 +148,35 @@ def test_a_first_iteration_past_its_deadline_falls_back_to_the_next_transport():
     print('[deadline]', par[-260:])
     assert d['value'] > 0 and 'FAILED' not in par and 'CONSERVATIVE' not in par, par
     assert 'did not complete within' in par and 'stream-ordered torch.distributed' in par, par
+
+
+def test_plain_line_is_lean_and_dumps_the_last_timed_step(tmp_path):
+    """A plain run times --steps steps and measures nothing else (no extra regions, no profiled steps, no other sizes or
+    modes, no CPU baseline: those need --full); --dump-outputs writes what the last timed step computed.  Two runs with the
+    same arguments start from the same seeded inputs, so their outputs agree."""
+    import numpy as np
+    names = ('image', 'image_ema', 'adam_exp_avg', 'adam_exp_avg_sq', 'losses')
+    got = []
+    for run in ('a', 'b'):
+        r = subprocess.run([sys.executable, 'bench.py', '--steps', '3', '--warmup', '1', '--size', '128',
+                            '--dump-outputs', str(tmp_path / run)], cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = _last_json(r.stdout)
+        for key in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'):
+            assert key in d, key
+        assert d['steps'] == 3 and d['warmup'] == 1 and abs(d['value'] * d['ms_per_step'] / 1e3 - 1.0) < 1e-6
+        for key in ('value_regions', 'roofline', 'roofline_hbm', 'extra_sizes', 'other_conv_arithmetic_it_s',
+                    'config2_default_run', 'cpu_baseline'):
+            assert key not in d, key
+        assert sorted(os.listdir(tmp_path / run)) == sorted(n + '.npy' for n in names)
+        arrays = {n: np.load(tmp_path / run / (n + '.npy')) for n in names}
+        assert sum(os.path.getsize(tmp_path / run / (n + '.npy')) for n in names) <= 64 * 2 ** 20
+        for n, a in arrays.items():
+            assert a.dtype == np.float32 and np.isfinite(a).all(), n
+            assert a.shape == ((8,) if n == 'losses' else (1, 3, 128, 128)), (n, a.shape)
+        assert abs(float(arrays['losses'][7]) - d['final_loss']) <= 1e-6 * abs(d['final_loss'])
+        assert arrays['image'].min() >= 0 and arrays['image'].max() <= 1
+        got.append(arrays)
+    for n in names:
+        assert np.allclose(got[0][n], got[1][n], rtol=1e-5, atol=1e-7), n
+    print('[dump] two runs bit-identical:', all(np.array_equal(got[0][n], got[1][n]) for n in names))

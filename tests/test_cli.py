@@ -144,10 +144,12 @@ def _free_port():
         return s.getsockname()[1]
 
 
-def _dist_init_worker(rank, world, port, out):
+def _dist_init_worker(rank, world, port, out, hide_gpus=False):
     import os
     import torch
     import torch.distributed as dist
+    if hide_gpus:
+        torch.cuda.is_available = lambda: False      # the launch logic of a host without GPUs (see the caller)
     os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank), MASTER_ADDR='127.0.0.1',
                       MASTER_PORT=str(port), ST_DIST_BACKEND='gloo')
     from style_transfer import cli as c
@@ -168,7 +170,10 @@ def test_cli_joins_the_process_group_under_torchrun():
     ctx = mp.get_context('spawn')
     out = ctx.Queue()
     port = _free_port()
-    procs = [ctx.Process(target=_dist_init_worker, args=(r, 2, port, out)) for r in range(2)]
+    # with GPUs visible, rank r binds to cuda:r, which a host with one GPU does not have: there the ranks run the launch
+    # logic as on a host without GPUs (the devices they are given are checked all the same)
+    hide = torch.cuda.is_available() and torch.cuda.device_count() < 2
+    procs = [ctx.Process(target=_dist_init_worker, args=(r, 2, port, out, hide)) for r in range(2)]
     for p in procs:
         p.start()
     for p in procs:

@@ -6,7 +6,7 @@ cd "$(dirname "$0")/.."
 for size in $SIZES; do
   for spec in "$@"; do
     name="${spec%%:*}"; envs="${spec#*:}"
-    env $envs timeout 120 python bench.py --no-extra --no-cpu-baseline --size "$size" --steps 40 --warmup 10 2>/dev/null |
+    env $envs timeout 120 python bench.py --full --no-extra --no-cpu-baseline --size "$size" --steps 40 --warmup 10 2>/dev/null |
       python -c "
 import sys, json
 d = json.loads(sys.stdin.readline())

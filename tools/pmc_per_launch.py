@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-launch FETCH_SIZE (x2, gfx950 correction) / WRITE_SIZE of the convolution launches of one bench step, from the two
-passes of tools/pmc_traffic.sh:  python tools/pmc_per_launch.py gpurun_out/pmc_traffic > table.md"""
+passes of tools/pmc_traffic.sh:  python tools/pmc_per_launch.py profile_out/pmc_traffic > table.md"""
 import csv, glob, os, sys
 root = sys.argv[1]
 

@@ -19,5 +19,5 @@ P
   done
 done
 for V in 0 1 0 1; do
-  echo "== ST_XCD_REMAP=$V bench $SZ"; ST_XCD_REMAP=$V python $R/bench.py --no-extra --no-cpu-baseline --no-pmc --size $SZ --steps 20 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('  it/s', round(d['value'],2), 'regions', [round(x,2) for x in d['value_regions']])"
+  echo "== ST_XCD_REMAP=$V bench $SZ"; ST_XCD_REMAP=$V python $R/bench.py --full --no-extra --no-cpu-baseline --no-pmc --size $SZ --steps 20 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('  it/s', round(d['value'],2), 'regions', [round(x,2) for x in d['value_regions']])"
 done
