@@ -300,6 +300,17 @@ int st_op_conv3x3_strip_ex(const float* in, const float* halo, int has_up, int h
 int st_op_conv1x1(const float* in, const float* weight, const float* bias, float* out, int cin, int cout,
                   long long npix, int precision, void* stream);
 
+/* 2x2 / stride-2 pooling of [C][H][W] -> [C][H/2][W/2] (floor mode: a trailing odd row / column is dropped), mode 0 =
+ * MaxPool2d(2), 1 = Scale(AvgPool2d(2), 2.0), 2 = Scale(LPPool2d(2, 2), 0.78) (style_transfer.py:21-22,41-46).  The
+ * plan's launcher: the 4-wide kernels when W % 4 == 0 and both pointers are 16-byte aligned, else the scalar ones.
+ * H, W >= 2. */
+int st_op_pool2x2(const float* in, float* out, int channels, int height, int width, int mode, void* stream);
+/* Its backward: grad_in [C][H][W] from grad_out [C][H/2][W/2] and the pool's input, masked by (in > 0) (the
+ * threshold_backward of the ReLU that produced `in`); the dropped row / column get 0.  The 4-wide kernel also needs
+ * an even H. */
+int st_op_pool2x2_backward(const float* in, const float* grad_out, float* grad_in, int channels, int height, int width,
+                           int mode, void* stream);
+
 /* ==================================================================================================================
  * MEASUREMENT AIDS - not part of the drop-in surface (no reference counterpart; a binding of the reference does not
  * need them).  They time the product's own kernels in isolation for tools/ and profiles/: st_op_sqrtm_time,

@@ -2622,6 +2622,21 @@ int st_op_conv1x1(const float* in, const float* weight, const float* bias, float
     return rc;
 }
 
+int st_op_pool2x2(const float* in, float* out, int channels, int height, int width, int mode, void* stream) {
+    ST_REQUIRE(in && out, "st_op_pool2x2: null argument");
+    ST_REQUIRE(mode >= 0 && mode <= 2, "st_op_pool2x2: mode must be 0 (max), 1 (average) or 2 (l2)");
+    ST_REQUIRE(channels > 0 && height >= 2 && width >= 2, "st_op_pool2x2: C >= 1 and H, W >= 2 required");
+    return launch_pool_fwd(in, out, channels, height, width, mode, static_cast<hipStream_t>(stream));
+}
+
+int st_op_pool2x2_backward(const float* in, const float* grad_out, float* grad_in, int channels, int height, int width,
+                           int mode, void* stream) {
+    ST_REQUIRE(in && grad_out && grad_in, "st_op_pool2x2_backward: null argument");
+    ST_REQUIRE(mode >= 0 && mode <= 2, "st_op_pool2x2_backward: mode must be 0 (max), 1 (average) or 2 (l2)");
+    ST_REQUIRE(channels > 0 && height >= 2 && width >= 2, "st_op_pool2x2_backward: C >= 1 and H, W >= 2 required");
+    return launch_pool_bwd(in, grad_out, grad_in, channels, height, width, mode, static_cast<hipStream_t>(stream));
+}
+
 int st_op_conv3x3_time(int cin, int cout, int height, int width, int dgrad, int precision, int iters,
                        double* avg_us, void* stream) {
     ST_REQUIRE(avg_us && iters > 0, "st_op_conv3x3_time: bad argument");

@@ -96,6 +96,8 @@ def _declare(lib):
         'st_op_conv3x3_strip': (i32, [vp, vp, i32, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
         'st_op_conv3x3_strip_ex': (i32, [vp, vp, i32, i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
         'st_op_conv1x1': (i32, [vp, vp, vp, vp, i32, i32, i64, i32, vp]),
+        'st_op_pool2x2': (i32, [vp, vp, i32, i32, i32, i32, vp]),
+        'st_op_pool2x2_backward': (i32, [vp, vp, vp, i32, i32, i32, i32, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)       # AttributeError here = header and library disagree
@@ -536,6 +538,36 @@ def op_conv1x1(x, weight, bias, precision=0):
                                  _ptr(bias.contiguous()) if bias is not None else None, _ptr(out), cin, cout,
                                  npix, int(precision), _stream()))
     return out
+
+
+POOL_MODES = {'max': 0, 'average': 1, 'l2': 2}
+
+
+def op_pool2x2(x, pooling, out=None):
+    """x [C, H, W] -> [C, H // 2, W // 2] by the plan's pooling launcher; `pooling` in POOL_MODES.  `out` (optional, a
+    contiguous fp32 tensor of that many elements) is written in place - the alignment of its pointer is the caller's."""
+    lib = load_library()
+    c, h, w = x.shape[-3:]
+    if out is None:
+        out = torch.empty((c, h // 2, w // 2), device=x.device, dtype=torch.float32)
+    assert out.numel() == c * (h // 2) * (w // 2)
+    with torch.cuda.device(x.device):
+        _check(lib.st_op_pool2x2(_ptr(x.contiguous()), _ptr(out), c, h, w, POOL_MODES[pooling], _stream()))
+    return out
+
+
+def op_pool2x2_backward(x, grad_out, pooling, grad_in=None):
+    """Gradient [C, H, W] of op_pool2x2(x) for grad_out [C, H // 2, W // 2], masked by (x > 0)."""
+    lib = load_library()
+    c, h, w = x.shape[-3:]
+    assert grad_out.numel() == c * (h // 2) * (w // 2)
+    if grad_in is None:
+        grad_in = torch.empty((c, h, w), device=x.device, dtype=torch.float32)
+    assert grad_in.numel() == c * h * w
+    with torch.cuda.device(x.device):
+        _check(lib.st_op_pool2x2_backward(_ptr(x.contiguous()), _ptr(grad_out.contiguous()), _ptr(grad_in), c, h, w,
+                                          POOL_MODES[pooling], _stream()))
+    return grad_in
 
 
 def op_conv3x3_dgrad(grad_out, relu_out, weight, precision=0):

@@ -23,6 +23,8 @@ What is recorded (all fp32, CPU, torch.set_num_threads(8), deterministic):
   stylize_lbfgs, stylize_init_{gray,uniform,normal,style_stats}
                stylize() with optimizer='lbfgs' (2 scales) and with each random `init` mode under
                torch.manual_seed(0) (two style images, weights .7/.3): loss trace + result
+  stylize_pool_{average,l2}
+               stylize() with pooling='average' / 'l2' (2 scales): loss trace + result
 
     python tests/golden/make_golden.py [case ...]   # only the named cases (e.g. eval_1024 stylize_lbfgs)
 """
@@ -201,7 +203,7 @@ def _pil(t):
     return Image.fromarray((t[0].permute(1, 2, 0) * 255).round().byte().numpy(), 'RGB')
 
 
-def case_stylize_variant(name, spread=False, **kw):
+def case_stylize_variant(name, spread=False, pooling='max', **kw):
     """stylize() with a non-default optimiser / init (style_transfer.py:380-406,464-467,482-483): 64x64 content,
     two style images (56x72 and 64x48) with weights .7/.3, torch.manual_seed(0) as the CLI sets it.
 
@@ -209,13 +211,14 @@ def case_stylize_variant(name, spread=False, **kw):
     reference's own trace is only reproducible to ~1e-3 after three iterations and ~2e-2 after seven.  The fixture
     records that: the same run with 1 instead of 8 threads (another summation order) and with conv1_1's bias
     scaled by 1 + 1e-6 / 1 + 1e-5, as `trace_spread` / `result_spread` (max relative / mean absolute deviation
-    from the base run).  The GPU test allows 5x that spread."""
+    from the base run).  The GPU test allows 5x that spread.  `pooling` is the StyleTransfer constructor's
+    (style_transfer.py:41-46)."""
     content = _pil(smooth_image(5, 64, 64))
     styles = [_pil(smooth_image(15, 56, 72)), _pil(smooth_image(16, 64, 48))]
 
     def run(threads=8, perturb=0.0):
         torch.set_num_threads(threads)
-        st, _ = make_reference('max')
+        st, _ = make_reference(pooling)
         if perturb:
             with torch.no_grad():
                 st.model.model[0].bias.mul_(1 + perturb)
@@ -595,6 +598,11 @@ CASES = {
     'stylize_init_style_stats': lambda: case_stylize_variant('stylize_init_style_stats', spread=True, init='style_stats',
                                                              min_scale=45, end_scale=64, iterations=3,
                                                              initial_iterations=4),
+    # pooling='average' / 'l2' (style_transfer.py:21-22,41-46) through stylize(), two scales
+    'stylize_pool_average': lambda: case_stylize_variant('stylize_pool_average', spread=True, pooling='average',
+                                                         min_scale=45, end_scale=64, iterations=3, initial_iterations=4),
+    'stylize_pool_l2': lambda: case_stylize_variant('stylize_pool_l2', spread=True, pooling='l2', min_scale=45,
+                                                    end_scale=64, iterations=3, initial_iterations=4),
 }
 
 

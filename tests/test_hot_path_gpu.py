@@ -114,24 +114,27 @@ def _smooth(seed, h, w):
     return (img + (torch.rand((1, 3, h, w), generator=g) - 0.5) * (24 / 255)).clamp(0, 1).contiguous()
 
 
-def _live_oracle_case(size, kind, precision, vgg_weights):
+def _live_oracle_case(size, kind, precision, vgg_weights, pooling='max'):
+    """`size`: an int (square) or (height, width)."""
     from style_transfer import _hip as hip
-    sh = size * 200 // 256                                  # a style image of another size (never upscaled)
+    height, width = size if isinstance(size, tuple) else (size, size)
+    size = f'{height}x{width}' if isinstance(size, tuple) else size
+    sh = height * 200 // 256                                # a style image of another size (never upscaled)
     if kind == 'photo_like':
-        content, style, image = _smooth(21, size, size), _smooth(22, sh, size), _smooth(23, size, size)
+        content, style, image = _smooth(21, height, width), _smooth(22, sh, width), _smooth(23, height, width)
     else:
         gen = torch.Generator().manual_seed(21)
-        content = torch.rand((1, 3, size, size), generator=gen)
-        style = torch.rand((1, 3, sh, size), generator=gen)
-        image = torch.rand((1, 3, size, size), generator=gen)
+        content = torch.rand((1, 3, height, width), generator=gen)
+        style = torch.rand((1, 3, sh, width), generator=gen)
+        image = torch.rand((1, 3, height, width), generator=gen)
     torch.set_num_threads(min(16, torch.get_num_threads()))   # 512^3 GEMMs oversubscribe on a 128-thread host
-    targets = O.build_targets(content, [style], vgg_weights)
-    terms, total, grad = O.loss_and_grad(image, vgg_weights, targets)
+    targets = O.build_targets(content, [style], vgg_weights, pooling=pooling)
+    terms, total, grad = O.loss_and_grad(image, vgg_weights, targets, pooling=pooling)
     w64 = [(w.double(), b.double()) for w, b in vgg_weights]
-    t64 = O.build_targets(content.double(), [style.double()], w64)
-    terms64, total64, grad64 = O.loss_and_grad(image.double(), w64, t64)
-    net, plan = _build_plan(hip, vgg_weights, content, [style], [1.0], precision=precision)
-    kind = f'{kind}/{precision}'
+    t64 = O.build_targets(content.double(), [style.double()], w64, pooling=pooling)
+    terms64, total64, grad64 = O.loss_and_grad(image.double(), w64, t64, pooling=pooling)
+    net, plan = _build_plan(hip, vgg_weights, content, [style], [1.0], pooling=pooling, precision=precision)
+    kind = f'{kind}/{precision}' if pooling == 'max' else f'{kind}/{precision}/{pooling}'
     losses, g = plan.loss_and_grad(image.to(DEV))
     got = losses.cpu().double().numpy()
     for k in range(7):
@@ -145,8 +148,8 @@ def _live_oracle_case(size, kind, precision, vgg_weights):
     rel_total = abs(got[7] - total) / abs(total)
     print(f'[parity] live{size}/{kind} total rel={rel_total:.2e}')
     assert rel_total <= TOTAL_TOL
-    err, floor_g = rel_l2(g.cpu(), grad), rel_l2(grad, grad64)
-    print(f'[parity] live{size}/{kind} image gradient rel_l2={err:.3e} (cpu32-vs-fp64 {floor_g:.3e})')
+    err, floor_g, err64 = rel_l2(g.cpu(), grad), rel_l2(grad, grad64), rel_l2(g.cpu(), grad64)
+    print(f'[parity] live{size}/{kind} image gradient rel_l2={err:.3e} (cpu32-vs-fp64 {floor_g:.3e}; hip-vs-fp64 {err64:.3e})')
     assert err <= (GRAD_TOL_BF16X3 if precision == 'bf16x3' else GRAD_TOL)
 
 
@@ -171,6 +174,21 @@ def test_closure_against_live_oracle_512(kind, precision, vgg_weights):
     consumer kernel's XL tile (conv1_2 ... conv2_2), its 256- and 128-pixel tiles (conv3_x ... conv5_1) and the
     fp16x3 Gram / 1x1 head kernels - the configuration bench.py measures."""
     _live_oracle_case(512, kind, precision, vgg_weights)
+
+
+@pytest.mark.parametrize('size,kind,precision', [
+    (512, 'photo_like', 'fp16x3'),            # the bench size: every pool level takes the 4-wide kernels
+    ((135, 181), 'photo_like', 'fp16x3'),     # pool inputs of 135, 67 and 33 rows (a row dropped) and odd widths
+    ((152, 200), 'white_noise', 'fp16x3'),    # pool inputs 200, 100, 50, 25 wide: 4-wide kernels, W % 4 == 2, odd W
+    ((135, 181), 'photo_like', 'fp32'),
+], ids=['512-photo_like-fp16x3', '135x181-photo_like-fp16x3', '152x200-white_noise-fp16x3', '135x181-photo_like-fp32'])
+@pytest.mark.parametrize('pooling', ['average', 'l2'])
+def test_closure_against_live_oracle_pooling_modes(pooling, size, kind, precision, vgg_weights):
+    """pooling='average' / 'l2' (StyleTransfer(pooling=...), style_transfer.py:21-22,41-46): the standalone pool kernels
+    in place of the max pool fused into the conv epilogue, and a pooled map that reuses its input's fp16x3 bound
+    (average pooling reaches 2 x, L2 pooling 1.56 x that input's maximum).  The same bars as the max-pool closure
+    against the live float64 oracle."""
+    _live_oracle_case(size, kind, precision, vgg_weights, pooling)
 
 
 def _strict_report(name, losses, want_terms, terms64):
@@ -287,7 +305,8 @@ def test_closure_against_reference_goldens_at_baseline_sizes(name, precision, vg
 def _spread_weights(weights, decades=6.0, seed=5):
     """The same network function with per-channel scales spanning `decades` decades inside it: output channel c of every
     conv that is NOT a tap is multiplied by s_c = 10^u (u uniform in +-decades/2, bias too) and input channel c of the
-    following conv by 1 / s_c.  ReLU and max pooling commute with positive per-channel factors, so every tap - hence
+    following conv by 1 / s_c.  ReLU and the three poolings (max, average, L2: each positively homogeneous, channel by
+    channel) commute with positive per-channel factors, so every tap - hence
     every loss term and the image gradient - is unchanged in exact arithmetic, while the feature maps BETWEEN the taps
     carry channels 10^6 apart, as the maps of the real VGG-19 do.  That is the stress case for fp16x3's single
     power-of-two scale per tensor."""
@@ -304,12 +323,15 @@ def _spread_weights(weights, decades=6.0, seed=5):
     return out
 
 
-def test_closure_with_six_decades_of_channel_scales(vgg_weights):
+@pytest.mark.parametrize('pooling', ['max', 'average', 'l2'])
+def test_closure_with_six_decades_of_channel_scales(pooling, vgg_weights):
     """Closure-level dynamic-range stress in the SHIPPED arithmetic (fp16x3) at 256^2 against the live oracle: feature
     maps whose channels span six decades (see _spread_weights).  Loss terms under the usual tolerances, the image
     gradient under 1e-3 - and both must stay where the unscaled network puts them.  Plain fp16x3 FAILS this (round 3,
     first run: content term off by 6.5e-3, relu5_1 by 2e-2 - two fp16 planes under one scale per tensor cannot hold a
-    channel 2^-20 below its neighbours); the library's range guard moves the affected layers to bf16x6."""
+    channel 2^-20 below its neighbours); the library's range guard moves the affected layers to bf16x6.  With average and
+    L2 pooling the pooled maps reuse their input's fp16x3 bound while exceeding it (up to 2 x / 1.56 x): this is the
+    closure-level check of that headroom."""
     from style_transfer import _hip as hip
     size = 256
     content, style, image = _smooth(41, size, size), _smooth(42, size, size), _smooth(43, size, size)
@@ -318,11 +340,13 @@ def test_closure_with_six_decades_of_channel_scales(vgg_weights):
     print(f'[parity] channel-scale stress: per-layer max/min output-channel weight norm {["%.1e" % r for r in ratios]}')
     assert max(ratios) >= 1e5
     torch.set_num_threads(min(16, torch.get_num_threads()))
-    targets = O.build_targets(content, [style], spread)
-    terms, total, grad = O.loss_and_grad(image, spread, targets)
+    targets = O.build_targets(content, [style], spread, pooling=pooling)
+    terms, total, grad = O.loss_and_grad(image, spread, targets, pooling=pooling)
     w64 = [(w.double(), b.double()) for w, b in spread]
-    terms64, _, grad64 = O.loss_and_grad(image.double(), w64, O.build_targets(content.double(), [style.double()], w64))
-    net, plan = _build_plan(hip, spread, content, [style], [1.0], precision='fp16x3')
+    terms64, _, grad64 = O.loss_and_grad(image.double(), w64, O.build_targets(content.double(), [style.double()], w64,
+                                                                              pooling=pooling), pooling=pooling)
+    net, plan = _build_plan(hip, spread, content, [style], [1.0], pooling=pooling, precision='fp16x3')
+    name = 'spread256/fp16x3' if pooling == 'max' else f'spread256/fp16x3/{pooling}'
     # the range guard (st_api.hip range_guard) must have recognised the compensating weights: forward of the conv AFTER a
     # rescaled layer (its input channels carry 1 / s), data gradient of the rescaled layer itself (its output channels
     # carry s) run bf16x6 - and with normalised weights nothing does
@@ -338,16 +362,16 @@ def test_closure_with_six_decades_of_channel_scales(vgg_weights):
     assert hip.Net(vgg_weights, 'max', DEV, 'fp16x3').wide_layers() == ([0] * 13, [0] * 13)
     losses, g = plan.loss_and_grad(image.to(DEV))
     losses, g = losses.clone(), g.clone()
-    _check_terms('spread256/fp16x3', losses, terms, total, terms64)
+    _check_terms(name, losses, terms, total, terms64)
     err, floor_g = rel_l2(g.cpu(), grad), rel_l2(grad, grad64)
-    print(f'[parity] spread256/fp16x3 image gradient rel_l2={err:.3e} (cpu32-vs-fp64 {floor_g:.3e})')
+    print(f'[parity] {name} image gradient rel_l2={err:.3e} (cpu32-vs-fp64 {floor_g:.3e})')
     assert err <= GRAD_TOL
     # the unscaled network computes the same function: the scaled run must not be visibly worse than it
-    net0, plan0 = _build_plan(hip, vgg_weights, content, [style], [1.0], precision='fp16x3')
+    net0, plan0 = _build_plan(hip, vgg_weights, content, [style], [1.0], pooling=pooling, precision='fp16x3')
     losses0, g0 = plan0.loss_and_grad(image.to(DEV))
     rel = ((losses - losses0).abs() / losses0.abs()).max().item()
     dg = rel_l2(g.cpu(), g0.cpu())
-    print(f'[parity] spread256/fp16x3 vs the unscaled network on the same inputs: loss terms {rel:.2e}, gradient {dg:.2e}')
+    print(f'[parity] {name} vs the unscaled network on the same inputs: loss terms {rel:.2e}, gradient {dg:.2e}')
     assert rel <= 3e-4 and dg <= 2e-3
 
 
@@ -543,13 +567,13 @@ def test_gpu_resampling_matches_cpu(mode, scale):
     assert d <= 2e-6
 
 
-def _stylize_variant(name, vgg_weights, **kw):
+def _stylize_variant(name, vgg_weights, pooling='max', **kw):
     from PIL import Image
     import style_transfer as st_pkg
     g = load_golden(name)
     content = Image.fromarray(g['content_u8'], 'RGB')
     styles = [Image.fromarray(g['style0_u8'], 'RGB'), Image.fromarray(g['style1_u8'], 'RGB')]
-    st = st_pkg.StyleTransfer(devices=[DEV], weights=vgg_weights)
+    st = st_pkg.StyleTransfer(devices=[DEV], weights=vgg_weights, pooling=pooling)
     its = []
     torch.manual_seed(0)
     st.stylize(content, styles, style_weights=[0.7, 0.3],
@@ -599,6 +623,18 @@ def test_stylize_non_default_parameters_against_reference(name, kw, vgg_weights)
     """Every numeric keyword of stylize() away from its default - loss weights, Adam step size, EMA decay, and the two
     ways of scaling the style images (style_scale_fac, style_size: style_transfer.py:433-437) - against reference runs."""
     st, rels, g = _stylize_variant(name, vgg_weights, **kw)
+    tol = np.maximum(5e-4, 5 * g['trace_spread'])
+    assert np.all(rels <= tol), (rels, tol)
+    _check_result(name, st.get_image_tensor().cpu(), _t(g['result']), g)
+
+
+@pytest.mark.parametrize('pooling', ['average', 'l2'])
+def test_stylize_pooling_modes_against_reference(pooling, vgg_weights):
+    """StyleTransfer(pooling='average' / 'l2') through stylize() on two scales (style_transfer.py:21-22,41-46) against
+    reference runs of the same call (golden stylize_pool_<mode>)."""
+    name = f'stylize_pool_{pooling}'
+    st, rels, g = _stylize_variant(name, vgg_weights, pooling=pooling, min_scale=45, end_scale=64, iterations=3,
+                                   initial_iterations=4)
     tol = np.maximum(5e-4, 5 * g['trace_spread'])
     assert np.all(rels <= tol), (rels, tol)
     _check_result(name, st.get_image_tensor().cpu(), _t(g['result']), g)

@@ -68,6 +68,15 @@ def test_strips_of_unequal_height_match_unsharded(h, w, rows, vgg_weights):
     _sharded_case(h, w, len(rows), 'fp16x3', 1, 1, vgg_weights, rows=rows)
 
 
+@pytest.mark.parametrize('h,w,world', [(96, 80, 3), (135, 181, 2)])
+@pytest.mark.parametrize('pooling', ['average', 'l2'])
+def test_sharded_pooling_modes_match_unsharded(pooling, h, w, world, vgg_weights):
+    """pooling='average' / 'l2' on strips (default overlap / owner settings): the standalone pool kernels on each strip, and
+    pooled maps whose halo rows can exceed the fp16x3 bound of the convolution that produced them (a pooled map reuses
+    its input's bound)."""
+    _sharded_case(h, w, world, 'fp16x3', 1, 1, vgg_weights, pooling=pooling)
+
+
 def test_halo_bounds_travel_with_the_rows(vgg_weights):
     """fp16x3: the consumer of a halo row scales its operand by max(|operand|, |halo rows|).  The sender measures its rows while
     it packs them and ships the word in the message's trailer (csrc/st_api.hip halo_exchange); the round-4 form measured them on
@@ -82,7 +91,7 @@ def test_halo_bounds_travel_with_the_rows(vgg_weights):
         assert torch.equal(out[1][0], out[0][0]) and torch.equal(out[1][1], out[0][1]), f'dark_top={dark}'
 
 
-def _sharded_case(h, w, world, precision, overlap, owner, vgg_weights, rows=None, dark_top=False):
+def _sharded_case(h, w, world, precision, overlap, owner, vgg_weights, rows=None, dark_top=False, pooling='max'):
     from style_transfer import _hip as hip, sharding as sh
     if precision != 'fp16x3' and (overlap, owner) == (2, 1):
         pytest.skip('only the fp16x3 producer / consumer kernel has interior / boundary launches')
@@ -93,7 +102,7 @@ def _sharded_case(h, w, world, precision, overlap, owner, vgg_weights, rows=None
         top = h // world
         image = image.clone()
         image[:, :, :top] = mean + (image[:, :, :top] - mean) * 1e-3
-    net = hip.Net(vgg_weights, 'max', DEV, precision)
+    net = hip.Net(vgg_weights, pooling, DEV, precision)
     # unsharded reference run of the same HIP code
     whole = hip.Plan(net, h, w)
     whole.forward(content.to(DEV), 22)
