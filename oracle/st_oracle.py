@@ -53,11 +53,13 @@ def layer_program():
     return prog
 
 
-def vgg_features(image, weights, layers, pooling='max'):
+def vgg_features(image, weights, layers, pooling='max', decisions=None):
     """VGGFeatures.forward (style_transfer.py:78-90) incl. the 'input' tap and the size check.
 
     image: [1,3,H,W] in [0,1] (un-normalised).  weights: 13 (w, b) pairs.  Returns {tap: tensor}.
     conv1_1 uses replicate padding (:39,52-59), every other conv zero padding.
+    decisions: None, or {index: ...} from ``decisions_from_maps``: every ReLU keeps the given mask and every max pool
+    the given argmax instead of deciding on this evaluation's values (see there).
     """
     layers = sorted(set(layers))
     h, w = image.shape[2:4]
@@ -83,9 +85,12 @@ def vgg_features(image, weights, layers, pooling='max'):
             else:
                 x = F.conv2d(x, wgt, bias, padding=1)
         elif op == 'relu':
-            x = torch.relu(x)
+            x = torch.relu(x) if decisions is None else x * decisions[idx].to(x.dtype)
         else:
-            if pooling == 'max':
+            if pooling == 'max' and decisions is not None:
+                arg = decisions[idx]
+                x = x.flatten(2).gather(2, arg.flatten(2)).view(arg.shape)
+            elif pooling == 'max':
                 x = F.max_pool2d(x, 2)
             elif pooling == 'average':                    # Scale(AvgPool2d(2), 2.0), :41-46
                 x = F.avg_pool2d(x, 2) * POOL_SCALE['average']
@@ -96,6 +101,22 @@ def vgg_features(image, weights, layers, pooling='max'):
         if idx in layers:
             feats[idx] = x
     return feats
+
+
+def decisions_from_maps(maps, pooling='max'):
+    """The discrete choices of a forward pass, from its ReLU outputs ``maps`` ({relu features index: [1,C,h,w]}, every
+    ReLU up to the deepest one wanted): each ReLU's mask (output > 0) and, for max pooling, each pool's argmax (first
+    maximum of the window, as F.max_pool2d).  ``vgg_features(..., decisions=...)`` then follows the same branches: an
+    evaluation in another precision differs from the one that made ``maps`` by its arithmetic alone, not by the elements
+    whose pre-activation or pool window is within rounding of a tie (a flipped one moves a whole receptive field's worth
+    of gradient)."""
+    out = {}
+    for idx, op, _ in layer_program():
+        if op == 'relu' and idx in maps:
+            out[idx] = maps[idx] > 0
+        elif op == 'pool' and pooling == 'max' and idx - 1 in maps:
+            out[idx] = F.max_pool2d(maps[idx - 1], 2, return_indices=True)[1]
+    return out
 
 
 # ----------------------------------------------------------------------------------------------
@@ -236,11 +257,12 @@ TERM_NAMES = ['content', 'style_relu1_1', 'style_relu2_1', 'style_relu3_1', 'sty
               'style_relu5_1', 'tv']
 
 
-def loss_terms(image, weights, targets, content_weight=0.015, tv_weight=2.0, pooling='max'):
+def loss_terms(image, weights, targets, content_weight=0.015, tv_weight=2.0, pooling='max', decisions=None):
     """SumLoss over [content, 5 x style, tv] with their Scale factors (:198-234,376,427-455).
 
     Returns (list of 7 *weighted* terms in SumLoss order, total)."""
-    feats = vgg_features(image, weights, STYLE_LAYERS + CONTENT_LAYERS, pooling)
+    kw = {} if decisions is None else dict(decisions=decisions)     # (tests substitute a four-argument vgg_features)
+    feats = vgg_features(image, weights, STYLE_LAYERS + CONTENT_LAYERS, pooling, **kw)
     terms = [content_mse(feats[22], targets.content_feat) * (content_weight / len(CONTENT_LAYERS))]
     for layer, lw in zip(STYLE_LAYERS, STYLE_LAYER_WEIGHTS):
         terms.append(style_w2(feats[layer], targets.style[layer]) * lw)
@@ -257,6 +279,16 @@ def loss_and_grad(image, weights, targets, **kw):
     terms, total = loss_terms(img, weights, targets, **kw)
     total.backward()
     return [float(t.detach()) for t in terms], float(total.detach()), img.grad.detach()
+
+
+def term_gradients(image, weights, targets, **kw):
+    """The image gradient of each weighted term ALONE (one forward, seven backward passes through the same graph):
+    what the closure returns when every other term's Scale factor is 0.  Returns (list of 7 weighted terms,
+    list of 7 gradients [1,3,H,W]) in SumLoss order."""
+    img = image.detach().clone().requires_grad_(True)
+    terms, _ = loss_terms(img, weights, targets, **kw)
+    grads = [torch.autograd.grad(t, img, retain_graph=k < len(terms) - 1)[0].detach() for k, t in enumerate(terms)]
+    return [float(t.detach()) for t in terms], grads
 
 
 # ----------------------------------------------------------------------------------------------

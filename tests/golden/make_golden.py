@@ -18,6 +18,9 @@ What is recorded (all fp32, CPU, torch.set_num_threads(8), deterministic):
                the same at BASELINE.json's config sizes (512^2: configs[1], 1024^2: configs[2], 2048^2: configs[3],
                2896 x 2172 (W x H): configs[4]); the inputs are regenerated from seeds by tests/synth.py
                (platform-stable) instead of being stored; above 1024^2 `terms64` comes from a no-grad float64 pass
+  term_grads_tiny
+               eval_tiny's inputs with every Scale factor but one at 0, seven times: each weighted term and its
+               image gradient alone
   iter_tiny    3 full hot-loop iterations (Adam + clamp + EMA) and the scale transition after them
   stylize_e2e  StyleTransfer.stylize() end to end on PIL inputs (2 scales), loss trace + result
   stylize_lbfgs, stylize_init_{gray,uniform,normal,style_stats}
@@ -154,6 +157,27 @@ def case_eval(name, pooling, h, w, style_shapes, style_w, seed, full_grad):
         out['grad_sub'] = grad.flatten()[::7].numpy().copy()
     np.savez_compressed(os.path.join(HERE, f'{name}.npz'), **out)
     print(f'{name}: total={total:.8g} terms={["%.6g" % t for t in terms]} |g|={float(grad.norm()):.6g}')
+
+
+def case_term_grads_tiny():
+    """eval_tiny's inputs through the reference's SumLoss seven times, each time with every Scale factor but one set to 0:
+    the image gradient of each weighted term alone (pins st_oracle.term_gradients' per-term split)."""
+    g = dict(np.load(os.path.join(HERE, 'eval_tiny.npz')))
+    st, _ = make_reference('max')
+    t = lambda key: torch.from_numpy(g[key])                                    # noqa: E731
+    crit = build_crit(st, t('content'), [t('style0')], [float(w) for w in g['style_weights']])
+    scales = [float(m.scale) for m in crit]
+    grads, terms = [], []
+    for k in range(len(crit)):
+        with torch.no_grad():
+            for j, m in enumerate(crit):
+                m.scale.fill_(scales[j] if j == k else 0.0)
+        tk, _, grad, _ = evaluate(st, crit, t('image'))
+        terms.append(tk[k])
+        grads.append(grad.numpy()[0])
+    np.savez_compressed(os.path.join(HERE, 'term_grads_tiny.npz'), grads=np.stack(grads),
+                        terms=np.array(terms, dtype=np.float64), scales=np.array(scales, dtype=np.float64))
+    print('term_grads_tiny: |g_k| =', ['%.4g' % float(np.linalg.norm(x)) for x in grads])
 
 
 def evaluate64_terms(content, style, image):
@@ -559,6 +583,8 @@ CASES = {
     'eval_s128': lambda: case_eval('eval_s128', 'max', 128, 128, [(96, 128), (128, 100)], [0.7, 0.3], seed=4,
                                    full_grad=False),
     'eval_odd181': lambda: case_eval('eval_odd181', 'max', 135, 181, [(181, 140)], [1.0], seed=6, full_grad=False),
+    # each term's image gradient alone at eval_tiny's inputs (reads eval_tiny.npz)
+    'term_grads_tiny': case_term_grads_tiny,
     'eval_512': lambda: case_eval_large('eval_512', 512, seed=40),
     'eval_1024': lambda: case_eval_large('eval_1024', 1024, seed=50),
     # BASELINE configs[3] / configs[4]: ~2 / ~3 CPU-minutes each incl. the float64 values;

@@ -49,6 +49,40 @@ def test_closure_evaluation_matches_reference(name, vgg_weights):
         assert abs(float(feats[layer].double().mean()) - float(g[f'tap{layer}_mean'])) < 1e-6
 
 
+def test_term_gradients_match_reference(vgg_weights):
+    """st_oracle.term_gradients (the per-term checker of tests/test_term_gradients_gpu.py) against the reference's SumLoss
+    with every Scale factor but one set to 0 (term_grads_tiny.npz), at eval_tiny's inputs: each term's value and its image
+    gradient alone, and the seven gradients add up to the reference's whole gradient."""
+    g, ref = load_golden('eval_tiny'), load_golden('term_grads_tiny')
+    targets = O.build_targets(_t(g['content']), [_t(g['style0'])], vgg_weights, list(g['style_weights']))
+    terms, grads = O.term_gradients(_t(g['image']), vgg_weights, targets)
+    assert np.allclose(ref['scales'], [0.015, *O.STYLE_LAYER_WEIGHTS, 2.0], rtol=1e-7, atol=0)
+    assert np.allclose(terms, ref['terms'], rtol=2e-6, atol=0), (terms, ref['terms'])
+    assert ref['grads'].shape == (7, 3, 40, 48)
+    for k, gk in enumerate(grads):
+        err = rel_l2(gk[0], ref['grads'][k])
+        assert err < 1e-5, (O.TERM_NAMES[k], err)
+    assert rel_l2(ref['grads'].astype(np.float64).sum(0), g['grad'][0]) < 1e-6
+
+
+@pytest.mark.parametrize('pooling', ['max', 'l2'])
+def test_oracle_on_its_own_branches_is_the_oracle(pooling, vgg_weights):
+    """vgg_features(..., decisions=decisions_from_maps(its own ReLU outputs)) follows the branches the plain evaluation takes:
+    the same terms and per-term gradients, bit for bit (tests/test_term_gradients_gpu.py evaluates float64 on the HIP
+    plan's branches this way)."""
+    g = load_golden('eval_tiny')
+    targets = O.build_targets(_t(g['content']), [_t(g['style0'])], vgg_weights, pooling=pooling)
+    relus = [idx for idx, op, _ in O.layer_program() if op == 'relu']
+    with torch.no_grad():
+        maps = O.vgg_features(_t(g['image']), vgg_weights, relus, pooling)
+    decisions = O.decisions_from_maps(maps, pooling)
+    assert len(decisions) == 13 + (4 if pooling == 'max' else 0)
+    terms, grads = O.term_gradients(_t(g['image']), vgg_weights, targets, pooling=pooling)
+    terms_p, grads_p = O.term_gradients(_t(g['image']), vgg_weights, targets, pooling=pooling, decisions=decisions)
+    assert terms_p == terms
+    assert all(torch.equal(a, b) for a, b in zip(grads_p, grads))
+
+
 def test_three_iterations_and_scale_transition(vgg_weights):
     g = load_golden('iter_tiny')
     targets = O.build_targets(_t(g['content']), [_t(g['style0'])], vgg_weights)
