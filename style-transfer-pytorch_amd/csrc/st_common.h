@@ -181,7 +181,7 @@ struct ConvProblem {
     int halo_amax_folded;  // strip plans: the caller has dealt with max |halo rows| - either folded it into amax_word
                            // or handed over the bounds the SENDERS measured (below)
     // strip plans, round 5: max |row| of the neighbours' halo rows as raw bits, measured by the sender while it packed the
-    // rows and shipped in the same message (st_api.hip halo_exchange: a 16-float trailer in front of the top rows / behind
+    // rows and shipped in the same message (st_strip.hip halo_exchange: a 16-float trailer in front of the top rows / behind
     // the bottom rows).  The kernels take max(amax_word, these) - no launch between the halo's arrival and its consumer.
     const unsigned int* halo_bound_up;
     const unsigned int* halo_bound_down;

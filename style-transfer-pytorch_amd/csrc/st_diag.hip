@@ -214,7 +214,7 @@ int run_wino_rate(int, int, double*, hipStream_t) {
 }
 #endif
 
-// ---- which streams share a hardware queue with a given stream?  (probe_queue_sharing, used by st_api.hip) ----------------
+// ---- which streams share a hardware queue with a given stream?  (probe_queue_sharing, used by st_closure.hip) -----------
 // ROCm deals HIP streams to GPU_MAX_HW_QUEUES (default 4) hardware queues and streams on one queue run in submission order.
 // A kernel that spins on a host-mapped flag is put on `ref`, then TWO one-store marker kernels on every candidate.  The
 // first marker of a stream carries no dependency and runs beside the spinner even on a shared queue; the second depends on

@@ -598,7 +598,7 @@ __device__ __forceinline__ void chain_body(const NsChainJob& job, int wg, Lds& l
 }
 
 // One wave per SIMD (~290 registers): ONE workgroup of a chain kernel per CU.  The launcher's callers therefore keep the
-// workgroups of all chain kernels that can be in flight at once <= the CU count (st_api.hip: ST_NS_CHAIN's head mask) - two
+// workgroups of all chain kernels that can be in flight at once <= the CU count (st_closure.hip: ST_NS_CHAIN's head mask) - two
 // persistent kernels that each hold some CUs and wait for the rest would wait for each other.
 template <bool CACHED>
 __device__ __forceinline__ void chain_kernel_body(const NsChainLaunch& launch, Lds& lds) {
@@ -629,13 +629,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(128))) void ns_
 
 int ns_chain_mask() {
     // bit 0: the three shallow heads (one launch), bit 1: relu4_1, bit 2: relu5_1, bit 3: the standalone operators
-    static Option on("ST_NS_CHAIN", 0);
+    static Option on("ST_NS_CHAIN", 0);           // 0 (default): one launch per product (rounds 1 - 4); see profiles/r05_ns_chain.md
     return on.get();
 }
-bool ns_chain_enabled() {
-    static Option on("ST_NS_CHAIN", 0);           // 0 (default): one launch per product (rounds 1 - 4); see profiles/r05_ns_chain.md
-    return on.get() != 0;
-}
+bool ns_chain_enabled() { return ns_chain_mask() != 0; }
 
 int ns_chain_sync_uints() { return kSyncUints; }
 

@@ -1,0 +1,278 @@
+// Internal to libst_amd.so: the VGG-19 program, the plan's nodes and style heads, st_net / st_plan, and the plan helpers
+// that more than one of st_api.hip, st_closure.hip, st_strip.hip and st_range_guard.hip call.
+#pragma once
+
+#include <functional>
+#include <unordered_map>
+#include <vector>
+
+#include "../../include/st_amd.h"
+#include "st_common.h"
+
+namespace st {
+
+// torchvision vgg19 cfg "E" truncated at features[29] (reference style_transfer.py:35)
+struct OpDesc {
+    int kind;        // 0 = conv(+ReLU), 1 = pool
+    int index;       // conv number 0..12 or pool number 0..3
+    int feat_index;  // features[] index of the produced tap (the ReLU for convs, the pool itself)
+    int cin, cout;
+};
+const OpDesc kProgram[] = {
+    {0, 0, 1, 3, 64},     {0, 1, 3, 64, 64},    {1, 0, 4, 64, 64},    {0, 2, 6, 64, 128},
+    {0, 3, 8, 128, 128},  {1, 1, 9, 128, 128},  {0, 4, 11, 128, 256}, {0, 5, 13, 256, 256},
+    {0, 6, 15, 256, 256}, {0, 7, 17, 256, 256}, {1, 2, 18, 256, 256}, {0, 8, 20, 256, 512},
+    {0, 9, 22, 512, 512}, {0, 10, 24, 512, 512}, {0, 11, 26, 512, 512}, {1, 3, 27, 512, 512},
+    {0, 12, 29, 512, 512},
+};
+constexpr int kNumOps = sizeof(kProgram) / sizeof(kProgram[0]);
+const int kStyleFeat[5] = {1, 6, 11, 20, 29};     // style_transfer.py:317
+const int kStyleConv[5] = {0, 2, 4, 8, 12};
+constexpr int kContentConv = 9;                   // relu4_2 = features[22]
+constexpr float kCovEps = 1e-4f;                  // StyleLossW2 eps (style_transfer.py:152)
+
+struct Node {
+    float* y = nullptr;   // activation (post-ReLU conv output or pooled map) [c][h][w]
+    float* g = nullptr;   // gradient w.r.t. y, same shape (allocated lazily)
+    float* yhalo = nullptr;   // strip mode: [2][c][w] rows of the neighbours (only if a conv reads this node)
+    float* ghalo = nullptr;   // strip mode: [2][c][w] masked gradient rows of the neighbours (conv outputs)
+    int c = 0, h = 0, w = 0;
+    int hg = 0;               // global height at this level (== h when not sharded)
+    bool pooled_by_conv = false;   // forward, strip plans: this conv's epilogue wrote the following max pool
+    unsigned char* pool_code = nullptr;   // conv feeding a max pool: argmax + mask codes of the pooled windows (closure only)
+    bool coded = false;            // this pass wrote pool_code INSTEAD of y (ConvProblem::pool_code)
+    // device words (raw float bits) bounding max |y| / max |g| for the fp16x3 convolutions' scales: written by
+    // the kernels that finalise y / g (amax_commit), zeroed at the start of every forward.  Pooled maps reuse
+    // their input's y word, and a conv feeding a pool reuses the pool's g word (see scale_exp's spare bit).
+    unsigned int* y_amax = nullptr;
+    unsigned int* g_amax = nullptr;
+    size_t count() const { return (size_t)c * h * w; }
+};
+
+struct StyleHead {
+    int n = 0;            // channels
+    long long npix = 0;        // GLOBAL pixel count of the tap (normalisation of the moments)
+    long long npix_local = 0;  // pixels held by this plan (== npix unless strip-sharded)
+    unsigned int* s_amax = nullptr;   // fp16x3: bound on max |ssym| of this pass (one of plan->amax_word's bounds)
+    bool target_set = false;
+    bool joined_in_build = false;    // phase construction: this head's broadcast + gradient step have been placed
+    // targets
+    float *mean_t = nullptr, *cov_t = nullptr, *root_t = nullptr;
+    // per-iteration
+    float *mean = nullptr, *srm = nullptr, *cov = nullptr, *tmat = nullptr, *mmat = nullptr, *root = nullptr,
+          *gm = nullptr, *dt = nullptr, *dcov = nullptr, *ssym = nullptr, *bvec = nullptr, *gdiag = nullptr;
+    float* conv_scratch = nullptr;     // split-K workspace of the head's 1x1 gradient conv (small taps only)
+    NSWorkspace ns{};
+    GramWorkspace gram{};
+    bool allocated = false;
+};
+
+struct ProfileEvent {
+    hipEvent_t start, stop;
+    double flops;
+};
+
+// HBM-bound kernels of the step, timed like the conv launches when profiling is on (bench.py `roofline_hbm`):
+// category, algorithmic bytes of the launch (operands read once + results written once)
+enum HbmCat { HBM_CONV1_FWD = 0, HBM_CONV1_DGRAD, HBM_POOL_BWD, HBM_ADAM, HBM_TV, HBM_GRAM1, HBM_CONTENT, HBM_HEAD_1X1, HBM_CATS };
+struct HbmEvent {
+    hipEvent_t start, stop;
+    int cat;
+    double bytes;
+};
+
+}  // namespace st
+
+struct st_net {
+    int pooling = 0;
+    float* w_first = nullptr;        // conv1_1 weight, torch layout [64][3][3][3]
+    float w_first_l1max = 0.f;       // max over output channels of sum |w|, and max |bias|: the a-priori bound of relu1_1 per
+    float b_first_max = 0.f;         // pixel block that the fused conv1_1 + Gram kernel scales its fp16 planes by
+    float* bias[13] = {};
+    float* w_fwd[13] = {};           // [9][Cin][Cout]   (convs 1..12)
+    float* w_bwd[13] = {};           // [9][Cout][Cin], taps rotated (convs 1..12)
+    int conv_planes = 0;             // 0: fp32 MFMA; 2 / 3 planes: split-precision convolutions (st_common.h)
+    int conv_elem = 0;               // plane element type: 0 bf16, 1 fp16 (fp16x3)
+    void* ws_fwd[13] = {};           // bf16 planes of the forward weights (convs 1..12)
+    void* ws_bwd[13] = {};           // bf16 planes of the data-gradient weights
+    // fp16x3 networks, dynamic-range guard: a convolution whose weights carry a channel far above the layer's median
+    // (the signature of weights that compensate a tiny-valued operand channel) runs in bf16x6 instead - three bf16
+    // planes, 8-bit exponents, no per-tensor scale to fall out of (see range_guard in net_fill)
+    int wide_fwd[13] = {};           // 1: this layer's forward runs bf16x6
+    int wide_bwd[13] = {};           // 1: its data gradient does
+    void* wsx_fwd[13] = {};          // bf16x6 planes of the flagged layers
+    void* wsx_bwd[13] = {};
+    float* w_torch[13] = {};         // the weights as given ([Cout][Cin][3][3]): source of planes built after creation, when
+                                     // the activation-aware guard (st_plan_range_guard) flags a layer
+    int guard_fwd[13] = {};          // 1: flagged by the activation-aware guard (subset of wide_*)
+    int guard_bwd[13] = {};
+};
+
+struct st_plan {
+    const st_net* net = nullptr;
+    int H = 0, W = 0;
+    st::Node conv[13];
+    st::Node pool[4];
+    bool grads_allocated = false;
+    float* content_target = nullptr;
+    bool content_set = false;
+    st::StyleHead style[5];
+    float content_weight = 0.015f;
+    float style_weight[5] = {256.f / 341, 64.f / 341, 16.f / 341, 4.f / 341, 1.f / 341};
+    float tv_weight = 2.0f;
+    float* grad_img = nullptr;       // [3][H][W] internal gradient for st_plan_step
+    float* losses = nullptr;         // [8] device
+    float* red_partials = nullptr;   // scratch for two-level reductions: TV [0, 4 kStreamBlocks), content MSE after it
+    float* guard_scratch[3] = {nullptr, nullptr, nullptr};      // plan_range_guard: three maps of the largest activation ...
+    float* guard_sums = nullptr;                                // ... and range_diff_kernel's per-block partial sums
+    unsigned int* tickets = nullptr; // zeroed device words of the "last block finishes the sum" kernels (self-resetting)
+    float* conv_scratch = nullptr;   // split-K workspace of the trunk convolutions (main stream only)
+    float* dp_scratch = nullptr;     // conv1_1 data gradient on the padded domain, dp_parts x 3 (H + 2) (W + 2)
+    int dp_parts = 1;                // channel slices of that kernel (conv_first_dgrad_parts of the GLOBAL shape)
+    float* amax_word = nullptr;      // 64 bounds of kAmaxWordUints: Node::y_amax [conv], +16 g_amax [conv], +32 g_amax [pool], +48 StyleHead::s_amax
+    long long bytes = 0;
+    std::vector<void*> allocations;
+    // strip sharding; strip == false -> the plan owns the whole image
+    bool strip = false;
+    int Hg = 0, row0 = 0, has_up = 0, has_down = 0;
+    float* img_halo = nullptr;       // [2][3][W]
+    // packed boundary rows, 64 * W floats each + the 16-float trailer whose first word is max |row| as raw bits (kHaloTrailer):
+    // send_up = [rows | trailer] (lands as the upper neighbour's BOTTOM halo), send_down = [trailer | rows] (the lower
+    // neighbour's TOP halo) - so that a halo block [trailer | top rows | bottom rows | trailer] receives either message contiguously
+    float* send_up = nullptr;
+    float* send_down = nullptr;
+    unsigned int* pack_scratch = nullptr;   // launch_pack_rows' block maxima + ticket
+    float* lossbuf = nullptr;        // [0] content sum of squares, [1..4] TV sums (all-reduced)
+    float* gram_raw[5] = {};         // per head [C*C + C] raw moment sums (all-reduced); one contiguous block
+    long long gram_total = 0;        // floats in that block
+    // strip closure, device-ordered exchanges: halo rows travel on comm_stream while the interior rows of the consuming
+    // convolution are computed on the caller's stream (pack_done: the boundary rows are packed; halo_landed: the
+    // exchange has been enqueued behind it)
+    hipStream_t comm_stream = nullptr;
+    bool comm_stream_borrowed = false;     // from the process-wide probed set (shared_head_streams)
+    hipStream_t chain_stream = nullptr;    // strip plans, compact layout: the owned heads' Newton-Schulz chains (else they run
+                                           // on the head's own stream)
+    hipEvent_t moments_ready[5] = {}, chain_done[5] = {};
+    hipEvent_t pack_done = nullptr, halo_landed = nullptr;
+    unsigned int* halo_bound = nullptr;     // operand bound of a boundary launch: the operand's own bound + its halo rows'
+
+    int rank = 0, world = 1;         // position of this strip among the ranks (NS-chain ownership)
+    float* head_result[5] = {};      // per head [C*C + C + 64]: Ssym | b | weighted loss term - what the owner broadcasts
+    struct Phase {
+        std::function<int(hipStream_t)> run;
+        st_exchange ex;
+        const float* halo = nullptr;         // the halo block a kind-1 exchange fills (finish_phases)
+    };
+    // halo blocks whose consumer is NOT cut into interior + boundary launches: their exchange is issued on the caller's
+    // stream, in line between the pack kernel and the consumer (add_strip_conv, finish_phases)
+    std::unordered_map<const float*, bool> halo_inline;
+    std::vector<Phase> phases;
+    size_t phase_pos = 0;
+    const float* ph_image = nullptr;
+    float* ph_grad = nullptr;
+    int ph_last_layer = -1;
+    unsigned ph_option_gen = 0;
+    // Side streams: the five W2 style heads are ~60 dependent small launches each (latency bound),
+    // so each runs on its own stream, forked when its tap is ready in the forward pass and joined
+    // just before the backward pass needs that tap's gradient.  They overlap the trunk and each other.
+    hipStream_t head_stream[5] = {};
+    bool head_stream_owned[5] = {};        // false: borrowed from the process-wide set (shared_head_streams)
+    hipEvent_t tap_ready[5] = {};
+    hipEvent_t head_done[5] = {};
+    bool streams_ready = false;
+    int device = 0;
+    // hipGraph replay of the closure.  The ~430 launches of one closure (6 streams) are captured once
+    // per (image, grad, losses) pointer triple on an internal stream and replayed; the caller's stream
+    // (possibly the legacy null stream, which cannot be captured) is bridged with two events.
+    // OFF by default: measured on ROCm 7.2 / MI355X the replay of this 6-branch graph is bit-identical
+    // but slower than eager launches (512^2: 5.9 vs 5.0 ms per step, 128^2: 3.1 vs 2.1 ms).
+    bool graph_enabled = false;
+    hipStream_t main_stream = nullptr;
+    bool gram1_fused = false;              // this pass's conv1_1 launch left relu1_1's partial moments (run_forward)
+    int gram1_splits = 0;
+    bool compact_streams = false;          // ensure_streams: only the streams that carry work exist
+    bool head4_on_caller = false;          // relu5_1's head runs on the caller's stream (shared_head_streams found no sharer)
+    std::vector<hipStream_t> junk_streams;  // ST_STREAM_DUMMIES (experiments)
+    hipEvent_t bridge_in = nullptr, bridge_out = nullptr;
+    // TV (needs only the image) and the content MSE run beside the trunk on one auxiliary stream
+    hipStream_t aux_stream = nullptr;
+    hipEvent_t aux_in = nullptr, aux_fwd = nullptr, tv_done = nullptr, content_done = nullptr;
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t graph_exec = nullptr;
+    const float* gk_image = nullptr;
+    float* gk_grad = nullptr;
+    float* gk_losses = nullptr;
+    int gk_seen = 0;
+    bool capturing = false;
+    // ST_AMD_TIMELINE=1: timing events at step start / forward end / each head done / backward end
+    bool timeline = false;
+    hipEvent_t tl_start = nullptr, tl_fwd = nullptr, tl_head[5] = {}, tl_bwd = nullptr;
+    hipEvent_t tl_h4[4] = {};        // relu5_1's head: chain start, after NS forward, after NS backward, (end = tl_head[4])
+    hipEvent_t tl_h3[4] = {};        // the same for relu4_1's head
+    int tl_count = 0;
+    // profiling
+    bool profiling = false;
+    std::vector<st::ProfileEvent> events;
+    size_t events_used = 0;
+    std::vector<st::HbmEvent> hbm_events;
+    size_t hbm_used = 0;
+    long long prof_launches = 0;
+    double prof_ms = 0, prof_flops = 0;
+    // st_plan_step: the losses' total and the clearing of the fp16x3 operand bounds ride in the update kernel (AdamTail)
+    bool defer_sum = false;          // loss_and_grad leaves the total to the caller
+    bool amax_clean = false;         // the update kernel has cleared amax_word: the next run_forward skips its memset
+    const st::FoldUpdate* fold_update = nullptr;     // st_plan_step: conv1_1's fold kernel applies the update (and the tail)
+    bool fold_updated = false;       // ... and has done so in this closure
+};
+
+namespace st {
+
+constexpr int kHaloTrailer = 16;            // floats; word 0 = the sender's max |row| (raw bits), the rest unused (64-byte alignment)
+
+// ---- st_closure.hip
+int plan_alloc(st_plan* p, float** out, size_t floats);
+int conv_launch_profiled(st_plan* p, const ConvProblem& prob, hipStream_t s, double flops_fraction = 1.0);
+template <class F>
+int hbm_profiled(st_plan* p, int cat, double bytes, hipStream_t s, F&& launch) {
+    if (!p->profiling) return launch();
+    if (p->hbm_used == p->hbm_events.size()) {
+        HbmEvent ev{};
+        ST_HIP(hipEventCreate(&ev.start));
+        ST_HIP(hipEventCreate(&ev.stop));
+        p->hbm_events.push_back(ev);
+    }
+    HbmEvent& ev = p->hbm_events[p->hbm_used++];
+    ev.cat = cat;
+    ev.bytes = bytes;
+    ST_HIP(hipEventRecord(ev.start, s));
+    const int rc = launch();
+    ST_HIP(hipEventRecord(ev.stop, s));
+    return rc;
+}
+
+void invalidate_graph(st_plan* p);
+int ensure_streams(st_plan* p, hipStream_t caller = nullptr);
+int ensure_style_alloc(st_plan* p, int idx);
+int ensure_grad_alloc(st_plan* p);
+int moments_of_tap(st_plan* p, int idx, float* mean_out, float* srm_out, hipStream_t s, float* cov_out = nullptr);
+int moment_sums_of_tap(st_plan* p, int idx, float* sums, hipStream_t s);
+int style_head_chain(st_plan* p, int idx, hipStream_t s, bool cov_ready = false);
+int style_head_gradient(st_plan* p, int idx, hipStream_t s);
+int join_head_for_conv(st_plan* p, int conv_index, hipStream_t s);
+int require_targets(const st_plan* p);
+int run_forward(st_plan* p, const float* image, int last_layer, hipStream_t s, bool fork_heads = false);
+int loss_and_grad(st_plan* p, const float* image, float* grad_out, float* losses_out, hipStream_t s);
+int closure_entry(st_plan* p, const float* image, float* grad_out, float* losses_out, hipStream_t s);
+// the trunk's 3x3 launches, described once for both closures and the range guard (kProgram[i] is a conv, i > 0)
+bool pool_follows(const st_plan* p, int i, int last_layer);
+void forward_conv(const st_plan* p, int i, ConvProblem& c);
+bool fuse_pool(ConvProblem& c, Node& n, bool fork_heads, const PcOverlap* cut);
+void dgrad_conv(const st_plan* p, int i, ConvProblem& c);
+
+// ---- st_strip.hip
+int halo_alloc(st_plan* p, float** out, size_t floats);
+
+// ---- st_range_guard.hip
+int range_guard(st_net* net, int conv, const float* weight_dev, int cin, int cout);
+
+}  // namespace st

@@ -144,7 +144,7 @@ __global__ __launch_bounds__(WV * 64) void gemm_batch_kernel(GemmBatch batch) {
 }
 
 // Problems of DIFFERENT sizes (64 / 128 / 256) in one launch: the recurrence steps of the three shallow style heads in
-// lockstep (st_api.hip).  8 waves for every size (k range of a wave: 8 / 16 / 32); blocks beyond a problem's tile count
+// lockstep (st_closure.hip).  8 waves for every size (k range of a wave: 8 / 16 / 32); blocks beyond a problem's tile count
 // leave at once.
 __global__ __launch_bounds__(512) void gemm_mixed_kernel(GemmBatch batch) {
     __shared__ float red[8][16][64];
@@ -559,11 +559,20 @@ int ns_chain_check(NSWorkspace& ws, const char* what) {
     return 0;
 }
 
+// ST_NS_FULL_BACKWARD=1: the reference's full Lyapunov recurrence even for a gradient that is a multiple of I
+static bool ns_full_backward() {
+    static Option opt("ST_NS_FULL_BACKWARD", 0);
+    return opt.get() != 0;
+}
+// ST_NS_F16_FWD=1: the forward chains in fp16x3 where ns_f16_applies
+static bool ns_f16_forward() {
+    static Option opt("ST_NS_F16_FWD", 0);
+    return opt.get() != 0;
+}
+
 // both recurrences of a head in one launch: only in the shipped arithmetic (fp32 forward chain, reduced backward recurrence)
 bool ns_chain_combined() {
-    static Option full("ST_NS_FULL_BACKWARD", 0);
-    static Option f16_fwd("ST_NS_F16_FWD", 0);
-    return ns_chain_enabled() && !full.get() && !f16_fwd.get();
+    return ns_chain_enabled() && !ns_full_backward() && !ns_f16_forward();
 }
 
 int ns_sqrt_chain(const float* const* m, float* const* root, float* const* grad_m, const int* n, NSWorkspace* const* ws,
@@ -601,8 +610,7 @@ int ns_sqrt_forward(const float* m, float* root, int n, NSWorkspace& ws, hipStre
     // exactly, six plane products down to 2^-22 of the result) shifted tr(root) by the SAME amount as two planes
     // (rank-deficient n = 512: +1.45e-5 for both against +6.5e-7 for the fp32 chain, profiles/r03_head_window.md): the
     // bias sits in how the 16-bit matrix instruction accumulates its 16 products, which no operand splitting removes.
-    static Option f16_fwd("ST_NS_F16_FWD", 0);
-    if (f16_fwd.get() && ns_f16_applies(n) && ws.planes) return ns_sqrt_forward_f16(m, root, n, ws, s);
+    if (ns_f16_forward() && ns_f16_applies(n) && ws.planes) return ns_sqrt_forward_f16(m, root, n, ws, s);
     // round 5: the whole recurrence as one persistent launch on upper-triangle tile pairs (st_nschain.hip)
     if ((ns_chain_mask() & 8) && ws.chain_sync) {
         NsChainLaunch launch{};
@@ -776,8 +784,7 @@ int ns_sqrt_backward(const float* root, const float* grad_root, const float* gra
                      NSWorkspace& ws, hipStream_t s, const W2LossJob* loss, int root_partials) {
     ST_REQUIRE(!loss || (grad_diag && loss->gdiag_out == grad_diag), "ns backward: a W2 job defines the diagonal seed it rides with");
     {
-        static Option full_opt("ST_NS_FULL_BACKWARD", 0);
-        if (grad_diag && !full_opt.get() && (ns_chain_mask() & 8) && ws.chain_sync) {
+        if (grad_diag && !ns_full_backward() && (ns_chain_mask() & 8) && ws.chain_sync) {
             NsChainLaunch launch{};
             launch.count = 1;
             NsChainJob& j = launch.job[0];
@@ -788,7 +795,7 @@ int ns_sqrt_backward(const float* root, const float* grad_root, const float* gra
             if (loss) j.loss = *loss;
             return launch_ns_chain(launch, s);
         }
-        if (grad_diag && !full_opt.get() && ns_f16_applies(n) && ws.planes)
+        if (grad_diag && !ns_full_backward() && ns_f16_applies(n) && ws.planes)
             return ns_sqrt_backward_diag_f16(root, grad_diag, grad_m, n, ws, s, loss, root_partials);
     }
     // norm_z = ||z||_F; a = z / norm_z; q = grad / norm_z                        (sqrtm.py:38-41)
@@ -801,9 +808,7 @@ int ns_sqrt_backward(const float* root, const float* grad_root, const float* gra
     // is identically zero (a is symmetric up to rounding; what the reference accumulates there is O(eps) noise)
     // and the step reduces to q <- q (3I - a a) / 2: three products per step instead of six.  The general
     // operator (grad_root, st_op_sqrtm_ns_backward) keeps the full recurrence.  ST_NS_FULL_BACKWARD=1 forces it.
-    static Option force_full_opt("ST_NS_FULL_BACKWARD", 0);
-    const bool force_full = force_full_opt.get() != 0;
-    const bool reduced = grad_diag != nullptr && !force_full;
+    const bool reduced = grad_diag != nullptr && !ns_full_backward();
     for (int it = 0; it < 12; ++it) {
         const bool last = (it == 11);
         GemmBatch b1{};

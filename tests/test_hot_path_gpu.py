@@ -347,7 +347,7 @@ def test_closure_with_six_decades_of_channel_scales(pooling, vgg_weights):
                                                                               pooling=pooling), pooling=pooling)
     net, plan = _build_plan(hip, spread, content, [style], [1.0], pooling=pooling, precision='fp16x3')
     name = 'spread256/fp16x3' if pooling == 'max' else f'spread256/fp16x3/{pooling}'
-    # the range guard (st_api.hip range_guard) must have recognised the compensating weights: forward of the conv AFTER a
+    # the range guard (st_range_guard.hip range_guard) must have recognised the compensating weights: forward of the conv AFTER a
     # rescaled layer (its input channels carry 1 / s), data gradient of the rescaled layer itself (its output channels
     # carry s) run bf16x6 - and with normalised weights nothing does
     wide_f, wide_b = net.wide_layers()

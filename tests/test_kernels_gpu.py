@@ -439,6 +439,29 @@ def test_winograd_conv_data_gradient_with_the_plan_epilogue(cin, cout, h, w):
     assert bool((out.cpu()[mask <= 0] == 0).all())
 
 
+def test_refused_winograd_calls_leave_no_device_memory_behind():
+    """A default library refuses operator precision 5 (the Winograd form) with an error that names --experiments, before the
+    operator allocates anything: dozens of refused calls leave the device's free memory where it was.  (Each refused call
+    used to keep its weight, scratch and bound buffers: > 32 MiB.)"""
+    hip = _hip()
+    if hip.has_experiments():
+        pytest.skip('an --experiments library serves precision 5')
+    x = torch.randn((1, 256, 32, 32), device=DEV)
+    wt = torch.randn((256, 256, 3, 3), device=DEV)
+    b = torch.zeros(256, device=DEV)
+    with pytest.raises(hip.HipLibraryError, match='--experiments'):      # (warm-up: torch's cached block for the output)
+        hip.op_conv3x3(x, wt, b, True, 5)
+    torch.cuda.synchronize()
+    free_before = torch.cuda.mem_get_info(DEV)[0]
+    for _ in range(40):
+        with pytest.raises(hip.HipLibraryError, match='--experiments'):
+            hip.op_conv3x3(x, wt, b, True, 5)
+    torch.cuda.synchronize()
+    free_after = torch.cuda.mem_get_info(DEV)[0]
+    print(f'[leak] 40 refused precision-5 calls: free device memory {free_before / 2**20:.1f} -> {free_after / 2**20:.1f} MiB')
+    assert free_after >= free_before - (4 << 20), (free_before, free_after)      # (slack far below one leaked call)
+
+
 @pytest.mark.parametrize('n', [64, 128, 256, 512])
 @pytest.mark.parametrize('kind', ['well_conditioned', 'rank_deficient'])
 def test_persistent_chain_kernel_against_the_launch_per_product_chains(n, kind):

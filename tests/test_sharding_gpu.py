@@ -79,7 +79,7 @@ def test_sharded_pooling_modes_match_unsharded(pooling, h, w, world, vgg_weights
 
 def test_halo_bounds_travel_with_the_rows(vgg_weights):
     """fp16x3: the consumer of a halo row scales its operand by max(|operand|, |halo rows|).  The sender measures its rows while
-    it packs them and ships the word in the message's trailer (csrc/st_api.hip halo_exchange); the round-4 form measured them on
+    it packs them and ships the word in the message's trailer (csrc/st_strip.hip halo_exchange); the round-4 form measured them on
     the receiver (ST_STRIP_HALO_BOUND=0: a copy + an amax launch per exchange).  Same maxima, same exponents: the closure must
     agree bit for bit - also where the bound matters, an image whose upper strip is 1000 x darker than the rows below it."""
     from style_transfer import _hip as hip
