@@ -170,6 +170,17 @@ const SharedStreams* shared_head_streams(int device, hipStream_t caller, int ord
     return &set;
 }
 
+// Flags of the events that order this device's streams among themselves (tap_ready, head_done, aux_*, tv_done, ...).
+// Recorded without hipEventDisableSystemFence, each of them puts a barrier packet with a SYSTEM-scope release on its queue:
+// the eight L2s are written back and the next kernel of that queue starts behind it - on the trunk's queue between two
+// dependent convolutions.  Their consumers are kernels of the same device, which the producing kernel's own agent-scope
+// release and the consumer's agent-scope acquire already serve; the host reads results behind a stream synchronise, which
+// releases to the system itself.  ST_EVENT_SYSTEM_FENCE=1: the former flavour (A/B, profiles/trunk_boundaries.md).
+unsigned order_event_flags() {
+    static Option fence_opt("ST_EVENT_SYSTEM_FENCE", 0);
+    return fence_opt.get() != 0 ? hipEventDisableTiming : (hipEventDisableTiming | hipEventDisableSystemFence);
+}
+
 int ensure_streams(st_plan* p, hipStream_t caller) {
     if (p->streams_ready) return 0;
     ST_HIP(hipGetDevice(&p->device));
@@ -228,13 +239,14 @@ int ensure_streams(st_plan* p, hipStream_t caller) {
             p->head_stream_owned[i] = true;
         }
     }
+    const unsigned flags = order_event_flags();
     for (hipEvent_t* e : {&p->aux_in, &p->aux_fwd, &p->tv_done, &p->content_done})
-        ST_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
+        ST_HIP(hipEventCreateWithFlags(e, flags));
     for (int i = 0; i < 5; ++i) {
-        ST_HIP(hipEventCreateWithFlags(&p->tap_ready[i], hipEventDisableTiming));
-        ST_HIP(hipEventCreateWithFlags(&p->head_done[i], hipEventDisableTiming));
-        ST_HIP(hipEventCreateWithFlags(&p->moments_ready[i], hipEventDisableTiming));
-        ST_HIP(hipEventCreateWithFlags(&p->chain_done[i], hipEventDisableTiming));
+        ST_HIP(hipEventCreateWithFlags(&p->tap_ready[i], flags));
+        ST_HIP(hipEventCreateWithFlags(&p->head_done[i], flags));
+        ST_HIP(hipEventCreateWithFlags(&p->moments_ready[i], flags));
+        ST_HIP(hipEventCreateWithFlags(&p->chain_done[i], flags));
     }
     const char* tl = option_env("ST_AMD_TIMELINE");
     if (tl && atoi(tl) == 1) {

@@ -432,6 +432,18 @@ bool conv_fat_applies(const ConvProblem& p) {
            (long long)9 * (p.cin / SK) * p.cout * 32 * 2 < (1ll << 31);
 }
 
+// the current device's CU count, asked of the runtime once per device: this rule runs on every eligible launch of the hot path
+static int fat_n_cu() {
+    static std::atomic<int> cached[16];
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return 256;
+    int cus = cached[dev].load(std::memory_order_relaxed);
+    if (cus) return cus;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 8) cus = 256;
+    cached[dev].store(cus, std::memory_order_relaxed);
+    return cus;
+}
+
 // Where this form is the faster one (profiles/r06_fat_conv.md): layers of >= 128 channels on both sides whose (128 co x 512 px)
 // tiles run in at least two WHOLE rounds of the chip (one workgroup per CU at a time, no persistent loop: a partial last round
 // idles CUs, and a single round exposes the prologue) and whose K loop has >= 16 chunks - conv3_x, conv4_x at 2048^2: 1.04 -
@@ -446,8 +458,7 @@ bool conv_fat_preferred(const ConvProblem& p) {
     if (mode == 2) return true;
     if (p.cout % 128 != 0 || p.cin < 256) return false;      // (>= 16 chunks per tile: a short K loop exposes the tile's prologue and epilogue)
     const long long wgs = (long long)ceil_div(p.width, 32) * ceil_div(p.height, 16) * (p.cout / 128);
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 8) cus = 256;
+    const int cus = fat_n_cu();
     static Option rounds_opt("ST_CONV_FAT_ROUNDS", 1);     // whole rounds of workgroups a launch must have (tools/fat_rounds_ab.sh)
     return wgs >= (long long)rounds_opt.get() * cus && wgs % cus == 0;
 }
