@@ -154,6 +154,48 @@ int st_plan_apply_update(st_plan* plan, float* image, const float* grad, float* 
                          double ema_decay, void* stream);
 
 /*
+ * optimizer='lbfgs' (style_transfer.py:464-465, 479-486): torch.optim.LBFGS(params, max_iter=1, history_size=10) with its
+ * defaults lr=1, tolerance_grad=1e-7, tolerance_change=1e-9, line_search_fn=None - one quasi-Newton update per call, fixed
+ * step length - as three launches and no host decision (csrc/st_lbfgs.hip).  torch/optim/lbfgs.py `step`, case by case:
+ *   |g|_inf <= tolerance_grad: return (n_iter is not advanced, nothing of the state moves);
+ *   first iteration: d = -g, t = min(1, 1 / |g|_1); afterwards t = 1 and d from the two-loop recursion over the pairs
+ *   (y = g - g_prev, s = t d) that passed `ys > 1e-10` (at most 10, oldest dropped), H_diag = ys / y.y of the newest;
+ *   g.d > -tolerance_change: d, t and g_prev are recorded, the parameter does not move;   otherwise p.add_(d, alpha=t).
+ * The recursion is evaluated on the Gram matrix of [s_i | y_i | g] in double; every launch adds in a fixed order, so a
+ * sequence of steps is bit-identical from run to run.
+ *
+ * State: ONE caller-owned device buffer of st_lbfgs_state_bytes(count) bytes for a parameter of `count` floats, 16-byte
+ * aligned (control block, per-workgroup partial sums, 2 * 11 + 1 parameter-sized slots: the ring of pairs with the candidate's
+ * spare slot, and g_prev).  A buffer whose first 4096 bytes are zero is a fresh optimiser (st_lbfgs_reset zeroes them on
+ * `stream`); the reference makes a new LBFGS per scale (:464-465).  Between the first and the second launch the three new
+ * rows of the Gram matrix and |g|_1 are one contiguous block of 70 doubles at byte 192 of the state, |g|_inf the double
+ * behind them: the place of an all-reduce when the parameter is cut into strips.
+ */
+long long st_lbfgs_state_bytes(long long count);
+int st_lbfgs_reset(void* state, long long count, void* stream);
+/*
+ * One LBFGS.step on an externally supplied gradient, then - when ema_value is not NULL - EMA.update(image) (:250-253,
+ * decay rounded to fp32 as in st_plan_step); no clamp (:482-483).  The L-BFGS counterpart of st_plan_apply_update.
+ * image, grad, ema_value: `count` floats each; grad must stay untouched until the call's last launch has run.
+ */
+int st_lbfgs_update(void* state, long long count, float* image, const float* grad, float* ema_value, double ema_decay,
+                    void* stream);
+/*
+ * One full iteration of the hot loop for optimizer='lbfgs' (style_transfer.py:472-486): closure, LBFGS.step, EMA.update.
+ * The counterpart of st_plan_step; `state` was sized for 3 * H * W floats.  losses_out as in st_plan_loss_and_grad (may be
+ * NULL); the loss is the one at the iterate BEFORE the move, as LBFGS.step returns it.
+ */
+int st_plan_lbfgs_step(st_plan* plan, float* image, void* state, float* ema_value, double ema_decay, float* losses_out,
+                       void* stream);
+/*
+ * Read-back of the optimiser's counters after the work on `stream` has finished (synchronous; tests and diagnostics):
+ * n_iter and history = len(old_dirs) of LBFGS's state; of the LAST step: exit_code (0 = moved, 1 = the tolerance_grad
+ * return, 2 = the tolerance_change break), accepted (its pair entered the history), t and gtd = g.d.  Any pointer may be NULL.
+ */
+int st_lbfgs_info(const void* state, long long count, int* n_iter, int* history, int* exit_code, int* accepted, double* t,
+                  double* gtd, void* stream);
+
+/*
  * Spatial strip sharding (replaces the reference's 2-device layer split, style_transfer.py:326-333).
  * A strip plan owns image rows [row_begin, row_end) of a global_height x width image; row_begin and
  * row_end must be multiples of 16 (row_end may instead equal global_height).  Its closure is a sequence

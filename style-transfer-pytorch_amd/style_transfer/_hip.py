@@ -62,6 +62,11 @@ def _declare(lib):
         'st_plan_loss_and_grad': (i32, [vp, vp, vp, vp, vp]),
         'st_plan_step': (i32, [vp, vp, vp, vp, vp, i64, f64, f64, f64, f64, f64, vp, vp]),
         'st_plan_apply_update': (i32, [vp, vp, vp, vp, vp, vp, i64, f64, f64, f64, f64, f64, vp]),
+        'st_lbfgs_state_bytes': (i64, [i64]),
+        'st_lbfgs_reset': (i32, [vp, i64, vp]),
+        'st_lbfgs_update': (i32, [vp, i64, vp, vp, vp, f64, vp]),
+        'st_plan_lbfgs_step': (i32, [vp, vp, vp, vp, f64, vp, vp]),
+        'st_lbfgs_info': (i32, [vp, i64, ip, ip, ip, ip, ctypes.POINTER(f64), ctypes.POINTER(f64), vp]),
         'st_plan_create_strip': (i32, [pp, vp, i32, i32, i32, i32]),
         'st_plan_closure_begin': (i32, [vp, vp, vp]),
         'st_plan_set_rank': (i32, [vp, i32, i32]),
@@ -355,6 +360,56 @@ class Plan:
         n, ms, fl = ctypes.c_longlong(), ctypes.c_double(), ctypes.c_double()
         _check(self.lib.st_plan_profile_read(self.handle, ctypes.byref(n), ctypes.byref(ms), ctypes.byref(fl)))
         return n.value, ms.value, fl.value
+
+
+class LBFGS:
+    """State of the native ``optimizer='lbfgs'`` step (st_lbfgs_* in include/st_amd.h):
+    ``torch.optim.LBFGS(max_iter=1, history_size=10)`` for ONE parameter tensor, every decision of ``LBFGS.step`` taken on
+    the device.  The state - ring of curvature pairs, Gram matrix, partial sums, counters - is one torch tensor, so
+    ``torch.cuda.max_memory_allocated`` counts it."""
+
+    EXITS = ('moved', 'gradient', 'change')      # exit_code of info(): the step moved / tolerance_grad / tolerance_change
+
+    def __init__(self, like):
+        self.lib = load_library()
+        self.device = like.device
+        self.count = like.numel()
+        nbytes = int(self.lib.st_lbfgs_state_bytes(self.count))
+        self.state = torch.empty((nbytes + 3) // 4, device=self.device, dtype=torch.float32)
+        self.reset()
+
+    def _state(self):
+        return ctypes.c_void_p(self.state.data_ptr())
+
+    def reset(self):
+        """A fresh optimiser (the reference makes a new LBFGS per scale)."""
+        with torch.cuda.device(self.device):
+            _check(self.lib.st_lbfgs_reset(self._state(), self.count, _stream()))
+
+    def step(self, plan, image, ema_value, ema_decay):
+        """closure + LBFGS.step + EMA.update(image) (st_plan_lbfgs_step); returns the plan's 8 losses (device)."""
+        assert image.numel() == self.count
+        with torch.cuda.device(self.device):
+            _check(self.lib.st_plan_lbfgs_step(plan.handle, plan._img(image), self._state(), _ptr(ema_value),
+                                               float(ema_decay), _ptr(plan.losses), _stream()))
+        return plan.losses
+
+    def update(self, image, grad, ema_value=None, ema_decay=0.99):
+        """LBFGS.step on an externally supplied gradient (+ EMA.update when ``ema_value`` is given): st_lbfgs_update."""
+        assert image.numel() == self.count and grad.numel() == self.count
+        with torch.cuda.device(self.device):
+            _check(self.lib.st_lbfgs_update(self._state(), self.count, _ptr(image), _ptr(grad), _ptr(ema_value),
+                                            float(ema_decay), _stream()))
+
+    def info(self):
+        """Counters and the last step's flags (synchronises): dict(n_iter, history, exit, accepted, t, gtd)."""
+        n, h, e, a = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        t, gtd = ctypes.c_double(), ctypes.c_double()
+        with torch.cuda.device(self.device):
+            _check(self.lib.st_lbfgs_info(self._state(), self.count, ctypes.byref(n), ctypes.byref(h), ctypes.byref(e),
+                                          ctypes.byref(a), ctypes.byref(t), ctypes.byref(gtd), _stream()))
+        return {'n_iter': n.value, 'history': h.value, 'exit': self.EXITS[e.value], 'accepted': bool(a.value),
+                't': t.value, 'gtd': gtd.value}
 
 
 def _copy_d2d(dst, src_ptr):

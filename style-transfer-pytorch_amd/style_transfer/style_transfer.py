@@ -872,14 +872,9 @@ class StyleTransfer:
                     sharding.run_phases(plan, fabric)
                     return plan.losses[7].clone()
             elif optimizer != 'adam':
-                self.image.requires_grad_()
-                opt = torch.optim.LBFGS([self.image], max_iter=1, history_size=10)
-
-                def closure(plan=plan):
-                    with torch.no_grad():
-                        losses, grad = plan.loss_and_grad(self.image.detach())
-                    self.image.grad = grad
-                    return losses[7].clone()
+                # torch.optim.LBFGS(max_iter=1, history_size=10), a fresh one per scale (reference :464-465), as the
+                # library's native step: closure, the quasi-Newton update and the EMA in one call, no host decision
+                opt = _hip.LBFGS(self.image)
 
             actual_its = initial_iterations if scale == scales[0] else iterations
             if timing:
@@ -900,9 +895,13 @@ class StyleTransfer:
                                        adam.step, step_size, 0.9, 0.99, 1e-8, avg_decay)
                     self.average.advance_accum()
                     loss = losses[7]
-                else:
+                elif sharded:
                     loss = opt.step(closure)                # no clamp for L-BFGS (reference :482-483)
                     self.average.update(self.image)
+                else:
+                    losses = opt.step(plan, self.image, self.average.value, avg_decay)      # (no clamp either)
+                    self.average.advance_accum()
+                    loss = losses[7]
                 if callback is not None:
                     gpu_ram = torch.cuda.max_memory_allocated(device) + plan.device_bytes()
                     callback(STIterate(w=cw, h=ch, i=i, i_max=actual_its, loss=loss.item(),
