@@ -169,7 +169,8 @@ int st_plan_apply_update(st_plan* plan, float* image, const float* grad, float* 
  * spare slot, and g_prev).  A buffer whose first 4096 bytes are zero is a fresh optimiser (st_lbfgs_reset zeroes them on
  * `stream`); the reference makes a new LBFGS per scale (:464-465).  Between the first and the second launch the three new
  * rows of the Gram matrix and |g|_1 are one contiguous block of 70 doubles at byte 192 of the state, |g|_inf the double
- * behind them: the place of an all-reduce when the parameter is cut into strips.
+ * behind them: when the parameter is cut into strips their place is taken by an all-gather of per-rank records, summed in
+ * rank order (st_qn_strip_* below).
  */
 long long st_lbfgs_state_bytes(long long count);
 int st_lbfgs_reset(void* state, long long count, void* stream);
@@ -207,6 +208,11 @@ int st_lbfgs_info(const void* state, long long count, int* n_iter, int* history,
  *   kind 2 (all-reduce): sum `count` floats at `buffer` over all ranks, in place;
  *   kind 4 (reduce): sum `count` floats at `buffer` over all ranks into rank `root`'s buffer (the others' contents
  *                  are undefined afterwards);   kind 5 (broadcast): rank `root`'s `buffer` to every rank;
+ *   kind 6 (all-gather): every rank contributes `count` opaque 32-bit words at buffer + rank * count and receives all
+ *                  world * count words at `buffer` (in place; the transport copies and does not compute - st_qn_strip_dots
+ *                  issues it, the phase machine does not).  The in-library transport issues it on ONE rank too (kinds 2, 4
+ *                  and 5 return at once there): one RCCL call per iteration that RCCL turns into the identity, so that a
+ *                  one-rank run and st_fabric_selftest execute the call the multi-rank step depends on;
  *   kind 3: nothing to exchange, call again;   kind 0: closure finished.
  * Ordering (ABI version 2): the exchange must be ordered on HIP stream `stream` - behind everything enqueued on it so
  * far, ahead of everything enqueued on it later - or, when `stream` is NULL, on the stream passed to
@@ -259,8 +265,8 @@ int st_fabric_create(st_fabric** out, const unsigned char* id_trunk128, const un
 int st_fabric_destroy(st_fabric* fabric);
 /* The same for a fabric whose operations may never complete (a rank left the run early): ncclCommAbort, no waiting. */
 int st_fabric_abort(st_fabric* fabric);
-/* Pre-flight of a fresh fabric: every operation kind of the phase machine (neighbour send / recv group, all-reduce, reduce,
- * broadcast) once per communicator on 4-float messages with known answers, enqueued on `stream`, awaited on the HOST with a
+/* Pre-flight of a fresh fabric: every operation kind the library issues (neighbour send / recv group, all-reduce, reduce,
+ * broadcast, all-gather) once per communicator on 4-float messages with known answers, enqueued on `stream`, awaited on the HOST with a
  * deadline.  0 = the transport works; otherwise st_last_error() says which operation gave what, or that nothing completed
  * within `timeout_ms` (the fabric is then only good for st_fabric_destroy, which aborts its communicators).  Collective:
  * every rank calls it.  No reference counterpart (the reference's `.to(device)` cannot hang). */
@@ -270,6 +276,37 @@ int st_fabric_selftest(st_fabric* fabric, void* stream, int timeout_ms);
  * communicator must not run concurrently: the call refuses a stream layout in which the heads' exchanges name different
  * streams (ST_STREAMS_COMPACT=0; use the descriptor form there). */
 int st_plan_closure_run(st_plan* plan, st_fabric* fabric, void* stream);
+/*
+ * The optimizer='lbfgs' step (st_lbfgs_* above) on a parameter that is cut into strips, one per rank (st_qn_*: quasi-Newton).
+ * Every rank holds `count` elements of the parameter, of the gradient and of the
+ * curvature pairs; what an iteration needs from the other ranks is their share of the 70 sums and the one maximum above,
+ * and that is ALL that crosses the fabric: each rank writes a RECORD of 72 doubles (the sums, |g|_inf, padding), one
+ * all-gather (exchange kind 6) hands every rank every record, and every rank adds them in rank order in double before
+ * its scalar work.  No sum is formed by the transport, so step length, coefficients and the exit taken are bit-identical on
+ * all ranks whatever algorithm it uses; no decision is taken on the host.  With world == 1 the step is st_lbfgs_update bit
+ * for bit when image, grad and ema_value are 16-byte aligned or count is no multiple of 4: st_qn_strip_dots chooses
+ * between the 16-byte and the scalar kernels from count, state and grad alone (it is not handed the other two), so with
+ * an aligned grad and a misaligned image or ema_value its partial sums are formed in another order than
+ * st_lbfgs_update's scalar pass - equally valid, not bit-identical.
+ * State: st_qn_strip_state_bytes(count, world) bytes, 16-byte aligned: the layout of st_lbfgs_state_bytes(count) with
+ * `world` records behind it, so st_lbfgs_reset and st_lbfgs_info work on it as they are.  0 for count < 1 or world outside
+ * 1 .. 8.
+ * st_qn_strip_dots: the first launch on this rank's elements; fills `gather` with the kind-6 exchange the caller must
+ * perform (ordered on `stream`) before st_qn_strip_apply: the scalar work and the move (+ EMA.update when ema_value is not
+ * NULL) - st_lbfgs_update's second and third launch.  grad must stay untouched until the last launch has run.
+ */
+long long st_qn_strip_state_bytes(long long count, int world);
+int st_qn_strip_dots(void* state, long long count, int rank, int world, const float* grad, st_exchange* gather,
+                     void* stream);
+int st_qn_strip_apply(void* state, long long count, int world, float* image, const float* grad, float* ema_value,
+                      double ema_decay, void* stream);
+/* One full optimizer='lbfgs' iteration on a strip, enqueued in ONE call that does not wait for the device - the strips'
+ * counterpart of st_plan_lbfgs_step: st_plan_closure_begin(image, grad), st_plan_closure_run, st_qn_strip_dots, an
+ * ncclAllGather of the records on the trunk communicator on `stream`, st_qn_strip_apply.  image, grad, ema_value: this
+ * rank's [3][rows][W]; `state` sized by st_qn_strip_state_bytes(3 * rows * W, world) with the plan's and the fabric's
+ * (equal) rank and world.  The losses are the plan's (st_plan_losses), at the iterate BEFORE the move. */
+int st_plan_qn_strip_step(st_plan* plan, st_fabric* fabric, float* image, float* grad, void* state, float* ema_value,
+                          double ema_decay, void* stream);
 /* Device array of 8 floats (7 weighted terms + total) written by the closure of this plan. */
 int st_plan_losses(st_plan* plan, float** losses);
 /* Target construction on strips: forward phases only (halo exchanges), then per-layer raw moment sums. */

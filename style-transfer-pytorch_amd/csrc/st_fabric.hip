@@ -9,7 +9,7 @@
 // next launch, so no exchange overlapped anything (+1.5 ms per iteration on a 2896 x 272 strip); (2) ~100 us of host time per
 // exchange (5 ms of enqueue per iteration against 6.5 ms of GPU work).  Here the library owns two communicators (trunk halos,
 // heads' collectives: operations of one communicator execute in issue order) and issues ncclSend / ncclRecv / ncclAllReduce /
-// ncclReduce / ncclBroadcast itself: the kernels run on the probed communication / head streams, and st_plan_closure_run
+// ncclReduce / ncclBroadcast / ncclAllGather itself: the kernels run on the probed communication / head streams, and st_plan_closure_run
 // walks through the whole phase sequence in one call.
 //
 // RCCL is resolved with dlopen at first use (librccl.so.1, the copy the process has already loaded if there is one):
@@ -20,6 +20,7 @@
 #include <cstring>
 #include <mutex>
 #include <thread>
+#include <vector>
 
 #include "st_common.h"
 #include "../../include/st_amd.h"
@@ -30,7 +31,7 @@ namespace {
 // the slice of rccl.h this file uses (ABI of RCCL 2.x: ncclUniqueId is 128 opaque bytes passed BY VALUE)
 struct NcclId { char internal[128]; };
 typedef void* NcclComm;
-constexpr int kNcclFloat = 7, kNcclSum = 0;
+constexpr int kNcclFloat = 7, kNcclUint32 = 3, kNcclSum = 0;
 
 struct Rccl {
     void* lib = nullptr;
@@ -45,6 +46,7 @@ struct Rccl {
     int (*AllReduce)(const void*, void*, size_t, int, int, NcclComm, hipStream_t) = nullptr;
     int (*Reduce)(const void*, void*, size_t, int, int, int, NcclComm, hipStream_t) = nullptr;
     int (*Broadcast)(const void*, void*, size_t, int, int, NcclComm, hipStream_t) = nullptr;
+    int (*AllGather)(const void*, void*, size_t, int, NcclComm, hipStream_t) = nullptr;
     const char* (*GetErrorString)(int) = nullptr;
 };
 
@@ -70,9 +72,10 @@ Rccl* rccl() {
         r.AllReduce = reinterpret_cast<decltype(r.AllReduce)>(sym("ncclAllReduce"));
         r.Reduce = reinterpret_cast<decltype(r.Reduce)>(sym("ncclReduce"));
         r.Broadcast = reinterpret_cast<decltype(r.Broadcast)>(sym("ncclBroadcast"));
+        r.AllGather = reinterpret_cast<decltype(r.AllGather)>(sym("ncclAllGather"));
         r.GetErrorString = reinterpret_cast<decltype(r.GetErrorString)>(sym("ncclGetErrorString"));
         ok = r.GetUniqueId && r.CommInitRank && r.CommDestroy && r.GroupStart && r.GroupEnd && r.Send && r.Recv &&
-             r.AllReduce && r.Reduce && r.Broadcast;
+             r.AllReduce && r.Reduce && r.Broadcast && r.AllGather;
     });
     return ok ? &r : nullptr;
 }
@@ -142,11 +145,25 @@ int fabric_apply(st_fabric* f, const st_exchange& ex, hipStream_t fallback) {
         ST_NCCL(r->GroupEnd());
         return 0;
     }
-    if (f->world == 1) return 0;                 // a collective over one rank is the identity
+    if (ex.kind == 6) {
+        // all-gather of opaque 32-bit words, in place: rank r's `count` words already lie at buffer + r * count.  Issued on
+        // one rank too (RCCL makes it the identity there): the L-BFGS strip step on a single rank runs the same calls
+        unsigned int* words = reinterpret_cast<unsigned int*>(ex.buffer);
+        ST_NCCL(r->AllGather(words + (size_t)f->rank * n, words, n, kNcclUint32, comm, s));
+        return 0;
+    }
+    if (f->world == 1) return 0;                 // a reduction or broadcast over one rank is the identity
     if (ex.kind == 2) ST_NCCL(r->AllReduce(ex.buffer, ex.buffer, n, kNcclFloat, kNcclSum, comm, s));
     else if (ex.kind == 4) ST_NCCL(r->Reduce(ex.buffer, ex.buffer, n, kNcclFloat, kNcclSum, ex.root, comm, s));
     else if (ex.kind == 5) ST_NCCL(r->Broadcast(ex.buffer, ex.buffer, n, kNcclFloat, ex.root, comm, s));
     else ST_REQUIRE(false, "fabric: unknown exchange kind %d", ex.kind);
+    return 0;
+}
+
+int fabric_position(const st_fabric* f, int* rank, int* world) {
+    ST_REQUIRE(f, "fabric: null fabric");
+    *rank = f->rank;
+    *world = f->world;
     return 0;
 }
 
@@ -193,7 +210,7 @@ int st_fabric_create(st_fabric** out, const unsigned char* id_trunk128, const un
 // HOST-SIDE deadline - a transport that does not work on a system (mismatched ranks, a fabric RCCL cannot route) shows up
 // here as an error the caller can act on (stylize() / bench.py fall back to torch.distributed) instead of as a hang in the
 // first iteration.  Values: rank r sends 10 r + 1 upwards and 10 r + 2 downwards; the sum of (1, r) over the ranks; a
-// reduction to rank 0; a broadcast from the last rank.
+// reduction to rank 0; a broadcast from the last rank; an all-gather of 20 r + 3.
 int st_fabric_selftest(st_fabric* f, void* stream, int timeout_ms) {
     ST_REQUIRE(f, "st_fabric_selftest: null fabric");
     (void)stream;
@@ -220,8 +237,11 @@ int st_fabric_selftest(st_fabric* f, void* stream, int timeout_ms) {
     constexpr int kN = 4;                                    // floats per message
     float*& dev = g.dev;                                     // [send_up | send_down | recv_up | recv_down | sum | red | bc] x 2 channels
     constexpr int kSlots = 7;
-    ST_HIP(hipMalloc(&dev, sizeof(float) * kN * kSlots * 2));
-    float host[kN * kSlots * 2];
+    const int fixed = kN * kSlots * 2;                       // ... then the all-gather areas, w slots of kN per channel
+    const int total = fixed + 2 * w * kN;
+    ST_HIP(hipMalloc(&dev, sizeof(float) * total));
+    std::vector<float> host_v(total, -1.f);
+    float* host = host_v.data();
     for (int c = 0; c < 2; ++c) {
         float* h = host + c * kN * kSlots;
         for (int i = 0; i < kN; ++i) {
@@ -231,9 +251,10 @@ int st_fabric_selftest(st_fabric* f, void* stream, int timeout_ms) {
             h[4 * kN + i] = (i & 1) ? (float)r : 1.f;
             h[5 * kN + i] = (float)(r + 1);
             h[6 * kN + i] = (r == w - 1) ? 7.f + c : -1.f;
+            host[fixed + (c * w + r) * kN + i] = 20.f * r + 3.f + 100.f * c;
         }
     }
-    ST_HIP(hipMemcpyAsync(dev, host, sizeof(host), hipMemcpyHostToDevice, s));
+    ST_HIP(hipMemcpyAsync(dev, host, sizeof(float) * total, hipMemcpyHostToDevice, s));
     const bool up = f->self_halo || r > 0, down = f->self_halo || r < w - 1;
     for (int c = 0; c < 2; ++c) {
         float* d = dev + c * kN * kSlots;
@@ -251,6 +272,8 @@ int st_fabric_selftest(st_fabric* f, void* stream, int timeout_ms) {
         co.kind = 4; co.buffer = d + 5 * kN; co.root = 0;
         if (fabric_apply(f, co, s)) return failed();
         co.kind = 5; co.buffer = d + 6 * kN; co.root = w - 1;
+        if (fabric_apply(f, co, s)) return failed();
+        co.kind = 6; co.buffer = dev + fixed + c * w * kN; co.root = 0;
         if (fabric_apply(f, co, s)) return failed();
     }
     hipEvent_t& done = g.done;
@@ -271,7 +294,7 @@ int st_fabric_selftest(st_fabric* f, void* stream, int timeout_ms) {
         std::this_thread::sleep_for(std::chrono::microseconds(200));
     }
     g.in_flight = false;                         // everything completed: the guard releases buffer, event and stream
-    ST_HIP(hipMemcpy(host, dev, sizeof(host), hipMemcpyDeviceToHost));
+    ST_HIP(hipMemcpy(host, dev, sizeof(float) * total, hipMemcpyDeviceToHost));
     for (int c = 0; c < 2; ++c) {
         const float* h = host + c * kN * kSlots;
         const int upper = f->self_halo ? r : r - 1, lower = f->self_halo ? r : r + 1;
@@ -284,6 +307,10 @@ int st_fabric_selftest(st_fabric* f, void* stream, int timeout_ms) {
             ST_REQUIRE(h[4 * kN + i] == want_sum, "st_fabric_selftest: rank %d channel %d: all-reduce gave %g, expected %g", r, c, h[4 * kN + i], want_sum);
             if (r == 0) ST_REQUIRE(h[5 * kN + i] == 0.5f * w * (w + 1), "st_fabric_selftest: channel %d: reduce gave %g", c, h[5 * kN + i]);
             ST_REQUIRE(h[6 * kN + i] == 7.f + c, "st_fabric_selftest: rank %d channel %d: broadcast gave %g", r, c, h[6 * kN + i]);
+            for (int q = 0; q < w; ++q) {
+                const float got = host[fixed + (c * w + q) * kN + i];
+                ST_REQUIRE(got == 20.f * q + 3.f + 100.f * c, "st_fabric_selftest: rank %d channel %d: all-gather slot %d is %g", r, c, q, got);
+            }
         }
     }
     return 0;

@@ -8,20 +8,30 @@
 //                          (candidate s, candidate y, g against every basis vector) + |g|_1 + |g|_inf.  Per-workgroup
 //                          partial sums; the workgroup that draws the last ticket adds them in index order in double
 //                          (run-to-run bit-identical, no floating-point atomics) into ONE contiguous block
-//                          (LbfgsCtl::rows: where an all-reduce over strips slots in).
-//   2. lbfgs_solve_kernel  one wave, plain C++ in double: the three exits of LBFGS.step as device flags, acceptance of the
+//                          (LbfgsCtl::rows) - or, when the parameter is cut into row strips, into this rank's RECORD of a
+//                          gather area (72 doubles per rank: the same 70 sums, |g|_inf, padding).
+//      [strips only]       one all-gather of the ranks' records: the only thing that crosses the fabric (kind 6 of
+//                          st_exchange: the transport copies, it forms no sum).
+//   2. lbfgs_solve_kernel  one wave, plain C++ in double: [strips: first the `world` records added in rank order, |g|_inf
+//                          their maximum - every rank adds the same numbers in the same order, so delta, t and the exit are
+//                          bit-identical on all of them whatever algorithm the transport uses;] the three exits of LBFGS.step as device flags, acceptance of the
 //                          candidate pair (y.s > 1e-10) and the rotation of the ring, the recursion on delta, t.
 //   3. lbfgs_move_kernel   one pass: d = sum_j delta_j b_j, the next candidate s = t d, g_prev = g, image += s unless a
 //                          flag forbids it, and the EMA update of the same pixels.
 // No decision is taken on the host, so the step never waits for the device.  State is ONE caller-owned device buffer
 // (st_lbfgs_state_bytes): [LbfgsCtl | per-workgroup partials | 11 s slots | 11 y slots | g_prev]; all zero = a fresh state.
-// The candidate pair lives in the ring's spare slot, so a rejected pair overwrites nothing.
+// The candidate pair lives in the ring's spare slot, so a rejected pair overwrites nothing.  A strip's state
+// (st_qn_strip_state_bytes) is that layout for the rank's own elements with the gather area behind it.
 #include <cstddef>
 #include <cstdint>
 
 #include "st_plan.h"
 
 namespace st {
+
+int fabric_apply(st_fabric* f, const st_exchange& ex, hipStream_t fallback);      // st_fabric.hip
+int fabric_position(const st_fabric* f, int* rank, int* world);
+
 namespace {
 
 constexpr int kHist = 10;                    // history_size (style_transfer.py:465)
@@ -47,15 +57,19 @@ struct LbfgsCtl {
     float t;                  // step length as the move applies it
     float coef[2 * kHist + 1];        // delta as fp32: s_0..s_{m-1} at [0, m), y at [kHist, kHist + m), g at [2 kHist]
     double t_d, gtd, h_diag, ys;
-    // the three new rows of B and |g|_1: sums over the elements (an all-reduce over strips adds exactly this block) ...
+    // the three new rows of B and |g|_1: sums over the elements (a strip's record holds exactly this block) ...
     double rows[3 * kRowW + 1];
-    double linf;              // ... and the one maximum
+    double linf;              // ... and the one maximum (on strips: what the solve kernel leaves after adding the records)
     double bss[kHist][kHist], bsy[kHist][kHist], byy[kHist][kHist];      // s_i.s_j, s_i.y_j, y_i.y_j of the history
 };
 constexpr size_t kCtlBytes = 4096;
 static_assert(sizeof(LbfgsCtl) <= kCtlBytes && sizeof(LbfgsCtl) % 4 == 0, "control block");
 static_assert(offsetof(LbfgsCtl, rows) == 192 && offsetof(LbfgsCtl, linf) == 192 + 70 * 8, "include/st_amd.h documents where the new rows lie");
 constexpr size_t kPartialBytes = (size_t)kMaxBlocks * kCols * sizeof(float);
+constexpr int kRecord = 72;                  // doubles per rank in the gather area: rows[70], |g|_inf, one of padding (16-byte multiple)
+constexpr int kRecordSums = 3 * kRowW + 1;
+constexpr int kMaxWorld = 8;
+static_assert(kRecordSums + 1 <= kRecord && (kRecord * sizeof(double)) % 16 == 0, "record layout");
 
 struct LbfgsState {
     LbfgsCtl* ctl;
@@ -177,9 +191,10 @@ __device__ __forceinline__ void dots_body(const float* __restrict__ g, const Lbf
     }
 }
 
+// record: null = the whole parameter is here, the sums go to LbfgsCtl::rows / linf; else this rank's slot of the gather area
 template <int V>
 __global__ __launch_bounds__(256) void lbfgs_dots_kernel(const float* __restrict__ g, LbfgsState st, long long nv,
-                                                         AdamTail tail) {
+                                                         AdamTail tail, double* __restrict__ record) {
     __shared__ float lds[4][kCols];
     __shared__ double part[3][kCols];
     __shared__ bool is_last;
@@ -231,22 +246,42 @@ __global__ __launch_bounds__(256) void lbfgs_dots_kernel(const float* __restrict
         if (r == 0) col = c;                                                                     // candidate s . everything
         else if (r == 1) col = c < 2 * kHist ? cY0 + c : c == 2 * kHist ? cSY : c == 2 * kHist + 1 ? cYY : cYG;
         else col = c < 2 * kHist ? cG0 + c : c == 2 * kHist ? cSG : c == 2 * kHist + 1 ? cYG : cGG;
-        st.ctl->rows[threadIdx.x] = part[0][col];
+        (record ? record : st.ctl->rows)[threadIdx.x] = part[0][col];
     }
     if (threadIdx.x == 0) {
-        st.ctl->rows[3 * kRowW] = part[0][cL1];
-        st.ctl->linf = part[0][cLinf];
+        if (record) {
+            record[kRecordSums - 1] = part[0][cL1];
+            record[kRecordSums] = part[0][cLinf];
+            record[kRecordSums + 1] = 0.0;
+        } else {
+            st.ctl->rows[3 * kRowW] = part[0][cL1];
+            st.ctl->linf = part[0][cLinf];
+        }
     }
 }
 
 // ---- launch 2 -----------------------------------------------------------------------------------------------------
 // LBFGS.step's scalar work (statement for statement as sharding.StripLBFGS.step restates it), every inner product read from B.
-__global__ __launch_bounds__(64) void lbfgs_solve_kernel(LbfgsCtl* ctl) {
+// gather: null, or `world` records (strips): added in rank order into rows / linf before anything reads them.
+__global__ __launch_bounds__(64) void lbfgs_solve_kernel(LbfgsCtl* ctl, const double* __restrict__ gather, int world) {
     __shared__ LbfgsCtl c;
     __shared__ double gs[kHist], gy[kHist], al[kHist], delta[2 * kHist + 1];      // (indexed at run time: not registers)
     constexpr int words = sizeof(LbfgsCtl) / 4;
     for (int i = threadIdx.x; i < words; i += 64) reinterpret_cast<unsigned int*>(&c)[i] = reinterpret_cast<const unsigned int*>(ctl)[i];
     __syncthreads();
+    if (gather) {
+        for (int i = threadIdx.x; i <= kRecordSums; i += 64) {
+            double v = gather[i];
+            if (i < kRecordSums) {
+                for (int r = 1; r < world; ++r) v += gather[r * kRecord + i];
+                c.rows[i] = v;
+            } else {
+                for (int r = 1; r < world; ++r) v = fmax(v, gather[r * kRecord + i]);
+                c.linf = v;
+            }
+        }
+        __syncthreads();
+    }
     if (threadIdx.x == 0) {
         const double* rs = c.rows;                 // candidate s . [s_i | y_i | s, y, g]
         const double* ry = c.rows + kRowW;         // candidate y . ...
@@ -422,25 +457,46 @@ __global__ __launch_bounds__(256) void lbfgs_move_kernel(float* __restrict__ ima
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-int launch_lbfgs_update(void* state, long long count, float* image, const float* grad, float* ema, double ema_decay,
-                        hipStream_t s, AdamTail tail) {
+// 16-byte accesses when the element count and every pointer of the launch allow them, else the scalar kernels
+int launch_dots(void* state, long long count, const float* grad, bool vec, hipStream_t s, AdamTail tail, double* record) {
     const LbfgsState st = carve(state, count);
-    // 16-byte accesses when the element count and every pointer allow them, else the scalar kernels
-    const bool vec = (count & 3) == 0 && aligned16(state) && aligned16(image) && aligned16(grad) && (!ema || aligned16(ema));
+    const long long nv = vec ? count >> 2 : count;
+    const int grid = (int)std::min<long long>((nv + 255) / 256, kMaxBlocks);
+    if (tail.losses_copy == tail.losses8) tail.losses_copy = nullptr;
+    if (vec) hipLaunchKernelGGL(lbfgs_dots_kernel<4>, dim3(grid), dim3(256), 0, s, grad, st, nv, tail, record);
+    else hipLaunchKernelGGL(lbfgs_dots_kernel<1>, dim3(grid), dim3(256), 0, s, grad, st, nv, tail, record);
+    ST_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_solve_move(void* state, long long count, float* image, const float* grad, float* ema, double ema_decay, bool vec,
+                      hipStream_t s, const double* gather, int world) {
+    const LbfgsState st = carve(state, count);
     const long long nv = vec ? count >> 2 : count;
     const int grid = (int)std::min<long long>((nv + 255) / 256, kMaxBlocks);
     const float decay = (float)ema_decay;                 // torch.tensor(decay): fp32 buffer (style_transfer.py:243)
     const float one_m_decay = 1.0f - decay;               // (1 - self.decay) evaluated in fp32 (:253)
-    if (tail.losses_copy == tail.losses8) tail.losses_copy = nullptr;
-    if (vec) hipLaunchKernelGGL(lbfgs_dots_kernel<4>, dim3(grid), dim3(256), 0, s, grad, st, nv, tail);
-    else hipLaunchKernelGGL(lbfgs_dots_kernel<1>, dim3(grid), dim3(256), 0, s, grad, st, nv, tail);
-    ST_LAUNCH_CHECK();
-    hipLaunchKernelGGL(lbfgs_solve_kernel, dim3(1), dim3(64), 0, s, st.ctl);
+    hipLaunchKernelGGL(lbfgs_solve_kernel, dim3(1), dim3(64), 0, s, st.ctl, gather, world);
     ST_LAUNCH_CHECK();
     if (vec) hipLaunchKernelGGL(lbfgs_move_kernel<4>, dim3(grid), dim3(256), 0, s, image, grad, ema, st, nv, decay, one_m_decay);
     else hipLaunchKernelGGL(lbfgs_move_kernel<1>, dim3(grid), dim3(256), 0, s, image, grad, ema, st, nv, decay, one_m_decay);
     ST_LAUNCH_CHECK();
     return 0;
+}
+
+int launch_lbfgs_update(void* state, long long count, float* image, const float* grad, float* ema, double ema_decay,
+                        hipStream_t s, AdamTail tail) {
+    const bool vec = (count & 3) == 0 && aligned16(state) && aligned16(image) && aligned16(grad) && (!ema || aligned16(ema));
+    if (launch_dots(state, count, grad, vec, s, tail, nullptr)) return 1;
+    return launch_solve_move(state, count, image, grad, ema, ema_decay, vec, s, nullptr, 1);
+}
+
+long long base_state_bytes(long long count) {
+    return (long long)(kCtlBytes + kPartialBytes) + (2ll * kSlots + 1) * slot_stride(count) * (long long)sizeof(float);
+}
+// the gather area of a strip's state: `world` records behind the unsharded layout (a 16-byte multiple)
+double* gather_area(void* state, long long count) {
+    return reinterpret_cast<double*>(static_cast<char*>(state) + base_state_bytes(count));
 }
 
 }  // namespace
@@ -452,7 +508,7 @@ extern "C" {
 
 long long st_lbfgs_state_bytes(long long count) {
     if (count < 1) return 0;
-    return (long long)(kCtlBytes + kPartialBytes) + (2ll * kSlots + 1) * slot_stride(count) * (long long)sizeof(float);
+    return base_state_bytes(count);
 }
 
 int st_lbfgs_reset(void* state, long long count, void* stream) {
@@ -506,6 +562,53 @@ int st_plan_lbfgs_step(st_plan* p, float* image, void* state, float* ema_value, 
     const int rc = launch_lbfgs_update(state, 3ll * p->H * p->W, image, p->grad_img, ema_value, ema_decay, s, tail);
     p->amax_clean = rc == 0 && tail.zero != nullptr;
     return rc;
+}
+
+// ---- the same step on a row strip of the parameter (the entry points are named st_qn_*: quasi-Newton) -------------------
+long long st_qn_strip_state_bytes(long long count, int world) {
+    if (count < 1 || world < 1 || world > kMaxWorld) return 0;
+    return base_state_bytes(count) + (long long)world * kRecord * (long long)sizeof(double);
+}
+
+int st_qn_strip_dots(void* state, long long count, int rank, int world, const float* grad, st_exchange* gather, void* stream) {
+    ST_REQUIRE(state && grad && gather && count >= 1, "st_qn_strip_dots: bad argument");
+    ST_REQUIRE(world >= 1 && world <= kMaxWorld && rank >= 0 && rank < world, "st_qn_strip_dots: rank %d of %d", rank, world);
+    ST_REQUIRE((reinterpret_cast<uintptr_t>(state) & 15) == 0, "st_qn_strip_dots: the state buffer must be 16-byte aligned");
+    double* area = gather_area(state, count);
+    const bool vec = (count & 3) == 0 && aligned16(grad);
+    if (launch_dots(state, count, grad, vec, static_cast<hipStream_t>(stream), AdamTail{}, area + (size_t)rank * kRecord)) return 1;
+    *gather = st_exchange{};
+    gather->kind = 6;
+    gather->count = kRecord * (long long)(sizeof(double) / sizeof(float));
+    gather->buffer = reinterpret_cast<float*>(area);
+    gather->stream = stream;
+    return 0;
+}
+
+int st_qn_strip_apply(void* state, long long count, int world, float* image, const float* grad, float* ema_value,
+                      double ema_decay, void* stream) {
+    ST_REQUIRE(state && image && grad && count >= 1, "st_qn_strip_apply: bad argument");
+    ST_REQUIRE(world >= 1 && world <= kMaxWorld, "st_qn_strip_apply: world %d", world);
+    ST_REQUIRE((reinterpret_cast<uintptr_t>(state) & 15) == 0, "st_qn_strip_apply: the state buffer must be 16-byte aligned");
+    const bool vec = (count & 3) == 0 && aligned16(image) && aligned16(grad) && (!ema_value || aligned16(ema_value));
+    return launch_solve_move(state, count, image, grad, ema_value, ema_decay, vec, static_cast<hipStream_t>(stream),
+                             gather_area(state, count), world);
+}
+
+int st_plan_qn_strip_step(st_plan* p, st_fabric* fabric, float* image, float* grad, void* state, float* ema_value,
+                          double ema_decay, void* stream) {
+    ST_REQUIRE(p && fabric && image && grad && state, "st_plan_qn_strip_step: null argument");
+    ST_REQUIRE(p->strip, "st_plan_qn_strip_step: not a strip plan (st_plan_lbfgs_step is the unsharded form)");
+    int rank = 0, world = 1;
+    if (fabric_position(fabric, &rank, &world)) return 1;
+    ST_REQUIRE(rank == p->rank && world == p->world, "st_plan_qn_strip_step: the plan is rank %d of %d, the fabric rank %d of %d",
+               p->rank, p->world, rank, world);
+    const long long count = 3ll * p->H * p->W;
+    if (st_plan_closure_begin(p, image, grad) || st_plan_closure_run(p, fabric, stream)) return 1;
+    st_exchange gather;
+    if (st_qn_strip_dots(state, count, rank, world, grad, &gather, stream)) return 1;
+    if (fabric_apply(fabric, gather, static_cast<hipStream_t>(stream))) return 1;
+    return st_qn_strip_apply(state, count, world, image, grad, ema_value, ema_decay, stream);
 }
 
 }  // extern "C"

@@ -67,6 +67,10 @@ def _declare(lib):
         'st_lbfgs_update': (i32, [vp, i64, vp, vp, vp, f64, vp]),
         'st_plan_lbfgs_step': (i32, [vp, vp, vp, vp, f64, vp, vp]),
         'st_lbfgs_info': (i32, [vp, i64, ip, ip, ip, ip, ctypes.POINTER(f64), ctypes.POINTER(f64), vp]),
+        'st_qn_strip_state_bytes': (i64, [i64, i32]),
+        'st_qn_strip_dots': (i32, [vp, i64, i32, i32, vp, ctypes.POINTER(Exchange), vp]),
+        'st_qn_strip_apply': (i32, [vp, i64, i32, vp, vp, vp, f64, vp]),
+        'st_plan_qn_strip_step': (i32, [vp, vp, vp, vp, vp, vp, f64, vp]),
         'st_plan_create_strip': (i32, [pp, vp, i32, i32, i32, i32]),
         'st_plan_closure_begin': (i32, [vp, vp, vp]),
         'st_plan_set_rank': (i32, [vp, i32, i32]),
@@ -366,15 +370,23 @@ class LBFGS:
     """State of the native ``optimizer='lbfgs'`` step (st_lbfgs_* in include/st_amd.h):
     ``torch.optim.LBFGS(max_iter=1, history_size=10)`` for ONE parameter tensor, every decision of ``LBFGS.step`` taken on
     the device.  The state - ring of curvature pairs, Gram matrix, partial sums, counters - is one torch tensor, so
-    ``torch.cuda.max_memory_allocated`` counts it."""
+    ``torch.cuda.max_memory_allocated`` counts it.
+
+    ``like`` may be ONE RANK'S STRIP of the parameter (``rank`` of ``world``): ``update_strip`` / ``step_strip`` then complete
+    the inner products over the ranks with one all-gather of 72 doubles per rank (st_qn_strip_* in include/st_amd.h).  The
+    state is the unsharded layout with ``world`` such records behind it, so every method works on it."""
 
     EXITS = ('moved', 'gradient', 'change')      # exit_code of info(): the step moved / tolerance_grad / tolerance_change
 
-    def __init__(self, like):
+    def __init__(self, like, rank=0, world=1):
         self.lib = load_library()
         self.device = like.device
         self.count = like.numel()
-        nbytes = int(self.lib.st_lbfgs_state_bytes(self.count))
+        self.rank, self.world = int(rank), int(world)
+        nbytes = int(self.lib.st_qn_strip_state_bytes(self.count, self.world))
+        if nbytes <= 0 or not 0 <= self.rank < self.world:
+            raise ValueError(f'LBFGS: rank {rank} of {world} ranks (1 ... 8) for {self.count} elements')
+        self._exchange = Exchange()
         self.state = torch.empty((nbytes + 3) // 4, device=self.device, dtype=torch.float32)
         self.reset()
 
@@ -400,6 +412,47 @@ class LBFGS:
         with torch.cuda.device(self.device):
             _check(self.lib.st_lbfgs_update(self._state(), self.count, _ptr(image), _ptr(grad), _ptr(ema_value),
                                             float(ema_decay), _stream()))
+
+    def strip_dots(self, grad):
+        """First launch of a strip's step (st_qn_strip_dots): this rank's record lands in its slot of the state's gather
+        area; returns the kind-6 exchange descriptor that must be performed before ``strip_apply``."""
+        assert grad.numel() == self.count
+        with torch.cuda.device(self.device):
+            _check(self.lib.st_qn_strip_dots(self._state(), self.count, self.rank, self.world, _ptr(grad),
+                                             ctypes.byref(self._exchange), _stream()))
+        return self._exchange
+
+    def strip_apply(self, image, grad, ema_value=None, ema_decay=0.99):
+        """Second and third launch (st_qn_strip_apply): the records added in rank order, LBFGS.step's scalar work, the move
+        and EMA.update."""
+        assert image.numel() == self.count and grad.numel() == self.count
+        with torch.cuda.device(self.device):
+            _check(self.lib.st_qn_strip_apply(self._state(), self.count, self.world, _ptr(image), _ptr(grad),
+                                              _ptr(ema_value), float(ema_decay), _stream()))
+
+    def update_strip(self, image, grad, fabric, ema_value=None, ema_decay=0.99):
+        """LBFGS.step on this rank's strip of an externally supplied gradient, the descriptor form: dots, the all-gather
+        through ``fabric.apply`` (a sharding.DistFabric), apply."""
+        ex = self.strip_dots(grad)
+        fabric.apply(ex, self.device)
+        self.strip_apply(image, grad, ema_value, ema_decay)
+
+    def step_strip(self, plan, fabric, image, grad, ema_value, ema_decay):
+        """closure + LBFGS.step + EMA.update on this rank's strip (``plan``: a sharding.StripPlan; ``grad``: the buffer the
+        closure writes).  Over a sharding.NativeFabric ONE call (st_plan_qn_strip_step: the in-library transport issues
+        the all-gather); otherwise closure_begin, run_phases, update_strip.  Returns the plan's 8 losses (device)."""
+        from . import sharding
+        assert image.numel() == self.count
+        if isinstance(fabric, sharding.NativeFabric):
+            plan._inflight = (image, grad)
+            with torch.cuda.device(self.device):
+                _check(self.lib.st_plan_qn_strip_step(plan.handle, fabric.handle, plan._img(image), _ptr(grad), self._state(),
+                                                      _ptr(ema_value), float(ema_decay), _stream()))
+        else:
+            plan.closure_begin(image, grad)
+            sharding.run_phases(plan, fabric)
+            self.update_strip(image, grad, fabric, ema_value, ema_decay)
+        return plan.losses
 
     def info(self):
         """Counters and the last step's flags (synchronises): dict(n_iter, history, exit, accepted, t, gtd)."""

@@ -343,6 +343,19 @@ class DistFabric:
                 else:
                     dist.broadcast(t, src=self._global(ex.root), group=group)
             self._sync(t)
+        elif ex.kind == 6:
+            # all-gather of opaque 32-bit words (the records of _hip.LBFGS.update_strip), in place: rank r's words already
+            # lie in slot r of the buffer.  The transport copies; the sum is formed by the library, in rank order
+            if self.world == 1 and not self.force:
+                return
+            key = (6, ex.buffer, int(ex.count), str(device))
+            parts = self._cache.get(key)
+            if parts is None:
+                parts = self._cache[key] = list(view(ex.buffer, ex.count * self.world, device).chunk(self.world))
+            self._sync(parts[0])
+            with self._on(ex, device):
+                dist.all_gather(parts, parts[self.rank], group=group)
+            self._sync(parts[0])
 
 
 class NativeFabric:
@@ -350,7 +363,7 @@ class NativeFabric:
     ncclSend / ncclRecv / collectives on the streams the descriptors name, two communicators of its own - and
     ``run_phases`` is ONE call per closure.  torch.distributed is only used to hand the two 128-byte communicator ids from
     rank 0 to the others (any backend) and stays the transport of the cold path (targets, scale transitions, L-BFGS
-    scalars: ``cold`` is a DistFabric).  ST_FABRIC_SELF_HALO=1 with one rank: that rank is its own neighbour."""
+    verdicts: ``cold`` is a DistFabric).  ST_FABRIC_SELF_HALO=1 with one rank: that rank is its own neighbour."""
 
     def __init__(self, rank, world, device, group=None, cold=None):
         import torch.distributed as dist
@@ -548,6 +561,22 @@ def run_phases_lockstep(plans, stub=False, wrap=False, owner_chains=None):
             for st in streams:
                 if st is not cur:
                     st.wait_stream(cur)
+
+
+def lbfgs_lockstep(opts, images, grads, emas=None, decay=0.99):
+    """One L-BFGS iteration of len(opts) ranks in one process (``opts[r]`` = ``_hip.LBFGS(strip_r, r, world)``; all strips
+    on one GPU), beside run_phases_lockstep: the dots launch on every rank's state, the all-gather replaced by device
+    copies of each rank's record into every state's gather area, then apply on every rank - the same kernels and the
+    same descriptors as between GPUs, what a one-GPU box can execute of the multi-rank path."""
+    dev = images[0].device
+    exs = [(e.buffer, int(e.count)) for e in (opt.strip_dots(g) for opt, g in zip(opts, grads))]
+    areas = [view(buf, n * len(opts), dev).view(len(opts), n) for buf, n in exs]
+    for r, src in enumerate(areas):
+        for q, dst in enumerate(areas):
+            if q != r:
+                dst[r].copy_(src[r])
+    for r, opt in enumerate(opts):
+        opt.strip_apply(images[r], grads[r], None if emas is None else emas[r], decay)
 
 
 # ---- scale transition on strips (cold path, once per scale; SURVEY.md 8(f) 1) ----------------------

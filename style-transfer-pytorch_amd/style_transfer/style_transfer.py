@@ -744,6 +744,9 @@ class StyleTransfer:
         # scale runs and the gathered full image once the last scale is done.  get_image_tensor() / get_image()
         # gather on demand (a collective: call them on every rank).
         rank, world = _dist_info()
+        if world > 8 and optimizer == 'lbfgs':
+            # (the strip step's gather area holds at most 8 records: st_qn_strip_state_bytes)
+            raise ValueError("optimizer='lbfgs' runs on at most 8 ranks")
         if world > 1:
             from . import sharding
             import torch.distributed as dist
@@ -864,13 +867,9 @@ class StyleTransfer:
             self.model.drop_plans()
 
             if optimizer != 'adam' and sharded:
-                # torch.optim.LBFGS(max_iter=1, history_size=10) with its inner products completed over the ranks
-                opt = sharding.StripLBFGS(self.image, grad, fabric.allreduce, fabric.allmax, history_size=10)
-
-                def closure(plan=plan, grad=grad):
-                    plan.closure_begin(self.image, grad)
-                    sharding.run_phases(plan, fabric)
-                    return plan.losses[7].clone()
+                # ... on this rank's strip: the same native step, its inner products completed over the ranks by one
+                # all-gather of a 72-double record per rank and summed in rank order on the device (no host decision)
+                opt = _hip.LBFGS(self.image, rank, world)
             elif optimizer != 'adam':
                 # torch.optim.LBFGS(max_iter=1, history_size=10), a fresh one per scale (reference :464-465), as the
                 # library's native step: closure, the quasi-Newton update and the EMA in one call, no host decision
@@ -896,8 +895,9 @@ class StyleTransfer:
                     self.average.advance_accum()
                     loss = losses[7]
                 elif sharded:
-                    loss = opt.step(closure)                # no clamp for L-BFGS (reference :482-483)
-                    self.average.update(self.image)
+                    losses = opt.step_strip(plan, fabric, self.image, grad, self.average.value, avg_decay)
+                    self.average.advance_accum()            # no clamp for L-BFGS (reference :482-483)
+                    loss = losses[7]
                 else:
                     losses = opt.step(plan, self.image, self.average.value, avg_decay)      # (no clamp either)
                     self.average.advance_accum()
