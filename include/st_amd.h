@@ -109,6 +109,30 @@ long long st_plan_device_bytes(const st_plan* plan);
 int st_plan_forward(st_plan* plan, const float* image, int last_layer, void* stream);
 /* Borrow a tap (any ReLU/pool index computed by the last forward): dense [C][h][w] device pointer. */
 int st_plan_feature(const st_plan* plan, int layer, const float** data, int* channels, int* height, int* width);
+/*
+ * The backward of VGGFeatures.forward (style_transfer.py:78-90) - what loss.backward() in the closure
+ * (style_transfer.py:472-476: feats = self.model(self.image); loss = crit(feats); loss.backward()) runs through the trunk -
+ * for gradients that arrive at the taps from OUTSIDE: the vector-Jacobian product of the last st_plan_forward on this plan.
+ * A loss of the caller's own (StyleLoss, ContentLoss, a second content layer, feature inversion, ...) is evaluated on the
+ * taps by the caller; this entry carries its gradient to the pixels.
+ *   layers[i], i < count: a features index that st_plan_feature accepts (a ReLU output 1, 3, 6, 8, 11, 13, 15, 17, 20, 22,
+ *       24, 26, 29 or a pool output 4, 9, 18, 27), at most the last forward's last_layer, each named once;
+ *   grads[i]: device pointer, dense [C][h][w] fp32, the gradient with respect to that tap - read only; it must stay
+ *       untouched until the launches have run (the array of pointers itself lives in host memory);
+ *   grad_image [3][H][W]: WRITTEN, not accumulated into; the backward of Normalize (:85) and the fold of conv1_1's
+ *       replicate padding (:39) are included, as in the closure.
+ * The pass starts at the deepest layer named, every gradient is masked by its producer (threshold_backward once, on the
+ * total that has arrived at a ReLU), and a tap's own gradient and the one from the layers above it are added in the tap's
+ * gradient buffer.  Every launch goes on `stream`; the call does not wait for the device.
+ * It fails when no st_plan_forward is current on the plan - none has run, or a closure (st_plan_loss_and_grad,
+ * st_plan_step, st_plan_lbfgs_step, st_plan_range_guard) has run since, whose fused pools leave argmax codes instead of
+ * maps: run st_plan_forward again - when a layer lies beyond that forward's last_layer, is no ReLU or pool output or is
+ * named twice, when count < 1, and on strip plans.  Not to be captured into a hipGraph.
+ * Memory: the gradient buffers (one per activation) are allocated by the first call, as by the first closure: it roughly
+ * doubles the plan's activation memory (st_plan_device_bytes shows it).
+ */
+int st_plan_backward(st_plan* plan, int count, const int* layers, const float* const* grads, float* grad_image,
+                     void* stream);
 
 /*
  * StyleLossW2.get_target (style_transfer.py:162-168) on a tap of the last forward:

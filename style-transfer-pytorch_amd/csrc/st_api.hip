@@ -386,7 +386,33 @@ long long st_plan_device_bytes(const st_plan* p) { return p ? p->bytes : 0; }
 int st_plan_forward(st_plan* p, const float* image, int last_layer, void* stream) {
     ST_REQUIRE(p && image, "st_plan_forward: null argument");
     ST_REQUIRE(last_layer >= 1 && last_layer <= 29, "st_plan_forward: last_layer %d out of range", last_layer);
-    return run_forward(p, image, last_layer, static_cast<hipStream_t>(stream));
+    if (run_forward(p, image, last_layer, static_cast<hipStream_t>(stream))) return 1;
+    p->fwd_last_layer = last_layer;
+    return 0;
+}
+
+int st_plan_backward(st_plan* p, int count, const int* layers, const float* const* grads, float* grad_image, void* stream) {
+    ST_REQUIRE(p, "st_plan_backward: null plan");
+    ST_REQUIRE(!p->strip, "st_plan_backward: strip plans are not supported (a strip's backward needs its neighbours' halo rows)");
+    ST_REQUIRE(count >= 1, "st_plan_backward: count is %d, at least one tap gradient is needed", count);
+    ST_REQUIRE(layers && grads && grad_image, "st_plan_backward: null argument");
+    ST_REQUIRE(p->fwd_last_layer > 0,
+               "st_plan_backward: no st_plan_forward is current on this plan (none has run, or a closure - st_plan_loss_and_grad, "
+               "st_plan_step, ... - has run since and left pooling codes instead of maps): run st_plan_forward first");
+    const float* seed[kNumOps] = {};
+    for (int k = 0; k < count; ++k) {
+        int at = -1;
+        for (int i = 0; i < kNumOps; ++i)
+            if (kProgram[i].feat_index == layers[k]) at = i;
+        ST_REQUIRE(at >= 0, "st_plan_backward: features[%d] is not a ReLU or pooling output", layers[k]);
+        ST_REQUIRE(layers[k] <= p->fwd_last_layer, "st_plan_backward: features[%d] lies beyond the last forward's last_layer %d",
+                   layers[k], p->fwd_last_layer);
+        ST_REQUIRE(seed[at] == nullptr, "st_plan_backward: features[%d] is named twice", layers[k]);
+        ST_REQUIRE(grads[k] != nullptr, "st_plan_backward: null gradient for features[%d]", layers[k]);
+        seed[at] = grads[k];
+    }
+    if (ensure_grad_alloc(p)) return 1;
+    return run_tap_backward(p, seed, grad_image, static_cast<hipStream_t>(stream));
 }
 
 int st_plan_feature(const st_plan* p, int layer, const float** data, int* channels, int* height, int* width) {

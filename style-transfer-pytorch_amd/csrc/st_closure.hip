@@ -300,6 +300,7 @@ int run_forward(st_plan* p, const float* image, int last_layer, hipStream_t s, b
     const Node* prev = nullptr;
     const bool bounds = net->conv_elem == 1;      // fp16x3: producers leave max |y|, max |g| for the consumers
     p->gram1_fused = false;
+    p->fwd_last_layer = 0;                        // the maps change: st_plan_forward marks them current when this returns
     if (bounds && !p->amax_clean) ST_HIP(hipMemsetAsync(p->amax_word, 0, (size_t)64 * kAmaxWordUints * sizeof(float), s));
     p->amax_clean = false;
     bool pooled_by_conv = false;
@@ -701,6 +702,66 @@ int run_backward(st_plan* p, float* grad_image, hipStream_t s) {
     return 0;
 }
 
+// st_plan_backward: run_backward's program for gradients that arrive at the taps from OUTSIDE (seed[i]: the gradient of
+// kProgram[i]'s tap, or null), behind a plain forward - every map is there, no pool left codes, no head runs, one stream.
+// It starts at the deepest seeded op; that node's gradient is final as the seeding kernel leaves it, so that kernel masks it
+// (a ReLU output) and commits its bound, as relu5_1's head does in the closure.  Below it every gradient is masked by its
+// producer, as in run_backward, and a launch that writes a seeded node's gradient adds the two: a data gradient accumulates
+// into the seed copied there just before it (and masks the total); a pooling backward writes, and the seed of the conv that
+// feeds the pool is added behind it.  grad_image is written: there is no TV gradient in it to add to.
+int run_tap_backward(st_plan* p, const float* const* seed, float* grad_image, hipStream_t s) {
+    const st_net* net = p->net;
+    const bool bounds = net->conv_elem == 1;
+    int top = -1;
+    for (int i = 0; i < kNumOps; ++i)
+        if (seed[i]) top = i;
+    ST_REQUIRE(top >= 0, "st_plan_backward: no tap gradient given");
+    auto node = [&](int i) -> Node& { return kProgram[i].kind == 0 ? p->conv[kProgram[i].index] : p->pool[kProgram[i].index]; };
+    // a forward clears the bounds at ITS start only: every max |g| this pass reads is re-established by this pass
+    if (bounds)
+        ST_HIP(hipMemsetAsync(reinterpret_cast<unsigned int*>(p->amax_word) + (size_t)16 * kAmaxWordUints, 0,
+                              (size_t)32 * kAmaxWordUints * sizeof(unsigned int), s));
+    {
+        Node& n = node(top);
+        if (launch_seed_grad(seed[top], kProgram[top].kind == 0 ? n.y : nullptr, n.g, (long long)n.count(), 0,
+                             bounds ? n.g_amax : nullptr, s))
+            return 1;
+    }
+    for (int i = top; i >= 0; --i) {
+        const OpDesc& op = kProgram[i];
+        if (op.kind == 0 && op.index == 0) {
+            // relu1_1's gradient was masked by conv1_2's data-gradient epilogue, or by the seeding kernel above
+            return hbm_profiled(p, HBM_CONV1_DGRAD, (64 + 3) * 4.0 * p->H * p->W, s, [&] {
+                return launch_conv_first_dgrad(p->conv[0].g, nullptr, net->w_first, grad_image, p->dp_scratch, p->H, p->W,
+                                               /*accumulate=*/0, s, nullptr, 0, 0, p->dp_parts, nullptr);
+            });
+        }
+        Node& in = node(i - 1);
+        const float* in_seed = seed[i - 1];
+        if (op.kind == 0) {
+            if (in_seed && launch_seed_grad(in_seed, nullptr, in.g, (long long)in.count(), 0, nullptr, s)) return 1;
+            ConvProblem c{};
+            dgrad_conv(p, i, c);
+            c.mask = nullptr;                      // (the operand was masked by whoever produced it, the top included)
+            c.accumulate = in_seed ? 1 : 0;        // any seeded conv or pool node, not only the closure's six taps
+            if (conv_launch_profiled(p, c, s)) return 1;
+        } else {
+            Node& n = p->pool[op.index];
+            if (hbm_profiled(p, HBM_POOL_BWD, (2.0 * in.count() + n.count()) * 4.0, s, [&] {
+                    return launch_pool_bwd(in.y, n.g, in.g, in.c, in.h, in.w, net->pooling, s);
+                }))
+                return 1;
+            // (the conv shares the pool's bound word.  What the upstream launch left there bounds the conv's share from the pool
+            // only because no pooling backward amplifies - max passes the value on, average halves it, l2 scales by <= 0.78 -
+            // and amax_commit is an atomic max, so the sum committed here can only raise it.  A pooling flavour that amplified
+            // would need a bound of its own.)
+            if (in_seed && launch_seed_grad(in_seed, in.y, in.g, (long long)in.count(), 1, bounds ? in.g_amax : nullptr, s))
+                return 1;
+        }
+    }
+    return 0;
+}
+
 // fp16x3: the three shallow heads share their launches (style_heads_shallow_lockstep); ST_HEAD_LOCKSTEP=0: one stream each
 static bool shallow_heads_lockstep(const st_plan* p) {
     static Option opt("ST_HEAD_LOCKSTEP", 1);
@@ -827,6 +888,7 @@ int loss_and_grad(st_plan* p, const float* image, float* grad_out, float* losses
 // Eager on first sight of a pointer triple (warm-up: allocations, function attributes), captured on
 // the second, replayed afterwards.  Anything that changes baked kernel arguments invalidates the graph.
 int closure_entry(st_plan* p, const float* image, float* grad_out, float* losses_out, hipStream_t s) {
+    p->fwd_last_layer = 0;                        // (a replayed graph does not pass through run_forward)
     if (!p->graph_enabled || p->profiling) return loss_and_grad(p, image, grad_out, losses_out, s);
     const bool same = (p->gk_image == image && p->gk_grad == grad_out && p->gk_losses == losses_out);
     if (!same) {

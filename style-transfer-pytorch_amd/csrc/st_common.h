@@ -598,6 +598,10 @@ int launch_scaled_identity_div(const float* diag_value, const float* scalar, flo
 constexpr int kStreamBlocks = 2048;
 int launch_content_mse(const float* feat, const float* target, long long count, float weight, float* grad,
                        float* partials, float* loss_out, hipStream_t s, unsigned int* ticket = nullptr);
+// st_plan_backward's seeding: g = ext (accumulate == 0) or g += ext over `count` elements; relu_out (optional): the result
+// is masked by (relu_out > 0); bound (optional): max |g| folded into that device bound for an fp16x3 consumer
+int launch_seed_grad(const float* ext, const float* relu_out, float* g, long long count, int accumulate, unsigned int* bound,
+                     hipStream_t s);
 // W2 head scalars after the NS forward.  loss_out[0] = weight * (mean((mu-mu_t)^2) + mean(diag(cov_t + cov - 2 root)))
 // gdiag_out[0] = -2 * (weight / n)   (the diagonal value of dL/d root)
 int launch_style_loss_value(const float* mean, const float* mean_t, const float* cov, const float* cov_t,

@@ -114,6 +114,8 @@ struct st_plan {
     st::Node conv[13];
     st::Node pool[4];
     bool grads_allocated = false;
+    int fwd_last_layer = 0;          // st_plan_forward's last_layer while the maps it wrote are current (st_plan_backward's
+                                     // operands); 0: none has run, or a closure has since (argmax codes instead of maps)
     float* content_target = nullptr;
     bool content_set = false;
     st::StyleHead style[5];
@@ -268,6 +270,8 @@ bool pool_follows(const st_plan* p, int i, int last_layer);
 void forward_conv(const st_plan* p, int i, ConvProblem& c);
 bool fuse_pool(ConvProblem& c, Node& n, bool fork_heads, const PcOverlap* cut);
 void dgrad_conv(const st_plan* p, int i, ConvProblem& c);
+// st_plan_backward: seed[i] = the external gradient of kProgram[i]'s tap, or null
+int run_tap_backward(st_plan* p, const float* const* seed, float* grad_image, hipStream_t s);
 
 // ---- st_strip.hip
 int halo_alloc(st_plan* p, float** out, size_t floats);

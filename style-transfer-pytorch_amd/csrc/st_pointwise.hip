@@ -187,6 +187,56 @@ __global__ __launch_bounds__(64) void content_mse_final_kernel(const float* __re
     if (threadIdx.x == 0) loss_out[0] = (s / count) * weight;
 }
 
+// The seeding of st_plan_backward (the backward of VGGFeatures.forward, style_transfer.py:78-90, for gradients that arrive
+// at the taps from outside): an external tap gradient enters the node's gradient buffer.
+//   ACC == false: g = ext.  Ahead of the data-gradient launch that accumulates into the node - that launch masks the total -
+//                 and at the top of the pass;
+//   ACC == true:  g += ext.  Behind a pooling backward, which WRITES its input node's gradient (masked already).
+//   relu_out != nullptr: the result is masked by (relu_out > 0), the node's own threshold_backward - the top of the pass, where
+//                 nothing accumulates afterwards, and the ACC form (a select on both shares is the select on their sum).
+//   bound != nullptr (fp16x3 networks): max |g| of what this launch leaves goes into the bound the consuming data gradient
+//                 scales its operand by (amax_commit).
+// n4 16-byte groups first, then the count - 4 n4 elements behind them one by one (n4 == 0: a pointer is not 16-byte aligned).
+template <bool ACC>
+__global__ __launch_bounds__(256) void seed_grad_kernel(const float* __restrict__ ext, const float* __restrict__ relu_out,
+                                                        float* __restrict__ g, long long count, long long n4,
+                                                        unsigned int* __restrict__ bound) {
+#pragma clang fp contract(off)
+    unsigned int amax = 0;
+    const long long first = blockIdx.x * 256ll + threadIdx.x, stride = (long long)gridDim.x * 256;
+    const f32x4* ext4 = reinterpret_cast<const f32x4*>(ext);
+    const f32x4* relu4 = reinterpret_cast<const f32x4*>(relu_out);
+    f32x4* g4 = reinterpret_cast<f32x4*>(g);
+    for (long long i = first; i < n4; i += stride) {
+        f32x4 v = ext4[i];
+        if (ACC) {
+            const f32x4 o = g4[i];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) v[k] += o[k];
+        }
+        if (relu_out) {
+            const f32x4 m = relu4[i];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) v[k] = m[k] > 0.f ? v[k] : 0.f;
+        }
+        g4[i] = v;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const unsigned int bits = abs_bits(v[k]);
+            amax = bits > amax ? bits : amax;
+        }
+    }
+    for (long long i = 4 * n4 + first; i < count; i += stride) {
+        float v = ext[i];
+        if (ACC) v += g[i];
+        if (relu_out) v = relu_out[i] > 0.f ? v : 0.f;
+        g[i] = v;
+        const unsigned int bits = abs_bits(v);
+        amax = bits > amax ? bits : amax;
+    }
+    if (bound) amax_commit(amax, bound);       // (every lane arrives here: grid-stride loops, no early return)
+}
+
 // W2 head scalars (StyleLossW2.forward, style_transfer.py:178-181) for one layer; single workgroup.
 __global__ __launch_bounds__(256) void style_loss_value_kernel(W2LossJob job) {
     __shared__ float scratch[4];
@@ -614,6 +664,21 @@ int launch_content_mse(const float* feat, const float* target, long long count, 
     if (ticket) return 0;                 // the last block wrote the loss
     hipLaunchKernelGGL(content_mse_final_kernel, dim3(1), dim3(64), 0, s, partials, blocks, (float)count,
                        weight, loss_out);
+    ST_LAUNCH_CHECK();
+    return 0;
+}
+
+// HBM-bound (reads 4 - 12 bytes and writes 4 per element): the 16-byte groups when every pointer allows them, like the
+// pool kernels' launcher; what is left of `count` behind them, or everything, goes one element at a time
+int launch_seed_grad(const float* ext, const float* relu_out, float* g, long long count, int accumulate, unsigned int* bound,
+                     hipStream_t s) {
+    ST_REQUIRE(ext && g && count > 0, "seed gradient: null argument");
+    const bool aligned = ((reinterpret_cast<uintptr_t>(ext) | reinterpret_cast<uintptr_t>(relu_out) |
+                           reinterpret_cast<uintptr_t>(g)) & 15) == 0;
+    const long long n4 = aligned ? count / 4 : 0;
+    const int blocks = grid_for(std::max(n4, count - 4 * n4));
+    if (accumulate) hipLaunchKernelGGL(seed_grad_kernel<true>, dim3(blocks), dim3(256), 0, s, ext, relu_out, g, count, n4, bound);
+    else hipLaunchKernelGGL(seed_grad_kernel<false>, dim3(blocks), dim3(256), 0, s, ext, relu_out, g, count, n4, bound);
     ST_LAUNCH_CHECK();
     return 0;
 }

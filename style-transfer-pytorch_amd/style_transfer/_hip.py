@@ -55,6 +55,7 @@ def _declare(lib):
         'st_plan_device_bytes': (i64, [vp]),
         'st_plan_forward': (i32, [vp, vp, i32, vp]),
         'st_plan_feature': (i32, [vp, i32, pp, ip, ip, ip]),
+        'st_plan_backward': (i32, [vp, i32, ip, pp, vp, vp]),
         'st_plan_moments': (i32, [vp, i32, vp, vp, vp]),
         'st_plan_set_content_target': (i32, [vp, vp, vp]),
         'st_plan_set_style_target': (i32, [vp, i32, vp, vp, vp]),
@@ -239,6 +240,10 @@ class Net:
 class Plan:
     """All device buffers and kernels for one image size (st_plan)."""
 
+    # bumped by every call that overwrites the activations (forward, loss_and_grad, step, range_guard, LBFGS.step): whoever
+    # keeps a forward's taps for a later backward() compares it to know whether that forward is still the current one
+    forward_count = 0
+
     def __init__(self, net, height, width):
         self.lib = net.lib
         self.net = net
@@ -275,8 +280,33 @@ class Plan:
         return _ptr(image)
 
     def forward(self, image, last_layer=29):
+        self.forward_count += 1
         with torch.cuda.device(self.device):
             _check(self.lib.st_plan_forward(self.handle, self._img(image), int(last_layer), _stream()))
+
+    def backward(self, layers, grads, grad_out=None):
+        """The vector-Jacobian product of the last ``forward`` (st_plan_backward): ``grads[i]`` is the gradient with respect
+        to the tap ``layers[i]`` (any ReLU or pool index up to that forward's ``last_layer``, each once; a contiguous fp32
+        tensor of the tap's shape on this device).  Returns the image gradient [1, 3, H, W] - written into ``grad_out`` when
+        given, not added to it.  Raises HipLibraryError when a closure (loss_and_grad, step, ...) has run on this plan since
+        the forward: run ``forward`` again."""
+        layers, grads = [int(layer) for layer in layers], list(grads)
+        assert len(layers) == len(grads), (len(layers), len(grads))
+        if grad_out is None:
+            grad_out = torch.empty((1, 3, self.height, self.width), device=self.device, dtype=torch.float32)
+        assert grad_out.numel() == 3 * self.height * self.width
+        for layer, g in zip(layers, grads):          # the library reads C * h * w floats behind each pointer
+            data, c, h, w = ctypes.c_void_p(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+            _check(self.lib.st_plan_feature(self.handle, layer, ctypes.byref(data), ctypes.byref(c), ctypes.byref(h),
+                                            ctypes.byref(w)))
+            assert g.numel() == c.value * h.value * w.value, (layer, tuple(g.shape), (c.value, h.value, w.value))
+        for t in (*grads, grad_out):                 # (_ptr checks fp32 and contiguous; the pointers are read on this device)
+            assert t.is_cuda and self.device.index in (None, t.device.index), (t.device, self.device)
+        la = (ctypes.c_int * max(len(layers), 1))(*layers)
+        ga = (ctypes.c_void_p * max(len(grads), 1))(*[_ptr(g).value for g in grads])
+        with torch.cuda.device(self.device):
+            _check(self.lib.st_plan_backward(self.handle, len(layers), la, ga, _ptr(grad_out), _stream()))
+        return grad_out
 
     def feature(self, layer):
         """Copy of a tap as a [1, C, h, w] tensor."""
@@ -319,6 +349,7 @@ class Plan:
         """Returns (losses[8] device tensor: 7 weighted terms + total, grad [like image])."""
         if grad_out is None:
             grad_out = torch.empty_like(image)
+        self.forward_count += 1
         with torch.cuda.device(self.device):
             _check(self.lib.st_plan_loss_and_grad(self.handle, self._img(image), _ptr(grad_out),
                                                   _ptr(self.losses), _stream()))
@@ -326,6 +357,7 @@ class Plan:
 
     def step(self, image, exp_avg, exp_avg_sq, ema_value, step, lr, beta1=0.9, beta2=0.99, eps=1e-8,
              ema_decay=0.99):
+        self.forward_count += 1
         with torch.cuda.device(self.device):
             _check(self.lib.st_plan_step(self.handle, self._img(image), _ptr(exp_avg), _ptr(exp_avg_sq),
                                          _ptr(ema_value), int(step), float(lr), float(beta1), float(beta2),
@@ -336,6 +368,7 @@ class Plan:
         """Activation-aware dynamic-range check of the fp16x3 convolutions on ``image`` (st_plan_range_guard): returns the
         ([13], [13]) forward / data-gradient layers this call moved to bf16x6 (cold path, synchronous)."""
         fwd, bwd = (ctypes.c_int * 13)(), (ctypes.c_int * 13)()
+        self.forward_count += 1
         with torch.cuda.device(self.device):
             _check(self.lib.st_plan_range_guard(self.handle, self._img(image), fwd, bwd, _stream()))
         return list(fwd), list(bwd)
@@ -401,6 +434,7 @@ class LBFGS:
     def step(self, plan, image, ema_value, ema_decay):
         """closure + LBFGS.step + EMA.update(image) (st_plan_lbfgs_step); returns the plan's 8 losses (device)."""
         assert image.numel() == self.count
+        plan.forward_count += 1
         with torch.cuda.device(self.device):
             _check(self.lib.st_plan_lbfgs_step(plan.handle, plan._img(image), self._state(), _ptr(ema_value),
                                                float(ema_decay), _ptr(plan.losses), _stream()))

@@ -216,8 +216,54 @@ def _resolve_weights(weights):
         "STYLE_TRANSFER_VGG19, or use weights='synthetic' (seeded random weights, tests/benchmarks only).")
 
 
+class VGGTrunkFunction(torch.autograd.Function):
+    """The HIP trunk as a node of an autograd graph: ``taps = VGGTrunkFunction.apply(input, plan, layers, device)``.
+
+    What ``loss.backward()`` of the reference's closure (:472-476) runs through ``VGGFeatures.forward`` (:78-90): the forward
+    is ``plan.forward`` and copies of the taps, the backward ``plan.backward`` on the gradients that autograd delivers at the
+    taps (st_plan_backward; Normalize and conv1_1's replicate padding included).  Batch 1, first order only.
+
+    A plan holds ONE forward's activations.  The node records ``plan.forward_count``; when another pass has run on the plan
+    between this forward and its backward (the style image at the same size, a fused closure), the backward first runs the
+    forward again from the saved input - one extra forward pass, same result.  The node keeps the plan alive, so the plan
+    cache of VGGFeatures may evict or drop it meanwhile.
+
+    ``plan`` is duck-typed: ``forward(x, last_layer)``, ``feature(layer)``, ``backward(layers, grads)`` and
+    ``forward_count``."""
+
+    @staticmethod
+    def forward(ctx, input, plan, layers, device):
+        if input.shape[0] != 1:
+            raise ValueError(f'the HIP trunk takes batch 1, got a batch of {input.shape[0]}')
+        layers = tuple(layers)
+        plan.forward(input.detach().to(device, torch.float32).contiguous(), max(layers))
+        ctx.plan, ctx.layers, ctx.device, ctx.count = plan, layers, device, plan.forward_count
+        ctx.save_for_backward(input)
+        ctx.set_materialize_grads(False)         # a tap the loss does not use arrives as None and is not seeded
+        return tuple(plan.feature(layer) for layer in layers)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *grad_taps):
+        (input,) = ctx.saved_tensors
+        plan = ctx.plan
+        seeded = [(layer, g.detach().to(ctx.device, torch.float32).contiguous())
+                  for layer, g in zip(ctx.layers, grad_taps) if g is not None]
+        if not seeded:
+            return None, None, None, None
+        if plan.forward_count != ctx.count:      # the plan's activations are another pass's by now
+            plan.forward(input.detach().to(ctx.device, torch.float32).contiguous(), max(ctx.layers))
+            ctx.count = plan.forward_count
+        grad = plan.backward([layer for layer, _ in seeded], [g for _, g in seeded])
+        return grad.reshape(input.shape).to(input.device, input.dtype), None, None, None
+
+
 class VGGFeatures:
-    """Feature extractor facade (reference :20-90) over the HIP trunk; keeps one plan per input size."""
+    """Feature extractor facade (reference :20-90) over the HIP trunk; keeps one plan per input size.
+
+    Called under ``torch.enable_grad()`` on an input that requires grad, the taps carry a ``grad_fn`` (VGGTrunkFunction) and
+    ``loss.backward()`` reaches the pixels through the HIP trunk, as in the reference's closure; ``feats['input']`` is the
+    caller's tensor itself, so a TV term flows through plain autograd.  Otherwise the taps are plain copies."""
 
     def __init__(self, layers, pooling='max', weights=None, device='cuda:0', precision='fp16x3'):
         if pooling not in vgg.POOLINGS:
@@ -245,10 +291,13 @@ class VGGFeatures:
         min_size = vgg.min_size_for(layers)
         if min(h, w) < min_size:
             raise ValueError(f'Input is {h}x{w} but must be at least {min_size}x{min_size}')
-        x = input.detach().to(self.device, torch.float32).contiguous()
         plan = self.plan_for(h, w)
-        plan.forward(x, max(layers))
         feats = {'input': input}
+        if torch.is_grad_enabled() and input.requires_grad:
+            feats.update(zip(layers, VGGTrunkFunction.apply(input, plan, tuple(layers), self.device)))
+            return feats
+        x = input.detach().to(self.device, torch.float32).contiguous()
+        plan.forward(x, max(layers))
         for layer in layers:
             feats[layer] = plan.feature(layer)
         return feats
