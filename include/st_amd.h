@@ -136,19 +136,44 @@ int st_plan_backward(st_plan* plan, int count, const int* layers, const float* c
 
 /*
  * StyleLossW2.get_target (style_transfer.py:162-168) on a tap of the last forward:
- * mean_out[C] = spatial mean, srm_out[C*C] = F F^T / (h*w).  `layer` in {1,6,11,20,29}.
+ * mean_out[C] = spatial mean, srm_out[C*C] = F F^T / (h*w).  `layer`: any features index that st_plan_feature accepts
+ * (C = 64, 128, 256 or 512); on strip plans one of {1,6,11,20,29}.
  */
 int st_plan_moments(st_plan* plan, int layer, float* mean_out, float* srm_out, void* stream);
 
-/* ContentLossMSE target (style_transfer.py:425-429): copies feat [512][H/8][W/8] into the plan. */
-int st_plan_set_content_target(st_plan* plan, const float* feat, void* stream);
 /*
- * StyleLossW2.__init__ (style_transfer.py:152-160) for style tap `index` (0..4 = relu1_1..relu5_1):
- * cov = srm - mean mean^T + 1e-4 I, cov_sqrt = sqrtm_ns(cov, 12) (sqrtm.py:9-25).
+ * StyleTransfer.content_layers / style_layers (style_transfer.py:315-317, read by every scale at :425-453): the layers the
+ * plan's closure puts its ContentLossMSE and StyleLossW2 terms on.  Each entry is a features index that st_plan_feature
+ * accepts - the 13 ReLU outputs 1 3 6 8 11 13 15 17 20 22 24 26 29 and the 4 pool outputs 4 9 18 27; the reference also
+ * accepts pre-ReLU convolution outputs, which the fused trunk does not keep.  Each list holds 0 to 16 entries (the plan
+ * has 16 bound words for its heads), each named once per list; together they name at least one layer; a layer may be in both.
+ * A plan that was never configured, or is configured with content [22], style [1 6 11 20 29], runs the closure built for
+ * that configuration; every other one runs a general closure (csrc/st_taps.hip: plain forward to the deepest layer named,
+ * one head per layer, st_plan_backward's pass from the heads' gradients onto the TV gradient) through the same entries:
+ * st_plan_loss_and_grad, st_plan_step, st_plan_lbfgs_step, st_plan_range_guard.  Such a plan always launches eagerly
+ * (st_plan_set_graph has no effect on it).  The call drops every target set before, resets the per-layer weights to content
+ * 0.015 / n_content each (:366) and style 1 / n_style each (the default configuration keeps running on the weights of
+ * st_plan_set_loss_weights, which the call leaves alone), invalidates a captured graph and allocates what the
+ * configuration needs.  Fails on strip plans.  Synchronous.
+ */
+int st_plan_set_taps(st_plan* plan, int n_content, const int* content_layers, int n_style, const int* style_layers);
+/* Scale factors of the configured lists (style_transfer.py:320-322,366,376,429,453): content_weights[n_content],
+ * style_weights[n_style], tv.  The general form of st_plan_set_loss_weights, which serves the default configuration only. */
+int st_plan_set_tap_weights(st_plan* plan, const float* content_weights, const float* style_weights, float tv_weight);
+
+/* ContentLossMSE target (style_transfer.py:425-429): copies feat [512][H/8][W/8] into the plan (a configured plan: the
+ * target of content layer 0, shaped like that layer). */
+int st_plan_set_content_target(st_plan* plan, const float* feat, void* stream);
+/* The same for content layer `index` of the configured list (:425-429, one ContentLossMSE per layer): feat is [C][h][w] of that
+ * layer. */
+int st_plan_set_content_target_at(st_plan* plan, int index, const float* feat, void* stream);
+/*
+ * StyleLossW2.__init__ (style_transfer.py:152-160) for style layer `index` of the configured list (default: 0..4 =
+ * relu1_1..relu5_1): cov = srm - mean mean^T + 1e-4 I, cov_sqrt = sqrtm_ns(cov, 12) (sqrtm.py:9-25).
  * mean[C], srm[C*C] are the (already blended, :442-450) targets.
  */
 int st_plan_set_style_target(st_plan* plan, int index, const float* mean, const float* srm, void* stream);
-/* Scale factors (style_transfer.py:320-322,366,376,429,453): content, 5 style layers, tv. */
+/* Scale factors (style_transfer.py:320-322,366,376,429,453): content, 5 style layers, tv.  Default configuration only. */
 int st_plan_set_loss_weights(st_plan* plan, float content_weight, const float* style_layer_weights, float tv_weight);
 
 /*
@@ -331,8 +356,14 @@ int st_qn_strip_apply(void* state, long long count, int world, float* image, con
  * (equal) rank and world.  The losses are the plan's (st_plan_losses), at the iterate BEFORE the move. */
 int st_plan_qn_strip_step(st_plan* plan, st_fabric* fabric, float* image, float* grad, void* state, float* ema_value,
                           double ema_decay, void* stream);
-/* Device array of 8 floats (7 weighted terms + total) written by the closure of this plan. */
+/* Device array of 8 floats (7 weighted terms + total) written by the closure of this plan.  A plan configured with other
+ * layers than the reference's (st_plan_set_taps) has another number of terms; there the array - and losses_out of the
+ * closure entries - holds [0] the sum of the content terms, [1] the sum of the style terms, [2..5] zero, [6] tv, [7] total. */
 int st_plan_losses(st_plan* plan, float** losses);
+/* SumLoss's terms (style_transfer.py:455: content losses in list order, style losses in list order, tv), weighted, as the
+ * plan's last closure left them: *terms = device array of *count = n_content + n_style + 1 floats, owned by the plan (for
+ * the default configuration the first 7 floats of st_plan_losses). */
+int st_plan_term_losses(st_plan* plan, float** terms, int* count);
 /* Target construction on strips: forward phases only (halo exchanges), then per-layer raw moment sums. */
 int st_plan_forward_begin(st_plan* plan, const float* image, int last_layer);
 /* Raw (un-normalised) moments of a style tap of this strip: sums[C*C + C] = [F F^T | F 1] over local pixels.

@@ -431,13 +431,25 @@ int st_plan_moments(st_plan* p, int layer, float* mean_out, float* srm_out, void
     int idx = -1;
     for (int i = 0; i < 5; ++i)
         if (kStyleFeat[i] == layer) idx = i;
-    ST_REQUIRE(idx >= 0, "st_plan_moments: features[%d] is not a style layer", layer);
+    if (idx < 0 || !p->taps_default) {
+        // any other of the 17 taps, and every layer of a configured plan (whose st_plan_set_taps has allocated that head already):
+        // the workspace of that position's own head
+        const int op = tap_position(layer);
+        ST_REQUIRE(op >= 0, "st_plan_moments: features[%d] is not a ReLU or pooling output", layer);
+        ST_REQUIRE(!p->strip, "st_plan_moments: strip plans take the reference's style layers only");
+        HeadSite at;
+        at.h = &tap_head_at(p, op);
+        at.tap = feature_node(p, layer);
+        if (ensure_style_alloc(p, *at.h)) return 1;
+        return moments_of_tap(p, at, mean_out, srm_out, static_cast<hipStream_t>(stream));
+    }
     if (ensure_style_alloc(p, idx)) return 1;
     return moments_of_tap(p, idx, mean_out, srm_out, static_cast<hipStream_t>(stream));
 }
 
 int st_plan_set_content_target(st_plan* p, const float* feat, void* stream) {
     ST_REQUIRE(p && feat, "st_plan_set_content_target: null argument");
+    if (!p->taps_default) return st_plan_set_content_target_at(p, 0, feat, stream);
     ST_HIP(hipMemcpyAsync(p->content_target, feat, p->conv[kContentConv].count() * sizeof(float),
                           hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
     p->content_set = true;     // (buffer contents only: a captured graph stays valid)
@@ -446,10 +458,11 @@ int st_plan_set_content_target(st_plan* p, const float* feat, void* stream) {
 
 int st_plan_set_style_target(st_plan* p, int index, const float* mean, const float* srm, void* stream) {
     ST_REQUIRE(p && mean && srm, "st_plan_set_style_target: null argument");
-    ST_REQUIRE(index >= 0 && index < 5, "st_plan_set_style_target: index %d out of range", index);
+    ST_REQUIRE(index >= 0 && index < p->n_style, "st_plan_set_style_target: index %d out of range (%d style layers)", index,
+               p->n_style);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (ensure_style_alloc(p, index)) return 1;
-    StyleHead& h = p->style[index];
+    StyleHead& h = p->taps_default ? p->style[index] : tap_head_at(p, p->style_op[index]);
+    if (ensure_style_alloc(p, h)) return 1;
     ST_HIP(hipMemcpyAsync(h.mean_t, mean, h.n * sizeof(float), hipMemcpyDeviceToDevice, s));
     if (launch_cov_from_moments(mean, srm, h.cov_t, h.n, kCovEps, s)) return 1;
     if (ns_sqrt_forward(h.cov_t, h.root_t, h.n, h.ns, s)) return 1;
@@ -460,6 +473,7 @@ int st_plan_set_style_target(st_plan* p, int index, const float* mean, const flo
 int st_plan_set_loss_weights(st_plan* p, float content_weight, const float* style_layer_weights,
                              float tv_weight) {
     ST_REQUIRE(p && style_layer_weights, "st_plan_set_loss_weights: null argument");
+    ST_REQUIRE(p->taps_default, "st_plan_set_loss_weights: the plan's layers were configured (st_plan_set_taps): use st_plan_set_tap_weights");
     p->content_weight = content_weight;
     for (int i = 0; i < 5; ++i) p->style_weight[i] = style_layer_weights[i];
     p->tv_weight = tv_weight;

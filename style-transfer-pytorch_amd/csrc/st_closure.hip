@@ -52,7 +52,6 @@ int conv_launch_profiled(st_plan* p, const ConvProblem& prob, hipStream_t s, dou
     return rc;
 }
 
-int style_head(st_plan* p, int idx, hipStream_t s);
 int style_heads_shallow_lockstep(st_plan* p, hipStream_t s, const int* idx, int lanes);
 
 // (compact layout: a head stream that the shipped configuration does not use - ST_HEAD_LOCKSTEP=0, the bf16 / fp32 modes -
@@ -351,8 +350,9 @@ int run_forward(st_plan* p, const float* image, int last_layer, hipStream_t s, b
     return 0;
 }
 
-int ensure_style_alloc(st_plan* p, int idx) {
-    StyleHead& h = p->style[idx];
+int ensure_style_alloc(st_plan* p, int idx) { return ensure_style_alloc(p, p->style[idx]); }
+
+int ensure_style_alloc(st_plan* p, StyleHead& h) {
     if (h.allocated) return 0;
     const size_t nn = (size_t)h.n * h.n;
     float** mats[] = {&h.cov_t, &h.root_t, &h.srm, &h.cov, &h.tmat, &h.mmat, &h.root,
@@ -405,9 +405,28 @@ static int ablate_side() {
     return opt.get();
 }
 
+// the default closure's head `idx`: it writes the tap's own gradient buffer and bound
+HeadSite head_site(st_plan* p, int idx) {
+    HeadSite at;
+    Node& tap = p->conv[kStyleConv[idx]];
+    at.h = &p->style[idx];
+    at.tap = &tap;
+    at.weight = p->style_weight[idx];
+    at.loss = p->losses + 1 + idx;
+    at.grad = tap.g;
+    at.grad_amax = tap.g_amax;
+    at.slot = idx;
+    return at;
+}
+
 int moments_of_tap(st_plan* p, int idx, float* mean_out, float* srm_out, hipStream_t s, float* cov_out) {
-    StyleHead& h = p->style[idx];
-    const Node& tap = p->conv[kStyleConv[idx]];
+    return moments_of_tap(p, head_site(p, idx), mean_out, srm_out, s, cov_out);
+}
+
+int moments_of_tap(st_plan* p, const HeadSite& at, float* mean_out, float* srm_out, hipStream_t s, float* cov_out) {
+    StyleHead& h = *at.h;
+    const Node& tap = *at.tap;
+    const int idx = at.slot;
     // (relu1_1 in the closure: conv1_1's launch has left the partials of its workgroups - run_forward)
     const bool fused = idx == 0 && p->gram1_fused;
     const int splits = fused ? p->gram1_splits : gram_choose_splits(h.n, h.npix_local, h.gram.max_splits);
@@ -462,18 +481,25 @@ static bool ns_chain_delayed() {
 }
 
 // StyleLossW2.forward + its backward down to the tap's feature gradient.
-int style_head(st_plan* p, int idx, hipStream_t s) {
-    StyleHead& h = p->style[idx];
+int style_head(st_plan* p, int idx, hipStream_t s) { return style_head(p, head_site(p, idx), s); }
+
+int style_head(st_plan* p, const HeadSite& at, hipStream_t s) {
+    StyleHead& h = *at.h;
     const bool with_cov = gram_fused_cov();
-    if (moments_of_tap(p, idx, h.mean, h.srm, s, with_cov ? h.cov : nullptr)) return 1;
-    if (style_head_chain(p, idx, s, with_cov)) return 1;
-    return style_head_gradient(p, idx, s);
+    if (moments_of_tap(p, at, h.mean, h.srm, s, with_cov ? h.cov : nullptr)) return 1;
+    if (style_head_chain(p, at, s, with_cov)) return 1;
+    return style_head_gradient(p, at, s);
 }
 
 int style_head_chain(st_plan* p, int idx, hipStream_t s, bool cov_ready) {
-    StyleHead& h = p->style[idx];
+    return style_head_chain(p, head_site(p, idx), s, cov_ready);
+}
+
+int style_head_chain(st_plan* p, const HeadSite& at, hipStream_t s, bool cov_ready) {
+    StyleHead& h = *at.h;
+    const int idx = at.slot;
     const int n = h.n;
-    const float w = p->style_weight[idx];
+    const float w = at.weight;
     const bool tl = p->timeline && (idx == 4 || idx == 3);
     hipEvent_t* tlh = idx == 4 ? p->tl_h4 : p->tl_h3;
     if (tl) ST_HIP(hipEventRecord(tlh[0], s));
@@ -489,8 +515,8 @@ int style_head_chain(st_plan* p, int idx, hipStream_t s, bool cov_ready) {
     if (launch_gemm_batch(mm, s)) return 1;
     // the loss term (style_transfer.py:178-181) and the seed dL/d root = gdiag * I ride in the backward chain's opening
     // kernel (one launch less on the iteration's critical path); then the Lyapunov recurrence -> dL/dM
-    const W2LossJob job{h.mean, h.mean_t, h.cov, h.cov_t, h.root, n, w, p->losses + 1 + idx, h.gdiag};
-    if (ns_chain_combined() && (ns_chain_mask() & (idx == 4 ? 4 : idx == 3 ? 2 : 1))) {
+    const W2LossJob job{h.mean, h.mean_t, h.cov, h.cov_t, h.root, n, w, at.loss, h.gdiag};
+    if (idx >= 0 && ns_chain_combined() && (ns_chain_mask() & (idx == 4 ? 4 : idx == 3 ? 2 : 1))) {
         // round 5: both recurrences and the loss scalars in ONE persistent launch (st_nschain.hip)
         const float* mm1[1] = {h.mmat};
         float* r1[1] = {h.root};
@@ -591,16 +617,19 @@ static bool head5_masks_its_gradient() {
     return opt.get() != 0;
 }
 
-int style_head_gradient(st_plan* p, int idx, hipStream_t s) {
-    StyleHead& h = p->style[idx];
+int style_head_gradient(st_plan* p, int idx, hipStream_t s) { return style_head_gradient(p, head_site(p, idx), s); }
+
+int style_head_gradient(st_plan* p, const HeadSite& at, hipStream_t s) {
+    StyleHead& h = *at.h;
+    const int idx = at.slot;
     const int n = h.n;
-    Node& tap = p->conv[kStyleConv[idx]];
+    const Node& tap = *at.tap;
     const bool f16 = p->net->conv_elem == 1;
-    // dF = Ssym F + b 1^T : a 1x1 convolution over the tap; WRITES the tap's gradient buffer
+    // dF = Ssym F + b 1^T : a 1x1 convolution over the tap; WRITES the tap's gradient buffer (general closure: its seed buffer)
     ConvProblem c{};
-    c.in = tap.y; c.mask = nullptr; c.wgt = h.ssym; c.bias = h.bvec; c.out = tap.g;
+    c.in = tap.y; c.mask = nullptr; c.wgt = h.ssym; c.bias = h.bvec; c.out = at.grad;
     c.cin = n; c.cout = n; c.height = tap.h; c.width = tap.w; c.taps = 1; c.relu = 0; c.accumulate = 0;
-    c.out_amax = f16 ? tap.g_amax : nullptr;
+    c.out_amax = f16 ? at.grad_amax : nullptr;
     static Option head_f32("ST_HEAD_1X1_F32", 0);          // attribution runs: the heads' 1x1 gradient step in exact fp32
     if (f16 && !head_f32.get()) {       // large taps: fp16x3 1x1 kernel (st_conv1x1.hip); launch_conv keeps split-K problems on fp32
         c.planes = 2; c.elem = 1; c.amax_word = tap.y_amax; c.wgt_amax = h.s_amax;
@@ -614,7 +643,7 @@ int style_head_gradient(st_plan* p, int idx, hipStream_t s) {
     const long long npix = (long long)tap.h * tap.w;
     if (head_dgrad_small_applies(n, npix))       // a tap of <= 1024 pixels: one small-GEMM launch instead of split-K + reduce
         return hbm_profiled(p, HBM_HEAD_1X1, 2.0 * n * (double)npix * sizeof(float), s, [&] {
-            return launch_head_dgrad_small(h.ssym, tap.y, h.bvec, c.out_mask, tap.g, n, npix, c.out_amax, s);
+            return launch_head_dgrad_small(h.ssym, tap.y, h.bvec, c.out_mask, at.grad, n, npix, c.out_amax, s);
         });
     // (not part of the `roofline` bracket, which is the 3x3 trunk kernel's: on the large taps this step is HBM-bound -
     // read F, write dF - and reported under roofline_hbm)
@@ -708,8 +737,9 @@ int run_backward(st_plan* p, float* grad_image, hipStream_t s) {
 // (a ReLU output) and commits its bound, as relu5_1's head does in the closure.  Below it every gradient is masked by its
 // producer, as in run_backward, and a launch that writes a seeded node's gradient adds the two: a data gradient accumulates
 // into the seed copied there just before it (and masks the total); a pooling backward writes, and the seed of the conv that
-// feeds the pool is added behind it.  grad_image is written: there is no TV gradient in it to add to.
-int run_tap_backward(st_plan* p, const float* const* seed, float* grad_image, hipStream_t s) {
+// feeds the pool is added behind it.  grad_image is written: there is no TV gradient in it to add to - except for the general
+// closure (onto_image), whose heads' gradients are the seeds and whose TV kernel has written grad_image before.
+int run_tap_backward(st_plan* p, const float* const* seed, float* grad_image, hipStream_t s, bool onto_image) {
     const st_net* net = p->net;
     const bool bounds = net->conv_elem == 1;
     int top = -1;
@@ -731,10 +761,14 @@ int run_tap_backward(st_plan* p, const float* const* seed, float* grad_image, hi
         const OpDesc& op = kProgram[i];
         if (op.kind == 0 && op.index == 0) {
             // relu1_1's gradient was masked by conv1_2's data-gradient epilogue, or by the seeding kernel above
-            return hbm_profiled(p, HBM_CONV1_DGRAD, (64 + 3) * 4.0 * p->H * p->W, s, [&] {
-                return launch_conv_first_dgrad(p->conv[0].g, nullptr, net->w_first, grad_image, p->dp_scratch, p->H, p->W,
-                                               /*accumulate=*/0, s, nullptr, 0, 0, p->dp_parts, nullptr);
-            });
+            if (hbm_profiled(p, HBM_CONV1_DGRAD, (64 + 3 + (onto_image ? 3 : 0)) * 4.0 * p->H * p->W, s, [&] {
+                    return launch_conv_first_dgrad(p->conv[0].g, nullptr, net->w_first, grad_image, p->dp_scratch, p->H, p->W,
+                                                   onto_image ? 1 : 0, s, nullptr, 0, 0, p->dp_parts,
+                                                   onto_image ? p->fold_update : nullptr);
+                }))
+                return 1;
+            if (onto_image) p->fold_updated = p->fold_update != nullptr;
+            return 0;
         }
         Node& in = node(i - 1);
         const float* in_seed = seed[i - 1];
@@ -769,6 +803,15 @@ static bool shallow_heads_lockstep(const st_plan* p) {
 }
 
 int require_targets(const st_plan* p) {
+    if (!p->taps_default) {
+        for (int i = 0; i < p->n_content; ++i)
+            ST_REQUIRE(p->tap_content_set[p->content_op[i]], "content target %d (features[%d]) not set (st_plan_set_content_target_at)", i,
+                       kProgram[p->content_op[i]].feat_index);
+        for (int i = 0; i < p->n_style; ++i)
+            ST_REQUIRE(p->tap_head[p->style_op[i]].target_set, "style target %d (features[%d]) not set (st_plan_set_style_target)", i,
+                       kProgram[p->style_op[i]].feat_index);
+        return 0;
+    }
     ST_REQUIRE(p->content_set, "content target not set (st_plan_set_content_target)");
     for (int i = 0; i < 5; ++i)
         ST_REQUIRE(p->style[i].target_set, "style target %d not set (st_plan_set_style_target)", i);
@@ -885,10 +928,19 @@ int loss_and_grad(st_plan* p, const float* image, float* grad_out, float* losses
     return 0;                                  // (losses_out was written by the sum kernel)
 }
 
+// the closure of the plan's configuration, launched eagerly: any configuration but the reference's own (st_plan_set_taps), or
+// that one under ST_GENERAL_TAPS, runs the general closure (st_taps.hip)
+int closure_eager(st_plan* p, const float* image, float* grad_out, float* losses_out, hipStream_t s) {
+    p->fwd_last_layer = 0;
+    if (general_taps(p)) return general_loss_and_grad(p, image, grad_out, losses_out, s);
+    return loss_and_grad(p, image, grad_out, losses_out, s);
+}
+
 // Eager on first sight of a pointer triple (warm-up: allocations, function attributes), captured on
 // the second, replayed afterwards.  Anything that changes baked kernel arguments invalidates the graph.
 int closure_entry(st_plan* p, const float* image, float* grad_out, float* losses_out, hipStream_t s) {
     p->fwd_last_layer = 0;                        // (a replayed graph does not pass through run_forward)
+    if (general_taps(p)) return closure_eager(p, image, grad_out, losses_out, s);      // (never captured)
     if (!p->graph_enabled || p->profiling) return loss_and_grad(p, image, grad_out, losses_out, s);
     const bool same = (p->gk_image == image && p->gk_grad == grad_out && p->gk_losses == losses_out);
     if (!same) {

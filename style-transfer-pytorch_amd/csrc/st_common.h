@@ -592,12 +592,13 @@ int launch_div_by_dev_scalar(const float* a, const float* scalar, float* y, long
 // q = (diag_value[0] / *scalar) * I
 int launch_scaled_identity_div(const float* diag_value, const float* scalar, float* q, int n, hipStream_t s);
 
-// ContentLossMSE value + gradient: loss_out[0] = weight * mean((f-t)^2); grad = weight * 2 (f-t) / count
+// ContentLossMSE value + gradient: loss_out[0] = weight * mean((f-t)^2); grad = weight * 2 (f-t) / count (accumulate != 0:
+// added to what grad holds)
 // partials: kStreamBlocks floats (content) / 4 * kStreamBlocks floats (TV).  ticket != nullptr: a zeroed device word;
 // the value is then finished by the kernel's last block (one launch instead of two)
 constexpr int kStreamBlocks = 2048;
 int launch_content_mse(const float* feat, const float* target, long long count, float weight, float* grad,
-                       float* partials, float* loss_out, hipStream_t s, unsigned int* ticket = nullptr);
+                       float* partials, float* loss_out, hipStream_t s, unsigned int* ticket = nullptr, int accumulate = 0);
 // st_plan_backward's seeding: g = ext (accumulate == 0) or g += ext over `count` elements; relu_out (optional): the result
 // is masked by (relu_out > 0); bound (optional): max |g| folded into that device bound for an fp16x3 consumer
 int launch_seed_grad(const float* ext, const float* relu_out, float* g, long long count, int accumulate, unsigned int* bound,
@@ -635,6 +636,8 @@ int launch_content_mse_final(const float* sum, long long global_count, float wei
 int launch_div_by_scalar(const float* a, float d, float* y, long long count, hipStream_t s);
 // total = ((((((l0 + l1) + l2) + l3) + l4) + l5) + l6)   (SumLoss order)
 int launch_sum_losses(float* losses8, hipStream_t s, float* copy = nullptr);
+// a configured plan's terms (n_content + n_style + 1 floats, SumLoss order) folded into the 8-float array (and its copy)
+int launch_sum_terms(const float* terms, int n_content, int n_style, float* losses8, hipStream_t s, float* copy = nullptr);
 struct AdamScalars {
     float lerp_w;        // (float)(1 - beta1)
     float beta2;         // (float)beta2

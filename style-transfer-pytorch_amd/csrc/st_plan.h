@@ -1,5 +1,5 @@
 // Internal to libst_amd.so: the VGG-19 program, the plan's nodes and style heads, st_net / st_plan, and the plan helpers
-// that more than one of st_api.hip, st_closure.hip, st_strip.hip and st_range_guard.hip call.
+// that more than one of st_api.hip, st_closure.hip, st_taps.hip, st_strip.hip and st_range_guard.hip call.
 #pragma once
 
 #include <functional>
@@ -65,6 +65,19 @@ struct StyleHead {
     NSWorkspace ns{};
     GramWorkspace gram{};
     bool allocated = false;
+};
+
+// Where a W2 style head sits.  The default closure's five heads are head_site(p, idx); the general closure (st_taps.hip) puts
+// one on any of the 17 taps.
+struct HeadSite {
+    StyleHead* h = nullptr;
+    const Node* tap = nullptr;       // the tap's node (a conv's ReLU output or a pooled map)
+    float weight = 0.f;
+    float* loss = nullptr;           // device word of the weighted loss term
+    float* grad = nullptr;           // dF is WRITTEN here: the tap's gradient buffer, or its seed buffer (general closure)
+    unsigned int* grad_amax = nullptr;   // fp16x3: bound of what is written (null: whoever consumes it next commits one)
+    int slot = -1;                   // 0 .. 4: the default closure's head of that index (relu1_1's fused Gram, relu5_1's mask,
+                                     // the timeline events, the persistent chain's mask); -1: none of these
 };
 
 struct ProfileEvent {
@@ -225,6 +238,20 @@ struct st_plan {
     bool amax_clean = false;         // the update kernel has cleared amax_word: the next run_forward skips its memset
     const st::FoldUpdate* fold_update = nullptr;     // st_plan_step: conv1_1's fold kernel applies the update (and the tail)
     bool fold_updated = false;       // ... and has done so in this closure
+    // st_plan_set_taps: the configured content / style lists as kProgram positions.  taps_default: they are the reference's
+    // own ([22], [1, 6, 11, 20, 29]) - the plan runs loss_and_grad on style[] / content_target above; every other
+    // configuration runs general_loss_and_grad (st_taps.hip) on the per-position heads and targets below.
+    bool taps_default = true;
+    int n_content = 1, n_style = 5;
+    int content_op[16] = {12};
+    int style_op[16] = {0, 3, 6, 11, 16};
+    float tap_content_weight[16] = {};
+    float tap_style_weight[16] = {};
+    st::StyleHead tap_head[st::kNumOps];             // the W2 head of a position (allocated when a list first names it)
+    float* tap_content_target[st::kNumOps] = {};
+    bool tap_content_set[st::kNumOps] = {};
+    float* tap_seed[st::kNumOps] = {};               // the heads' gradient of a tapped position: run_tap_backward's seed
+    float* terms = nullptr;                          // [64], at most 16 + 16 + 1 used: the weighted terms in SumLoss order (st_plan_term_losses)
 };
 
 namespace st {
@@ -255,23 +282,40 @@ int hbm_profiled(st_plan* p, int cat, double bytes, hipStream_t s, F&& launch) {
 void invalidate_graph(st_plan* p);
 int ensure_streams(st_plan* p, hipStream_t caller = nullptr);
 int ensure_style_alloc(st_plan* p, int idx);
+int ensure_style_alloc(st_plan* p, StyleHead& h);
 int ensure_grad_alloc(st_plan* p);
+HeadSite head_site(st_plan* p, int idx);
 int moments_of_tap(st_plan* p, int idx, float* mean_out, float* srm_out, hipStream_t s, float* cov_out = nullptr);
+int moments_of_tap(st_plan* p, const HeadSite& at, float* mean_out, float* srm_out, hipStream_t s, float* cov_out = nullptr);
 int moment_sums_of_tap(st_plan* p, int idx, float* sums, hipStream_t s);
+int style_head(st_plan* p, int idx, hipStream_t s);
+int style_head(st_plan* p, const HeadSite& at, hipStream_t s);
 int style_head_chain(st_plan* p, int idx, hipStream_t s, bool cov_ready = false);
+int style_head_chain(st_plan* p, const HeadSite& at, hipStream_t s, bool cov_ready = false);
 int style_head_gradient(st_plan* p, int idx, hipStream_t s);
+int style_head_gradient(st_plan* p, const HeadSite& at, hipStream_t s);
 int join_head_for_conv(st_plan* p, int conv_index, hipStream_t s);
 int require_targets(const st_plan* p);
 int run_forward(st_plan* p, const float* image, int last_layer, hipStream_t s, bool fork_heads = false);
 int loss_and_grad(st_plan* p, const float* image, float* grad_out, float* losses_out, hipStream_t s);
 int closure_entry(st_plan* p, const float* image, float* grad_out, float* losses_out, hipStream_t s);
+int closure_eager(st_plan* p, const float* image, float* grad_out, float* losses_out, hipStream_t s);
 // the trunk's 3x3 launches, described once for both closures and the range guard (kProgram[i] is a conv, i > 0)
 bool pool_follows(const st_plan* p, int i, int last_layer);
 void forward_conv(const st_plan* p, int i, ConvProblem& c);
 bool fuse_pool(ConvProblem& c, Node& n, bool fork_heads, const PcOverlap* cut);
 void dgrad_conv(const st_plan* p, int i, ConvProblem& c);
-// st_plan_backward: seed[i] = the external gradient of kProgram[i]'s tap, or null
-int run_tap_backward(st_plan* p, const float* const* seed, float* grad_image, hipStream_t s);
+// st_plan_backward: seed[i] = the external gradient of kProgram[i]'s tap, or null.  onto_image (general closure): grad_image
+// holds the TV gradient and is added to, with the step's update folded in where the plan asks for it (st_plan::fold_update).
+int run_tap_backward(st_plan* p, const float* const* seed, float* grad_image, hipStream_t s, bool onto_image = false);
+
+// ---- st_taps.hip
+bool general_taps(const st_plan* p);
+int general_loss_and_grad(st_plan* p, const float* image, float* grad_out, float* losses_out, hipStream_t s);
+int tap_position(int layer);          // kProgram position of features[layer], -1: not one of the 17 taps
+int closure_top_op(const st_plan* p); // the deepest kProgram position the plan's closure runs
+bool targets_ready(const st_plan* p);
+StyleHead& tap_head_at(st_plan* p, int op);
 
 // ---- st_strip.hip
 int halo_alloc(st_plan* p, float** out, size_t floats);

@@ -138,6 +138,8 @@ __device__ __forceinline__ bool last_block_arrives(const LastBlock& lb, bool* sh
     return last;
 }
 
+// ACC (general closure, st_taps.hip): the layer is a style layer as well, whose head has WRITTEN grad - this term's is added.
+template <bool ACC>
 __global__ __launch_bounds__(256) void content_mse_kernel(const float* __restrict__ feat,
                                                           const float* __restrict__ target, long long count,
                                                           float weight, float norm, float* __restrict__ grad,
@@ -155,11 +157,13 @@ __global__ __launch_bounds__(256) void content_mse_kernel(const float* __restric
         for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
             const f32x4 f = f4[i], t = t4[i];
             f32x4 g;
+            if (ACC) g = g4[i];
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const float d = f[k] - t[k];
                 s += d * d;
-                g[k] = (norm * d) * weight;      // mse_loss_backward: (2/numel) * (x - t) * grad_out
+                const float v = (norm * d) * weight;      // mse_loss_backward: (2/numel) * (x - t) * grad_out
+                g[k] = ACC ? g[k] + v : v;
             }
             g4[i] = g;
         }
@@ -167,7 +171,8 @@ __global__ __launch_bounds__(256) void content_mse_kernel(const float* __restric
         for (long long i = blockIdx.x * 256ll + threadIdx.x; i < count; i += (long long)gridDim.x * 256) {
             const float d = feat[i] - target[i];
             s += d * d;
-            grad[i] = (norm * d) * weight;
+            const float v = (norm * d) * weight;
+            grad[i] = ACC ? grad[i] + v : v;
         }
     }
     s = block_sum_256(s, scratch);
@@ -563,6 +568,30 @@ __global__ void sum_losses_kernel(float* l, float* copy) {
     }
 }
 
+// General closure (st_taps.hip): the weighted terms of a configured plan in SumLoss order (style_transfer.py:455) - n_content
+// content terms, n_style style terms, tv - folded into the 8-float loss array: [0] the content terms' sum, [1] the style
+// terms', [2..5] zero, [6] tv, [7] total.  The total is formed as sum_losses_kernel and AdamTail form it, 0 + l[0] + ... +
+// l[6], so that a step whose tail sums the array again leaves the same bits.
+__global__ void sum_terms_kernel(const float* __restrict__ terms, int n_content, int n_style, float* __restrict__ l,
+                                 float* __restrict__ copy) {
+#pragma clang fp contract(off)
+    if (threadIdx.x == 0 && blockIdx.x == 0) {
+        float c = 0.f, st = 0.f;
+        for (int i = 0; i < n_content; ++i) c = c + terms[i];
+        for (int i = 0; i < n_style; ++i) st = st + terms[n_content + i];
+        const float tv = terms[n_content + n_style];
+        float t = 0.f;
+        t = t + c;
+        t = t + st;
+        for (int i = 2; i < 6; ++i) t = t + 0.f;
+        t = t + tv;
+        for (int k = 0; k < (copy ? 2 : 1); ++k) {
+            float* o = k ? copy : l;
+            o[0] = c; o[1] = st; o[2] = 0.f; o[3] = 0.f; o[4] = 0.f; o[5] = 0.f; o[6] = tv; o[7] = t;
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // torch.optim.Adam single-tensor step (torch/optim/adam.py:414-547, as configured at
 // style_transfer.py:458) + image.clamp_(0, 1) (:485) + EMA.update (:250-253), one pass over 3HW.
@@ -655,11 +684,15 @@ int launch_scaled_identity_div(const float* diag_value, const float* scalar, flo
 static int stream_blocks(long long work_items) { return grid_for(work_items, kStreamBlocks); }
 
 int launch_content_mse(const float* feat, const float* target, long long count, float weight, float* grad,
-                       float* partials, float* loss_out, hipStream_t s, unsigned int* ticket) {
+                       float* partials, float* loss_out, hipStream_t s, unsigned int* ticket, int accumulate) {
     const int blocks = stream_blocks((count & 3) == 0 ? count / 4 : count);
     const float norm = (float)(2.0 / (double)count);
-    hipLaunchKernelGGL(content_mse_kernel, dim3(blocks), dim3(256), 0, s, feat, target, count, weight, norm,
-                       grad, partials, LastBlock{ticket}, (float)count, loss_out);
+    if (accumulate)
+        hipLaunchKernelGGL(content_mse_kernel<true>, dim3(blocks), dim3(256), 0, s, feat, target, count, weight, norm,
+                           grad, partials, LastBlock{ticket}, (float)count, loss_out);
+    else
+        hipLaunchKernelGGL(content_mse_kernel<false>, dim3(blocks), dim3(256), 0, s, feat, target, count, weight, norm,
+                           grad, partials, LastBlock{ticket}, (float)count, loss_out);
     ST_LAUNCH_CHECK();
     if (ticket) return 0;                 // the last block wrote the loss
     hipLaunchKernelGGL(content_mse_final_kernel, dim3(1), dim3(64), 0, s, partials, blocks, (float)count,
@@ -790,7 +823,7 @@ int launch_content_mse_strip(const float* feat, const float* target, long long l
                              float* sum_out, hipStream_t s) {
     const int blocks = stream_blocks((local_count & 3) == 0 ? local_count / 4 : local_count);
     const float norm = (float)(2.0 / (double)global_count);
-    hipLaunchKernelGGL(content_mse_kernel, dim3(blocks), dim3(256), 0, s, feat, target, local_count, weight, norm,
+    hipLaunchKernelGGL(content_mse_kernel<false>, dim3(blocks), dim3(256), 0, s, feat, target, local_count, weight, norm,
                        grad, partials, LastBlock{nullptr}, 0.f, static_cast<float*>(nullptr));
     ST_LAUNCH_CHECK();
     hipLaunchKernelGGL(reduce_partials_kernel, dim3(1), dim3(64), 0, s, partials, blocks, 1, sum_out);
@@ -813,6 +846,12 @@ int launch_div_by_scalar(const float* a, float d, float* y, long long count, hip
 
 int launch_sum_losses(float* losses8, hipStream_t s, float* copy) {
     hipLaunchKernelGGL(sum_losses_kernel, dim3(1), dim3(64), 0, s, losses8, copy == losses8 ? nullptr : copy);
+    ST_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_sum_terms(const float* terms, int n_content, int n_style, float* losses8, hipStream_t s, float* copy) {
+    hipLaunchKernelGGL(sum_terms_kernel, dim3(1), dim3(64), 0, s, terms, n_content, n_style, losses8, copy == losses8 ? nullptr : copy);
     ST_LAUNCH_CHECK();
     return 0;
 }

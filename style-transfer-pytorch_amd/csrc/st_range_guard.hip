@@ -165,17 +165,16 @@ int plan_range_guard(st_plan* p, const float* image, hipStream_t s, int* new_fwd
         }
         if (!flagged) break;
     }
-    if (!p->content_set) return finish(0);
-    for (int i = 0; i < 5; ++i)
-        if (!p->style[i].target_set) return finish(0);
+    if (!targets_ready(p)) return finish(0);
 
     // ---- data gradients: the gradients of one closure; both arithmetics on the same operand ----
     int lowest_checked = 13;                                       // layers >= this index are settled
     for (int pass = 0; pass < 13; ++pass) {
-        if (loss_and_grad(p, image, p->grad_img, nullptr, s)) return finish(1);
+        if (closure_eager(p, image, p->grad_img, nullptr, s)) return finish(1);
         ST_HIP(hipStreamSynchronize(s));
         bool flagged = false;
-        for (int i = kNumOps - 1; i >= 0 && !flagged; --i) {
+        // (a configured plan's closure stops at its deepest layer: no gradient exists above it)
+        for (int i = closure_top_op(p); i >= 0 && !flagged; --i) {
             const OpDesc& op = kProgram[i];
             if (op.kind != 0 || op.index == 0 || op.index >= lowest_checked) continue;
             const OpDesc& pop = kProgram[i - 1];

@@ -18,6 +18,9 @@ _LIB_CANDIDATES = (os.path.join(_PKG_ROOT, 'lib', 'libst_amd.so'),
 LIB_PATH = next((c for c in _LIB_CANDIDATES if os.path.exists(c)), _LIB_CANDIDATES[0])
 
 _c_float_p = ctypes.c_void_p      # device pointers travel as integers
+# features indices the trunk keeps: the 13 ReLU outputs and the 4 pool outputs (st_plan_feature)
+TAPS = (1, 3, 4, 6, 8, 9, 11, 13, 15, 17, 18, 20, 22, 24, 26, 27, 29)
+DEFAULT_CONTENT_LAYERS, DEFAULT_STYLE_LAYERS = (22,), (1, 6, 11, 20, 29)
 _lib = None
 
 
@@ -60,6 +63,10 @@ def _declare(lib):
         'st_plan_set_content_target': (i32, [vp, vp, vp]),
         'st_plan_set_style_target': (i32, [vp, i32, vp, vp, vp]),
         'st_plan_set_loss_weights': (i32, [vp, f32, ctypes.POINTER(f32), f32]),
+        'st_plan_set_taps': (i32, [vp, i32, ip, i32, ip]),
+        'st_plan_set_tap_weights': (i32, [vp, ctypes.POINTER(f32), ctypes.POINTER(f32), f32]),
+        'st_plan_set_content_target_at': (i32, [vp, i32, vp, vp]),
+        'st_plan_term_losses': (i32, [vp, pp, ip]),
         'st_plan_loss_and_grad': (i32, [vp, vp, vp, vp, vp]),
         'st_plan_step': (i32, [vp, vp, vp, vp, vp, i64, f64, f64, f64, f64, f64, vp, vp]),
         'st_plan_apply_update': (i32, [vp, vp, vp, vp, vp, vp, i64, f64, f64, f64, f64, f64, vp]),
@@ -243,6 +250,8 @@ class Plan:
     # bumped by every call that overwrites the activations (forward, loss_and_grad, step, range_guard, LBFGS.step): whoever
     # keeps a forward's taps for a later backward() compares it to know whether that forward is still the current one
     forward_count = 0
+    # the configured layers (set_taps); strip plans keep the default
+    content_layers, style_layers = DEFAULT_CONTENT_LAYERS, DEFAULT_STYLE_LAYERS
 
     def __init__(self, net, height, width):
         self.lib = net.lib
@@ -264,6 +273,27 @@ class Plan:
         h, self.handle = getattr(self, 'handle', None), None
         if h and self.lib is not None:
             self.lib.st_plan_destroy(h)
+
+    def set_taps(self, content_layers, style_layers):
+        """The layers of the closure's content / style terms (st_plan_set_taps): any of ``TAPS``, 0 to 16 per list, each once
+        per list, at least one in all.  Drops every target set before and resets a non-default configuration's weights
+        (``set_loss_weights`` afterwards).  Anything but the default lists runs the general closure."""
+        content_layers, style_layers = [int(v) for v in content_layers], [int(v) for v in style_layers]
+        ca = (ctypes.c_int * max(len(content_layers), 1))(*content_layers)
+        sa = (ctypes.c_int * max(len(style_layers), 1))(*style_layers)
+        with torch.cuda.device(self.device):
+            _check(self.lib.st_plan_set_taps(self.handle, len(content_layers), ca, len(style_layers), sa))
+        self.content_layers, self.style_layers = content_layers, style_layers
+
+    def term_losses(self):
+        """The weighted terms of the last closure in SumLoss order - content layers, style layers, tv - as a device tensor
+        (st_plan_term_losses; a copy)."""
+        data, n = ctypes.c_void_p(), ctypes.c_int()
+        with torch.cuda.device(self.device):
+            _check(self.lib.st_plan_term_losses(self.handle, ctypes.byref(data), ctypes.byref(n)))
+            out = torch.empty(n.value, device=self.device, dtype=torch.float32)
+            _copy_d2d(out, data.value)
+        return out
 
     def device_bytes(self):
         return int(self.lib.st_plan_device_bytes(self.handle))
@@ -319,22 +349,32 @@ class Plan:
         return out
 
     def moments(self, layer):
-        c = {1: 64, 6: 128, 11: 256, 20: 512, 29: 512}[int(layer)]
+        """(mean [C], srm [C, C]) of a tap of the last forward (st_plan_moments): any of ``TAPS``."""
+        if int(layer) not in TAPS:
+            raise ValueError(f'features[{int(layer)}] is not one of the taps {TAPS}')
+        c = 64 if layer < 5 else 128 if layer < 10 else 256 if layer < 19 else 512
         mean = torch.empty(c, device=self.device, dtype=torch.float32)
         srm = torch.empty((c, c), device=self.device, dtype=torch.float32)
         with torch.cuda.device(self.device):
             _check(self.lib.st_plan_moments(self.handle, int(layer), _ptr(mean), _ptr(srm), _stream()))
         return mean, srm
 
-    def set_content_target(self, feat):
+    def set_content_target(self, feat, index=0):
+        """The target of content layer ``index`` of the configured list (st_plan_set_content_target_at)."""
+        data, c, h, w = ctypes.c_void_p(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        _check(self.lib.st_plan_feature(self.handle, self.content_layers[int(index)], ctypes.byref(data), ctypes.byref(c),
+                                        ctypes.byref(h), ctypes.byref(w)))
+        assert feat.numel() == c.value * h.value * w.value, (tuple(feat.shape), (c.value, h.value, w.value))
         with torch.cuda.device(self.device):
-            _check(self.lib.st_plan_set_content_target(self.handle, _ptr(feat.contiguous()), _stream()))
+            _check(self.lib.st_plan_set_content_target_at(self.handle, int(index), _ptr(feat.contiguous()), _stream()))
 
     def set_content_target_from_forward(self):
-        data = ctypes.c_void_p()
-        _check(self.lib.st_plan_feature(self.handle, 22, ctypes.byref(data), None, None, None))
-        with torch.cuda.device(self.device):
-            _check(self.lib.st_plan_set_content_target(self.handle, data, _stream()))
+        """Every configured content layer's target from the maps of the current forward."""
+        for index, layer in enumerate(self.content_layers):
+            data = ctypes.c_void_p()
+            _check(self.lib.st_plan_feature(self.handle, layer, ctypes.byref(data), None, None, None))
+            with torch.cuda.device(self.device):
+                _check(self.lib.st_plan_set_content_target_at(self.handle, index, data, _stream()))
 
     def set_style_target(self, index, mean, srm):
         with torch.cuda.device(self.device):
@@ -342,8 +382,23 @@ class Plan:
                                                      _ptr(srm.contiguous()), _stream()))
 
     def set_loss_weights(self, content_weight, style_layer_weights, tv_weight):
-        arr = (ctypes.c_float * 5)(*[float(w) for w in style_layer_weights])
-        _check(self.lib.st_plan_set_loss_weights(self.handle, float(content_weight), arr, float(tv_weight)))
+        """``content_weight``: one float for every content layer, or one per layer; ``style_layer_weights``: one per style
+        layer (st_plan_set_tap_weights; a plan with the default layers: st_plan_set_loss_weights)."""
+        nc, ns = len(self.content_layers), len(self.style_layers)
+        try:                                        # any sequence (list, tuple, numpy array, tensor), or one number
+            cws = [float(w) for w in content_weight]
+        except TypeError:
+            cws = [float(content_weight)] * nc
+        sws = [float(w) for w in style_layer_weights]
+        if (tuple(self.content_layers), tuple(self.style_layers)) == (DEFAULT_CONTENT_LAYERS, DEFAULT_STYLE_LAYERS):
+            # (as before this entry took lists: fewer than 5 style weights leave the rest at zero)
+            sa = (ctypes.c_float * 5)(*sws)
+            _check(self.lib.st_plan_set_loss_weights(self.handle, cws[0], sa, float(tv_weight)))
+            return
+        if len(cws) != nc or len(sws) != ns:
+            raise ValueError(f'{len(cws)} content and {len(sws)} style weights for {nc} content and {ns} style layers')
+        ca, sa = (ctypes.c_float * max(nc, 1))(*cws), (ctypes.c_float * max(ns, 1))(*sws)
+        _check(self.lib.st_plan_set_tap_weights(self.handle, ca, sa, float(tv_weight)))
 
     def loss_and_grad(self, image, grad_out=None):
         """Returns (losses[8] device tensor: 7 weighted terms + total, grad [like image])."""
@@ -363,6 +418,14 @@ class Plan:
                                          _ptr(ema_value), int(step), float(lr), float(beta1), float(beta2),
                                          float(eps), float(ema_decay), _ptr(self.losses), _stream()))
         return self.losses
+
+    def apply_update(self, image, grad, exp_avg, exp_avg_sq, ema_value, step, lr, beta1=0.9, beta2=0.99, eps=1e-8,
+                     ema_decay=0.99):
+        """Only the update of ``step`` - Adam + clamp + EMA - on an externally supplied gradient (st_plan_apply_update)."""
+        with torch.cuda.device(self.device):
+            _check(self.lib.st_plan_apply_update(self.handle, self._img(image), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq),
+                                                 _ptr(ema_value), int(step), float(lr), float(beta1), float(beta2),
+                                                 float(eps), float(ema_decay), _stream()))
 
     def range_guard(self, image):
         """Activation-aware dynamic-range check of the fp16x3 convolutions on ``image`` (st_plan_range_guard): returns the

@@ -196,6 +196,34 @@ def _starting_image(init, content_image, style_images, style_weights, height, wi
     raise ValueError("init must be one of 'content', 'gray', 'uniform', 'style_mean'")
 
 
+def _resolve_taps(content_layers, style_layers, style_weights, world=1):
+    """``StyleTransfer.content_layers`` / ``style_layers`` / ``style_weights`` as the fused closure takes them: returns
+    (content layers, style layers, their weights).  The style pairs are ``zip(style_layers, style_weights)`` as the reference
+    forms them (:451).  Raises ``ValueError`` for what the closure cannot serve, before any device work."""
+    content = [int(layer) for layer in content_layers]
+    pairs = [(int(layer), float(weight)) for layer, weight in zip(style_layers, style_weights)]
+    style = [layer for layer, _ in pairs]
+    for name, layers in (('content_layers', content), ('style_layers', style)):
+        for layer in layers:
+            if layer not in _hip.TAPS:
+                raise ValueError(
+                    f'{name}: features[{layer}] is not one of the 17 taps of the fused trunk - the ReLU outputs 1, 3, 6, 8, 11, '
+                    '13, 15, 17, 20, 22, 24, 26, 29 and the pool outputs 4, 9, 18, 27.  The pre-ReLU convolution outputs, which '
+                    'the reference accepts, are not kept by the fused trunk.')
+        if len(set(layers)) != len(layers):
+            raise ValueError(f'{name}: a layer is named twice in {layers}')
+        if len(layers) > 16:
+            raise ValueError(f'{name}: {len(layers)} layers; the fused closure takes at most 16 per list')
+    if not content and not style:
+        raise ValueError('content_layers and style_layers are both empty')
+    default = (tuple(content), tuple(style)) == (_hip.DEFAULT_CONTENT_LAYERS, _hip.DEFAULT_STYLE_LAYERS)
+    if world > 1 and not default:
+        raise ValueError(f'content_layers {content} / style_layers {style} on {world} ranks: row strips run the default layers '
+                         '(content [22], style [1, 6, 11, 20, 29]) only; other layer sets are out of scope for strips - run '
+                         'them on one device')
+    return content, style, [weight for _, weight in pairs]
+
+
 def _resolve_weights(weights):
     if isinstance(weights, (list, tuple)):
         return list(weights)
@@ -608,13 +636,15 @@ class StyleTransfer:
     # ---- per-scale targets (reference :425-453) ----
     def _build_targets(self, plan, content, style_images, style_weights, scale, style_scale_fac, style_size):
         device = self.devices[0]
+        content_layers, style_layers = list(plan.content_layers), list(plan.style_layers)
         # fp16x3's activation-aware range guard (cold path, st_plan_range_guard): the forward arithmetic is checked on every
         # image BEFORE its features become targets; the closure's gradients are checked in stylize() once the targets exist
         guarded = self.model.net.precision == 'fp16x3'
         if guarded:
             plan.range_guard(content)
-        plan.forward(content, 22)
-        plan.set_content_target_from_forward()
+        if content_layers:
+            plan.forward(content, max(content_layers))
+            plan.set_content_target_from_forward()
         blended = {}
         for i, image in enumerate(style_images):
             if style_size is None:
@@ -628,8 +658,10 @@ class StyleTransfer:
             splan = plan if (sh, sw) == (plan.height, plan.width) else self.model.plan_for(sh, sw)
             if guarded:
                 splan.range_guard(style)
-            splan.forward(style, 29)
-            for layer in self.style_layers:
+            if not style_layers:
+                continue
+            splan.forward(style, max(style_layers))
+            for layer in style_layers:
                 mean, srm = splan.moments(layer)
                 mean *= style_weights[i]
                 srm *= style_weights[i]
@@ -638,7 +670,7 @@ class StyleTransfer:
                 else:
                     blended[layer][0].add_(mean)
                     blended[layer][1].add_(srm)
-        for idx, layer in enumerate(self.style_layers):
+        for idx, layer in enumerate(style_layers):
             plan.set_style_target(idx, *blended[layer])
 
     def _guard_rows(self, rows_image, blended=None, content_weight=None, tv_weight=None):
@@ -766,6 +798,10 @@ class StyleTransfer:
                 style_size: int = None,
                 callback=None):
 
+        # the loss's layers are read NOW, as the reference reads them at every scale (:425-453)
+        content_layers, style_layers, layer_weights = _resolve_taps(
+            self.content_layers, self.style_layers, self.style_weights,
+            world=max(len(self.devices), _dist_info()[1]))
         if len(self.devices) > 1 and self._job is None:
             return _device_list_stylize(self, content_image, style_images, dict(
                 style_weights=style_weights, content_weight=content_weight, tv_weight=tv_weight, optimizer=optimizer,
@@ -773,7 +809,7 @@ class StyleTransfer:
                 step_size=step_size, avg_decay=avg_decay, init=init, style_scale_fac=style_scale_fac, style_size=style_size),
                 callback)
         min_scale = min(min_scale, end_scale)
-        content_weights = [content_weight / len(self.content_layers)] * len(self.content_layers)
+        content_weights = [content_weight / len(content_layers)] * len(content_layers) if content_layers else []
 
         if style_weights is None:
             style_weights = [1 / len(style_images)] * len(style_images)
@@ -886,10 +922,15 @@ class StyleTransfer:
                                                       style_scale_fac, style_size)
                 grad = torch.empty_like(self.image)
             else:
+                min_size = vgg.min_size_for(content_layers + style_layers)
+                if min(ch, cw) < min_size:
+                    raise ValueError(f'Input is {ch}x{cw} but must be at least {min_size}x{min_size}')
                 plan = self._plan = _hip.Plan(self.model.net, ch, cw)
+                if (content_layers, style_layers) != (list(plan.content_layers), list(plan.style_layers)):
+                    plan.set_taps(content_layers, style_layers)
                 self._build_targets(plan, content.to(device), style_images, style_weights, scale, style_scale_fac,
                                     style_size)
-            plan.set_loss_weights(content_weights[0], self.style_weights, tv_weight)
+            plan.set_loss_weights(content_weights, layer_weights, tv_weight)
             if sharded and self.model.net.precision == 'fp16x3':
                 # ... sharded: on this rank's rows of the iterate, against the scale's style targets; the union of the ranks'
                 # verdicts; forward layers flagged only now have shaped the targets: build them again
