@@ -155,6 +155,29 @@ def _sharded_case(h, w, world, precision, overlap, owner, vgg_weights, rows=None
     frac = float((diff > 1e-4).float().mean())
     print(f'[shard] post-update image: mean_abs {float(diff.mean()):.2e}, {100 * frac:.3f}% pixels off > 1e-4')
     assert float(diff.mean()) < 1e-5 and frac < 5e-3
+
+    # ... and a second one that is more than lr * sign(g): step 7 from a seeded non-zero state, and BOTH sides on the strips'
+    # concatenated gradient, which takes the gradient's strip-vs-whole difference out of the comparison.  The update is
+    # element-wise: image, both moments and the EMA must agree bit for bit, any difference is an indexing error.
+    gen = torch.Generator().manual_seed(7)
+    g_cpu = grad_s.cpu()
+    m0 = (g_cpu * (3 * torch.rand(g_cpu.shape, generator=gen) - 1.5)).contiguous()
+    v0 = (g_cpu * g_cpu * (0.05 + torch.rand(g_cpu.shape, generator=gen))).contiguous()
+    e0 = (0.3 * torch.rand(g_cpu.shape, generator=gen)).contiguous()
+    state_w = [t.to(DEV).clone() for t in (image, m0, v0, e0)]
+    whole.apply_update(state_w[0], grad_s.contiguous(), state_w[1], state_w[2], state_w[3], 7, 0.02)
+    state_s = []
+    for p, g, (b, e) in zip(plans, grads, rows):
+        strip = [t[:, :, b:e].contiguous().to(DEV) for t in (image, m0, v0, e0)]
+        p.apply_update(strip[0], g, strip[1], strip[2], strip[3], 7, 0.02)
+        state_s.append(strip)
+    torch.cuda.synchronize()
+    for k, name in enumerate(('image', 'exp_avg', 'exp_avg_sq', 'ema')):
+        got = torch.cat([strip[k] for strip in state_s], dim=2)
+        assert torch.equal(got, state_w[k]), (name, float((got - state_w[k]).abs().max()))
+    assert not torch.equal(state_w[0], image.to(DEV)) and bool(state_w[1].any()) and bool(state_w[2].any())
+    print(f'[shard] {h}x{w} R={world}: step-7 update per strip == on the whole image, bit for bit '
+          f'(strips of {[e - b for b, e in rows]} rows)')
     return grad_s.cpu(), plans[0].losses.cpu().clone()
 
 
