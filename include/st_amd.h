@@ -151,10 +151,12 @@ int st_plan_moments(st_plan* plan, int layer, float* mean_out, float* srm_out, v
  * that configuration; every other one runs a general closure (csrc/st_taps.hip: plain forward to the deepest layer named,
  * one head per layer, st_plan_backward's pass from the heads' gradients onto the TV gradient) through the same entries:
  * st_plan_loss_and_grad, st_plan_step, st_plan_lbfgs_step, st_plan_range_guard.  Such a plan always launches eagerly
- * (st_plan_set_graph has no effect on it).  The call drops every target set before, resets the per-layer weights to content
- * 0.015 / n_content each (:366) and style 1 / n_style each (the default configuration keeps running on the weights of
- * st_plan_set_loss_weights, which the call leaves alone), invalidates a captured graph and allocates what the
- * configuration needs.  Fails on strip plans.  Synchronous.
+ * (st_plan_set_graph has no effect on it).  The call drops every target set before, invalidates a captured graph and
+ * allocates what the configuration needs (the five heads of the default lists too, which a plan that was never configured
+ * allocates when their targets are set).  Weights: a plan on the default lists that is given the default lists again keeps
+ * its weights; every other call resets them to the new lists' defaults - content 0.015 / n_content each (:366) and style
+ * 1 / n_style each, or, for the default lists, the weights of a fresh plan (0.015; 256/341 ... 1/341) - so set the weights
+ * after the layers.  Fails on strip plans.  Synchronous.
  */
 int st_plan_set_taps(st_plan* plan, int n_content, const int* content_layers, int n_style, const int* style_layers);
 /* Scale factors of the configured lists (style_transfer.py:320-322,366,376,429,453): content_weights[n_content],

@@ -91,13 +91,6 @@ AdamScalars adam_scalars(long long step, double lr, double beta1, double beta2, 
     sc.one_m_decay = 1.0f - sc.decay;        // (1 - self.decay) evaluated in fp32 (:253)
     return sc;
 }
-
-const Node* feature_node(const st_plan* p, int layer) {
-    for (int i = 0; i < kNumOps; ++i)
-        if (kProgram[i].feat_index == layer)
-            return kProgram[i].kind == 0 ? &p->conv[kProgram[i].index] : &p->pool[kProgram[i].index];
-    return nullptr;
-}
 }  // namespace
 }  // namespace st
 
@@ -209,6 +202,8 @@ int st_net_destroy(st_net* net) {
     return 0;
 }
 
+static size_t moment_floats(const StyleHead& h) { return (size_t)h.n * h.n + h.n; }      // [F F^T | F 1]
+
 static int plan_create_common(st_plan** out, const st_net* net, int local_height, int width, int global_height,
                               int row0, bool strip_mode) {
     st_plan* p = new st_plan();
@@ -224,7 +219,7 @@ static int plan_create_common(st_plan** out, const st_net* net, int local_height
     int h = local_height, w = width, hg = global_height;
     for (int i = 0; i < kNumOps; ++i) {
         const OpDesc& op = kProgram[i];
-        Node& n = (op.kind == 0) ? p->conv[op.index] : p->pool[op.index];
+        Node& n = node_at(p, i);
         if (op.kind == 1) { h /= 2; w /= 2; hg /= 2; }
         n.c = op.cout; n.h = h; n.w = w; n.hg = hg;
         if (plan_alloc(p, &n.y, n.count())) { st_plan_destroy(p); return 1; }
@@ -244,11 +239,11 @@ static int plan_create_common(st_plan** out, const st_net* net, int local_height
         if (plan_alloc(p, &mem, ((size_t)n.c * (n.h / 2) * (n.w / 2) + 3) / 4)) { st_plan_destroy(p); return 1; }
         n.pool_code = reinterpret_cast<unsigned char*>(mem);
     }
-    for (int i = 0; i < 5; ++i) {
-        const Node& tap = p->conv[kStyleConv[i]];
-        p->style[i].n = tap.c;
-        p->style[i].npix = (long long)tap.hg * tap.w;
-        p->style[i].npix_local = (long long)tap.h * tap.w;
+    for (int op = 0; op < kNumOps; ++op) {
+        const Node& tap = node_at(p, op);
+        p->head[op].n = tap.c;
+        p->head[op].npix = (long long)tap.hg * tap.w;
+        p->head[op].npix_local = (long long)tap.h * tap.w;
     }
     float* ticket_mem = nullptr;
     if (plan_alloc(p, &ticket_mem, 256) || hipMemset(ticket_mem, 0, 256 * sizeof(float)) != hipSuccess) {
@@ -259,7 +254,7 @@ static int plan_create_common(st_plan** out, const st_net* net, int local_height
     if (plan_alloc(p, &p->losses, 64) || plan_alloc(p, &p->red_partials, 5 * kStreamBlocks) ||
         plan_alloc(p, &p->conv_scratch, kConvScratchFloats) ||
         plan_alloc(p, &p->dp_scratch, (size_t)3 * (local_height + 2) * (width + 2) * p->dp_parts) || plan_alloc(p, &p->amax_word, (size_t)64 * kAmaxWordUints) ||
-        plan_alloc(p, &p->content_target, p->conv[kContentConv].count())) {
+        plan_alloc(p, &p->content_target[p->content_op[0]], node_at(p, p->content_op[0]).count())) {
         st_plan_destroy(p);
         return 1;
     }
@@ -278,8 +273,7 @@ static int plan_create_common(st_plan** out, const st_net* net, int local_height
             }
         }
     }
-    for (int i = 0; i < 5; ++i)
-        p->style[i].s_amax = reinterpret_cast<unsigned int*>(p->amax_word) + (size_t)(48 + i) * kAmaxWordUints;
+    assign_head_bounds(p);
     if (p->strip) {
         float* hb = nullptr;
         if (plan_alloc(p, &hb, kAmaxWordUints)) { st_plan_destroy(p); return 1; }
@@ -301,14 +295,15 @@ static int plan_create_common(st_plan** out, const st_net* net, int local_height
         }
         // raw moment sums of the five heads in ONE block: a single all-reduce per closure
         size_t total = 0;
-        for (int i = 0; i < 5; ++i) total += (size_t)p->style[i].n * p->style[i].n + p->style[i].n;
+        for (int k = 0; k < p->n_style; ++k) total += moment_floats(p->head[p->style_op[k]]);
         float* block = nullptr;
         if (plan_alloc(p, &block, total)) { st_plan_destroy(p); return 1; }
         p->gram_total = (long long)total;
-        for (int i = 0; i < 5; ++i) {
-            p->gram_raw[i] = block;
-            block += (size_t)p->style[i].n * p->style[i].n + p->style[i].n;
-            if (plan_alloc(p, &p->head_result[i], (size_t)p->style[i].n * p->style[i].n + p->style[i].n + 64)) {
+        for (int k = 0; k < p->n_style; ++k) {
+            const size_t floats = moment_floats(p->head[p->style_op[k]]);
+            p->gram_raw[k] = block;
+            block += floats;
+            if (plan_alloc(p, &p->head_result[k], floats + 64)) {
                 st_plan_destroy(p);
                 return 1;
             }
@@ -401,9 +396,7 @@ int st_plan_backward(st_plan* p, int count, const int* layers, const float* cons
                "st_plan_step, ... - has run since and left pooling codes instead of maps): run st_plan_forward first");
     const float* seed[kNumOps] = {};
     for (int k = 0; k < count; ++k) {
-        int at = -1;
-        for (int i = 0; i < kNumOps; ++i)
-            if (kProgram[i].feat_index == layers[k]) at = i;
+        const int at = tap_position(layers[k]);
         ST_REQUIRE(at >= 0, "st_plan_backward: features[%d] is not a ReLU or pooling output", layers[k]);
         ST_REQUIRE(layers[k] <= p->fwd_last_layer, "st_plan_backward: features[%d] lies beyond the last forward's last_layer %d",
                    layers[k], p->fwd_last_layer);
@@ -417,8 +410,9 @@ int st_plan_backward(st_plan* p, int count, const int* layers, const float* cons
 
 int st_plan_feature(const st_plan* p, int layer, const float** data, int* channels, int* height, int* width) {
     ST_REQUIRE(p && data, "st_plan_feature: null argument");
-    const Node* n = feature_node(p, layer);
-    ST_REQUIRE(n != nullptr, "st_plan_feature: features[%d] is not a ReLU or pooling output", layer);
+    const int op = tap_position(layer);
+    ST_REQUIRE(op >= 0, "st_plan_feature: features[%d] is not a ReLU or pooling output", layer);
+    const Node* n = &node_at(p, op);
     *data = n->y;
     if (channels) *channels = n->c;
     if (height) *height = n->h;
@@ -428,32 +422,24 @@ int st_plan_feature(const st_plan* p, int layer, const float** data, int* channe
 
 int st_plan_moments(st_plan* p, int layer, float* mean_out, float* srm_out, void* stream) {
     ST_REQUIRE(p && mean_out && srm_out, "st_plan_moments: null argument");
-    int idx = -1;
-    for (int i = 0; i < 5; ++i)
-        if (kStyleFeat[i] == layer) idx = i;
-    if (idx < 0 || !p->taps_default) {
-        // any other of the 17 taps, and every layer of a configured plan (whose st_plan_set_taps has allocated that head already):
-        // the workspace of that position's own head
-        const int op = tap_position(layer);
-        ST_REQUIRE(op >= 0, "st_plan_moments: features[%d] is not a ReLU or pooling output", layer);
-        ST_REQUIRE(!p->strip, "st_plan_moments: strip plans take the reference's style layers only");
-        HeadSite at;
-        at.h = &tap_head_at(p, op);
-        at.tap = feature_node(p, layer);
-        if (ensure_style_alloc(p, *at.h)) return 1;
-        return moments_of_tap(p, at, mean_out, srm_out, static_cast<hipStream_t>(stream));
-    }
-    if (ensure_style_alloc(p, idx)) return 1;
-    return moments_of_tap(p, idx, mean_out, srm_out, static_cast<hipStream_t>(stream));
+    const int op = tap_position(layer);
+    ST_REQUIRE(op >= 0, "st_plan_moments: features[%d] is not a ReLU or pooling output", layer);
+    int j = -1;
+    for (int k = 0; k < p->n_style; ++k)
+        if (p->style_op[k] == op) j = k;
+    ST_REQUIRE(j >= 0 || !p->strip, "st_plan_moments: strip plans take the reference's style layers only");
+    // the workspace of the position's head; a layer of the reference's lists: the default closure's head of that index, whose
+    // Gram conv1_1's launch may have left (run_forward)
+    HeadSite at;
+    at.h = &p->head[op];
+    at.tap = &node_at(p, op);
+    if (j >= 0 && p->reference_taps) at = head_site(p, j);
+    if (ensure_style_alloc(p, *at.h)) return 1;
+    return moments_of_tap(p, at, mean_out, srm_out, static_cast<hipStream_t>(stream));
 }
 
 int st_plan_set_content_target(st_plan* p, const float* feat, void* stream) {
-    ST_REQUIRE(p && feat, "st_plan_set_content_target: null argument");
-    if (!p->taps_default) return st_plan_set_content_target_at(p, 0, feat, stream);
-    ST_HIP(hipMemcpyAsync(p->content_target, feat, p->conv[kContentConv].count() * sizeof(float),
-                          hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
-    p->content_set = true;     // (buffer contents only: a captured graph stays valid)
-    return 0;
+    return st_plan_set_content_target_at(p, 0, feat, stream);
 }
 
 int st_plan_set_style_target(st_plan* p, int index, const float* mean, const float* srm, void* stream) {
@@ -461,7 +447,7 @@ int st_plan_set_style_target(st_plan* p, int index, const float* mean, const flo
     ST_REQUIRE(index >= 0 && index < p->n_style, "st_plan_set_style_target: index %d out of range (%d style layers)", index,
                p->n_style);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    StyleHead& h = p->taps_default ? p->style[index] : tap_head_at(p, p->style_op[index]);
+    StyleHead& h = p->head[p->style_op[index]];
     if (ensure_style_alloc(p, h)) return 1;
     ST_HIP(hipMemcpyAsync(h.mean_t, mean, h.n * sizeof(float), hipMemcpyDeviceToDevice, s));
     if (launch_cov_from_moments(mean, srm, h.cov_t, h.n, kCovEps, s)) return 1;
@@ -473,12 +459,12 @@ int st_plan_set_style_target(st_plan* p, int index, const float* mean, const flo
 int st_plan_set_loss_weights(st_plan* p, float content_weight, const float* style_layer_weights,
                              float tv_weight) {
     ST_REQUIRE(p && style_layer_weights, "st_plan_set_loss_weights: null argument");
-    ST_REQUIRE(p->taps_default, "st_plan_set_loss_weights: the plan's layers were configured (st_plan_set_taps): use st_plan_set_tap_weights");
-    p->content_weight = content_weight;
+    ST_REQUIRE(p->reference_taps, "st_plan_set_loss_weights: the plan's layers were configured (st_plan_set_taps): use st_plan_set_tap_weights");
+    p->content_weight[0] = content_weight;
     for (int i = 0; i < 5; ++i) p->style_weight[i] = style_layer_weights[i];
     p->tv_weight = tv_weight;
     invalidate_graph(p);       // the weights are baked into kernel arguments
-    p->phases.clear();         // (phase lambdas read the weights at run time, but keep it simple)
+    p->phases.clear();         // (a strip's phase sequence is rebuilt by its next closure)
     return 0;
 }
 
@@ -563,10 +549,10 @@ int st_plan_losses(st_plan* p, float** losses) {
 int st_plan_moment_sums(st_plan* p, int layer, float* sums, void* stream) {
     ST_REQUIRE(p && sums, "st_plan_moment_sums: null argument");
     int idx = -1;
-    for (int i = 0; i < 5; ++i)
-        if (kStyleFeat[i] == layer) idx = i;
+    for (int k = 0; k < p->n_style; ++k)
+        if (kProgram[p->style_op[k]].feat_index == layer) idx = k;
     ST_REQUIRE(idx >= 0, "st_plan_moment_sums: features[%d] is not a style layer", layer);
-    if (ensure_style_alloc(p, idx)) return 1;
+    if (ensure_style_alloc(p, p->head[p->style_op[idx]])) return 1;
     return moment_sums_of_tap(p, idx, sums, static_cast<hipStream_t>(stream));
 }
 

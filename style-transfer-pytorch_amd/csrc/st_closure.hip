@@ -259,10 +259,6 @@ int ensure_streams(st_plan* p, hipStream_t caller) {
     return 0;
 }
 
-const Node& op_node(const st_plan* p, int i) {
-    return kProgram[i].kind == 0 ? p->conv[kProgram[i].index] : p->pool[kProgram[i].index];
-}
-
 // a max pool follows kProgram[i] within the pass: the conv's epilogue may write it (fuse_pool)
 bool pool_follows(const st_plan* p, int i, int last_layer) {
     return i + 1 < kNumOps && kProgram[i + 1].kind == 1 && kProgram[i + 1].feat_index <= last_layer && p->net->pooling == 0;
@@ -271,7 +267,7 @@ bool pool_follows(const st_plan* p, int i, int last_layer) {
 void forward_conv(const st_plan* p, int i, ConvProblem& c) {
     const st_net* net = p->net;
     const OpDesc& op = kProgram[i];
-    const Node& in = op_node(p, i - 1);
+    const Node& in = node_at(p, i - 1);
     const Node& n = p->conv[op.index];
     c.in = in.y; c.mask = nullptr; c.wgt = net->w_fwd[op.index]; c.bias = net->bias[op.index];
     c.out = n.y; c.cin = op.cin; c.cout = op.cout; c.height = n.h; c.width = n.w;
@@ -313,9 +309,10 @@ int run_forward(st_plan* p, const float* image, int last_layer, hipStream_t s, b
                 const double hw4 = 4.0 * p->H * p->W;
                 // closure, fp16x3: relu1_1's Gram matrix and mean come out of this launch (conv_first_fwd_gram_kernel) instead
                 // of a second pass over the largest tap; ST_CONV1_GRAM=0: the two-kernel form
-                StyleHead& h0 = p->style[0];
+                // (reference_taps: relu1_1's head serves other lists too, whose closure does not read these partials)
+                StyleHead& h0 = p->head[0];
                 static Option fwd_too("ST_CONV1_GRAM_IN_FORWARD", 0);      // tests: st_plan_forward + st_plan_moments as well
-                p->gram1_fused = (fork_heads || fwd_too.get() != 0) && last_layer >= 1 && bounds && h0.allocated &&
+                p->gram1_fused = (fork_heads || fwd_too.get() != 0) && last_layer >= 1 && bounds && p->reference_taps && h0.allocated &&
                                  conv_first_gram_applies(p->H, p->W, image, n.y, h0.gram.max_splits);
                 if (hbm_profiled(p, HBM_CONV1_FWD, (3 + 64) * hw4, s, [&] {
                         if (p->gram1_fused)
@@ -337,8 +334,8 @@ int run_forward(st_plan* p, const float* image, int last_layer, hipStream_t s, b
             if (fork_heads) {
                 // only mark the tap here; the head's ~66 launches are enqueued after the whole trunk so
                 // that the host never delays the trunk's next kernel (launch cost ~3-5 us each)
-                for (int k = 0; k < 5; ++k)
-                    if (kStyleConv[k] == op.index) ST_HIP(hipEventRecord(p->tap_ready[k], s));
+                for (int k = 0; k < p->n_style; ++k)
+                    if (p->style_op[k] == i) ST_HIP(hipEventRecord(p->tap_ready[k], s));
             }
         } else {
             Node& n = p->pool[op.index];
@@ -349,8 +346,6 @@ int run_forward(st_plan* p, const float* image, int last_layer, hipStream_t s, b
     }
     return 0;
 }
-
-int ensure_style_alloc(st_plan* p, int idx) { return ensure_style_alloc(p, p->style[idx]); }
 
 int ensure_style_alloc(st_plan* p, StyleHead& h) {
     if (h.allocated) return 0;
@@ -405,22 +400,20 @@ static int ablate_side() {
     return opt.get();
 }
 
-// the default closure's head `idx`: it writes the tap's own gradient buffer and bound
-HeadSite head_site(st_plan* p, int idx) {
+// the head of the j-th LISTED style layer as the default and strip closures run it: it writes the tap's own gradient buffer and
+// bound and is the closure's head of that index.  (The general closure redirects it to the seed buffer: general_head_site.)
+HeadSite head_site(st_plan* p, int j) {
     HeadSite at;
-    Node& tap = p->conv[kStyleConv[idx]];
-    at.h = &p->style[idx];
+    const int op = p->style_op[j];
+    Node& tap = node_at(p, op);
+    at.h = &p->head[op];
     at.tap = &tap;
-    at.weight = p->style_weight[idx];
-    at.loss = p->losses + 1 + idx;
+    at.weight = p->style_weight[j];
+    at.loss = p->losses + 1 + j;
     at.grad = tap.g;
     at.grad_amax = tap.g_amax;
-    at.slot = idx;
+    at.slot = j;
     return at;
-}
-
-int moments_of_tap(st_plan* p, int idx, float* mean_out, float* srm_out, hipStream_t s, float* cov_out) {
-    return moments_of_tap(p, head_site(p, idx), mean_out, srm_out, s, cov_out);
 }
 
 int moments_of_tap(st_plan* p, const HeadSite& at, float* mean_out, float* srm_out, hipStream_t s, float* cov_out) {
@@ -445,9 +438,9 @@ int moments_of_tap(st_plan* p, const HeadSite& at, float* mean_out, float* srm_o
 }
 
 // raw sums over the local pixels: sums = [F F^T (C*C) | F 1 (C)]  (strip mode, before the all-reduce)
-int moment_sums_of_tap(st_plan* p, int idx, float* sums, hipStream_t s) {
-    StyleHead& h = p->style[idx];
-    const Node& tap = p->conv[kStyleConv[idx]];
+int moment_sums_of_tap(st_plan* p, int j, float* sums, hipStream_t s) {
+    StyleHead& h = p->head[p->style_op[j]];
+    const Node& tap = node_at(p, p->style_op[j]);
     const int splits = gram_choose_splits(h.n, h.npix_local, h.gram.max_splits);
     if (launch_gram_partial(tap.y, h.n, h.npix_local, splits, h.gram, s, p->net->conv_elem == 1 ? tap.y_amax : nullptr))
         return 1;
@@ -481,18 +474,12 @@ static bool ns_chain_delayed() {
 }
 
 // StyleLossW2.forward + its backward down to the tap's feature gradient.
-int style_head(st_plan* p, int idx, hipStream_t s) { return style_head(p, head_site(p, idx), s); }
-
 int style_head(st_plan* p, const HeadSite& at, hipStream_t s) {
     StyleHead& h = *at.h;
     const bool with_cov = gram_fused_cov();
     if (moments_of_tap(p, at, h.mean, h.srm, s, with_cov ? h.cov : nullptr)) return 1;
     if (style_head_chain(p, at, s, with_cov)) return 1;
     return style_head_gradient(p, at, s);
-}
-
-int style_head_chain(st_plan* p, int idx, hipStream_t s, bool cov_ready) {
-    return style_head_chain(p, head_site(p, idx), s, cov_ready);
 }
 
 int style_head_chain(st_plan* p, const HeadSite& at, hipStream_t s, bool cov_ready) {
@@ -547,6 +534,7 @@ int style_heads_shallow_lockstep(st_plan* p, hipStream_t s, const int* idx, int 
     // idx: `lanes` (1 ... 3) of the shallow heads, in the order the backward needs them
     const bool with_cov = gram_fused_cov();
     StyleHead* h[3];
+    HeadSite at[3];
     int n[3];
     // ST_GRAM_DEFER_PIXELS=n (experiment, default off): on images of >= n pixels hold the shallow taps' Gram kernels back
     // until the forward trunk has ended, i.e. run these image-sized launches in the window in which the trunk waits for
@@ -556,10 +544,11 @@ int style_heads_shallow_lockstep(st_plan* p, hipStream_t s, const int* idx, int 
     static Option defer_opt("ST_GRAM_DEFER_PIXELS", 0);
     const bool defer = defer_opt.get() > 0 && (long long)p->H * p->W >= defer_opt.get();
     for (int l = 0; l < lanes; ++l) {
-        h[l] = &p->style[idx[l]];
+        at[l] = head_site(p, idx[l]);
+        h[l] = at[l].h;
         n[l] = h[l]->n;
         ST_HIP(hipStreamWaitEvent(s, defer ? p->aux_fwd : p->tap_ready[idx[l]], 0));
-        if (moments_of_tap(p, idx[l], h[l]->mean, h[l]->srm, s, with_cov ? h[l]->cov : nullptr)) return 1;
+        if (moments_of_tap(p, at[l], h[l]->mean, h[l]->srm, s, with_cov ? h[l]->cov : nullptr)) return 1;
         if (!with_cov && launch_cov_from_moments(h[l]->mean, h[l]->srm, h[l]->cov, n[l], kCovEps, s)) return 1;
     }
     auto batch3 = [&](auto make) {
@@ -581,8 +570,7 @@ int style_heads_shallow_lockstep(st_plan* p, hipStream_t s, const int* idx, int 
     for (int l = 0; l < lanes; ++l) { mm[l] = h[l]->mmat; roots[l] = h[l]->root; ws[l] = &h[l]->ns; }
     W2LossJob jobs[3];
     for (int l = 0; l < lanes; ++l)
-        jobs[l] = W2LossJob{h[l]->mean, h[l]->mean_t, h[l]->cov, h[l]->cov_t, h[l]->root, n[l], p->style_weight[idx[l]],
-                            p->losses + 1 + idx[l], h[l]->gdiag};
+        jobs[l] = W2LossJob{h[l]->mean, h[l]->mean_t, h[l]->cov, h[l]->cov_t, h[l]->root, n[l], at[l].weight, at[l].loss, h[l]->gdiag};
     const float* croots[3] = {};
     const float* gd[3] = {};
     float* gm[3] = {};
@@ -601,10 +589,10 @@ int style_heads_shallow_lockstep(st_plan* p, hipStream_t s, const int* idx, int 
     if (batch3([&](int l) { return one_gemm(n[l], h[l]->root_t, h[l]->dt, h[l]->dcov, 1, 0).p[0]; })) return 1;
     const bool f16 = p->net->conv_elem == 1;
     for (int l = 0; l < lanes; ++l) {
-        if (launch_style_grad_finish(h[l]->dcov, h[l]->mean, h[l]->mean_t, n[l], p->style_weight[idx[l]], h[l]->npix, h[l]->ssym,
-                                     h[l]->bvec, s, f16 ? h[l]->s_amax : nullptr))
+        if (launch_style_grad_finish(h[l]->dcov, h[l]->mean, h[l]->mean_t, n[l], at[l].weight, h[l]->npix, h[l]->ssym, h[l]->bvec, s,
+                                     f16 ? h[l]->s_amax : nullptr))
             return 1;
-        if (style_head_gradient(p, idx[l], s)) return 1;
+        if (style_head_gradient(p, at[l], s)) return 1;
         ST_HIP(hipEventRecord(p->head_done[idx[l]], s));
         if (p->timeline) ST_HIP(hipEventRecord(p->tl_head[idx[l]], s));
     }
@@ -616,8 +604,6 @@ static bool head5_masks_its_gradient() {
     static Option opt("ST_HEAD5_MASK", 1);
     return opt.get() != 0;
 }
-
-int style_head_gradient(st_plan* p, int idx, hipStream_t s) { return style_head_gradient(p, head_site(p, idx), s); }
 
 int style_head_gradient(st_plan* p, const HeadSite& at, hipStream_t s) {
     StyleHead& h = *at.h;
@@ -650,16 +636,18 @@ int style_head_gradient(st_plan* p, const HeadSite& at, hipStream_t s) {
     return hbm_profiled(p, HBM_HEAD_1X1, 2.0 * n * (double)tap.h * tap.w * sizeof(float), s, [&] { return launch_conv(c, s); });
 }
 
-bool conv_is_tap(int conv_index) {
-    if (conv_index == kContentConv) return true;
-    for (int k : kStyleConv)
-        if (k == conv_index) return true;
+// kProgram[op] is one of the listed content or style layers
+bool op_is_tap(const st_plan* p, int op) {
+    for (int i = 0; i < p->n_content; ++i)
+        if (p->content_op[i] == op) return true;
+    for (int k = 0; k < p->n_style; ++k)
+        if (p->style_op[k] == op) return true;
     return false;
 }
 
 int join_head_for_conv(st_plan* p, int conv_index, hipStream_t s) {
-    for (int k = 0; k < 5; ++k) {
-        if (kStyleConv[k] != conv_index) continue;
+    for (int k = 0; k < p->n_style; ++k) {
+        if (!head_taps_conv(p, k, conv_index)) continue;
         ST_HIP(hipStreamWaitEvent(s, p->head_done[k], 0));
     }
     return 0;
@@ -670,16 +658,19 @@ void dgrad_conv(const st_plan* p, int i, ConvProblem& c) {
     const OpDesc& op = kProgram[i];
     const OpDesc& pop = kProgram[i - 1];
     const Node& n = p->conv[op.index];
-    const Node& in = op_node(p, i - 1);
+    const Node& in = node_at(p, i - 1);
+    // (mask and accumulate below serve the default and strip closures, which run the reference's lists only - relu5_1's head
+    // on top; run_tap_backward and the range guard set both themselves)
+    const bool top = i == kNumOps - 1;
     // threshold_backward: every gradient tensor is masked by its PRODUCER (the previous data-gradient
     // conv's out_mask, or pool_bwd), so the staging needs no mask stream - except at the top, where the
     // gradient comes straight from relu5_1's style head (whose 1x1 launch masks it, style_head_gradient)
-    c.in = n.g; c.mask = (op.index == kStyleConv[4] && !head5_masks_its_gradient()) ? n.y : nullptr;
+    c.in = n.g; c.mask = (top && !head5_masks_its_gradient()) ? n.y : nullptr;
     c.out_mask = (pop.kind == 0) ? in.y : nullptr;
     c.wgt = net->w_bwd[op.index]; c.bias = nullptr; c.out = in.g;
     c.cin = op.cout; c.cout = op.cin; c.height = n.h; c.width = n.w; c.taps = 9; c.relu = 0;
     // (the launch ACCUMULATES into a style or content tap's gradient, which that tap's head has written)
-    c.accumulate = (pop.kind == 0 && conv_is_tap(pop.index)) ? 1 : 0;
+    c.accumulate = (pop.kind == 0 && op_is_tap(p, i - 1)) ? 1 : 0;
     c.scratch = p->conv_scratch;
     conv_arithmetic(net, op.index, true, c);
     c.amax_word = n.g_amax; c.out_amax = net->conv_elem == 1 ? in.g_amax : nullptr;
@@ -709,8 +700,7 @@ int run_backward(st_plan* p, float* grad_image, hipStream_t s) {
             // ... and this launch ACCUMULATES into the input node's gradient: if that node is a style
             // tap, its head (which WRITES the buffer first) must have finished
             if (pop.kind == 0 && join_head_for_conv(p, pop.index, s)) return 1;
-            if (pop.kind == 0 && pop.index == kContentConv)
-                ST_HIP(hipStreamWaitEvent(s, p->content_done, 0));
+            if (i - 1 == p->content_op[0]) ST_HIP(hipStreamWaitEvent(s, p->content_done, 0));
             ConvProblem c{};
             dgrad_conv(p, i, c);
             if (conv_launch_profiled(p, c, s)) return 1;
@@ -746,13 +736,12 @@ int run_tap_backward(st_plan* p, const float* const* seed, float* grad_image, hi
     for (int i = 0; i < kNumOps; ++i)
         if (seed[i]) top = i;
     ST_REQUIRE(top >= 0, "st_plan_backward: no tap gradient given");
-    auto node = [&](int i) -> Node& { return kProgram[i].kind == 0 ? p->conv[kProgram[i].index] : p->pool[kProgram[i].index]; };
     // a forward clears the bounds at ITS start only: every max |g| this pass reads is re-established by this pass
     if (bounds)
         ST_HIP(hipMemsetAsync(reinterpret_cast<unsigned int*>(p->amax_word) + (size_t)16 * kAmaxWordUints, 0,
                               (size_t)32 * kAmaxWordUints * sizeof(unsigned int), s));
     {
-        Node& n = node(top);
+        Node& n = node_at(p, top);
         if (launch_seed_grad(seed[top], kProgram[top].kind == 0 ? n.y : nullptr, n.g, (long long)n.count(), 0,
                              bounds ? n.g_amax : nullptr, s))
             return 1;
@@ -770,7 +759,7 @@ int run_tap_backward(st_plan* p, const float* const* seed, float* grad_image, hi
             if (onto_image) p->fold_updated = p->fold_update != nullptr;
             return 0;
         }
-        Node& in = node(i - 1);
+        Node& in = node_at(p, i - 1);
         const float* in_seed = seed[i - 1];
         if (op.kind == 0) {
             if (in_seed && launch_seed_grad(in_seed, nullptr, in.g, (long long)in.count(), 0, nullptr, s)) return 1;
@@ -802,19 +791,14 @@ static bool shallow_heads_lockstep(const st_plan* p) {
     return opt.get() != 0 && p->net->conv_elem == 1;
 }
 
+// targets_ready (st_taps.hip) with messages
 int require_targets(const st_plan* p) {
-    if (!p->taps_default) {
-        for (int i = 0; i < p->n_content; ++i)
-            ST_REQUIRE(p->tap_content_set[p->content_op[i]], "content target %d (features[%d]) not set (st_plan_set_content_target_at)", i,
-                       kProgram[p->content_op[i]].feat_index);
-        for (int i = 0; i < p->n_style; ++i)
-            ST_REQUIRE(p->tap_head[p->style_op[i]].target_set, "style target %d (features[%d]) not set (st_plan_set_style_target)", i,
-                       kProgram[p->style_op[i]].feat_index);
-        return 0;
-    }
-    ST_REQUIRE(p->content_set, "content target not set (st_plan_set_content_target)");
-    for (int i = 0; i < 5; ++i)
-        ST_REQUIRE(p->style[i].target_set, "style target %d not set (st_plan_set_style_target)", i);
+    for (int i = 0; i < p->n_content; ++i)
+        ST_REQUIRE(p->content_set[p->content_op[i]], "content target %d (features[%d]) not set (st_plan_set_content_target_at)", i,
+                   kProgram[p->content_op[i]].feat_index);
+    for (int j = 0; j < p->n_style; ++j)
+        ST_REQUIRE(p->head[p->style_op[j]].target_set, "style target %d (features[%d]) not set (st_plan_set_style_target)", j,
+                   kProgram[p->style_op[j]].feat_index);
     return 0;
 }
 
@@ -856,12 +840,13 @@ int loss_and_grad(st_plan* p, const float* image, float* grad_out, float* losses
     if (p->timeline) ST_HIP(hipEventRecord(p->tl_fwd, s));
     // ContentLossMSE on relu4_2: WRITES that tap's gradient buffer (auxiliary stream, or the tail of relu4_1's head stream;
     // joined before conv4_3's data gradient accumulates into it)
-    Node& ct = p->conv[kContentConv];
+    const int cop = p->content_op[0];
+    Node& ct = node_at(p, cop);
     ST_HIP(hipEventRecord(p->aux_fwd, s));
     auto content = [&](hipStream_t cstream) {
         ST_HIP(hipStreamWaitEvent(cstream, p->aux_fwd, 0));
         if (hbm_profiled(p, HBM_CONTENT, 3.0 * 4.0 * ct.count(), cstream, [&] {
-                return launch_content_mse(ct.y, p->content_target, (long long)ct.count(), p->content_weight, ct.g,
+                return launch_content_mse(ct.y, p->content_target[cop], (long long)ct.count(), p->content_weight[0], ct.g,
                                           p->red_partials + 4 * kStreamBlocks, p->losses + 0, cstream, p->tickets + 64);
             }))
             return 1;
@@ -876,6 +861,7 @@ int loss_and_grad(st_plan* p, const float* image, float* grad_out, float* losses
     // stream and ~62 launches per head, as rounds 1 / 2 (A/B: 512^2 416.5 -> 422.8 it/s, 256^2 650 -> 664, 181^2 646 / 609 ->
     // 656, 128^2 588 ... 619 -> 753 ... 779 - the slow mode of the small scales, where a shallow head shared relu5_1's
     // hardware queue, is gone)
+    // (this closure runs the reference's lists only - closure_eager: head k is relu(k+1)_1's, content_op[0] is relu4_2)
     const bool lockstep = shallow_heads_lockstep(p);
     for (int k = 4; k >= (lockstep ? 3 : 0); --k) {
         // (head4_on_caller, the shipped form: relu5_1's head runs on the caller's stream itself - the trunk waits for that
@@ -886,7 +872,7 @@ int loss_and_grad(st_plan* p, const float* image, float* grad_out, float* losses
         if (!on_caller && ensure_head_stream(p, k)) return 1;
         hipStream_t hs = on_caller ? s : p->head_stream[k];
         if (!on_caller) ST_HIP(hipStreamWaitEvent(hs, p->tap_ready[k], 0));
-        if (style_head(p, k, hs)) return 1;
+        if (style_head(p, head_site(p, k), hs)) return 1;
         ST_HIP(hipEventRecord(p->head_done[k], hs));
         if (p->timeline) ST_HIP(hipEventRecord(p->tl_head[k], hs));
         if (k == 3 && !p->aux_stream && content(p->head_stream[3])) return 1;

@@ -26,9 +26,6 @@ const OpDesc kProgram[] = {
     {0, 12, 29, 512, 512},
 };
 constexpr int kNumOps = sizeof(kProgram) / sizeof(kProgram[0]);
-const int kStyleFeat[5] = {1, 6, 11, 20, 29};     // style_transfer.py:317
-const int kStyleConv[5] = {0, 2, 4, 8, 12};
-constexpr int kContentConv = 9;                   // relu4_2 = features[22]
 constexpr float kCovEps = 1e-4f;                  // StyleLossW2 eps (style_transfer.py:152)
 
 struct Node {
@@ -67,8 +64,8 @@ struct StyleHead {
     bool allocated = false;
 };
 
-// Where a W2 style head sits.  The default closure's five heads are head_site(p, idx); the general closure (st_taps.hip) puts
-// one on any of the 17 taps.
+// Where a W2 style head sits: head_site(p, j) for the j-th LISTED style layer in the default and strip closures, the same
+// with the seed buffer as destination in the general closure (st_taps.hip), by hand for an unlisted position (st_plan_moments).
 struct HeadSite {
     StyleHead* h = nullptr;
     const Node* tap = nullptr;       // the tap's node (a conv's ReLU output or a pooled map)
@@ -129,12 +126,28 @@ struct st_plan {
     bool grads_allocated = false;
     int fwd_last_layer = 0;          // st_plan_forward's last_layer while the maps it wrote are current (st_plan_backward's
                                      // operands); 0: none has run, or a closure has since (argmax codes instead of maps)
-    float* content_target = nullptr;
-    bool content_set = false;
-    st::StyleHead style[5];
-    float content_weight = 0.015f;
-    float style_weight[5] = {256.f / 341, 64.f / 341, 16.f / 341, 4.f / 341, 1.f / 341};
+    // The loss terms, ONE description for every configuration: the content / style lists as kProgram positions with a weight
+    // per LISTED entry, and the W2 head, content target and seed buffer of a position, indexed by kProgram position.
+    // st_plan_set_taps replaces the lists; a head or target buffer serves whichever configuration names its position.
+    // reference_taps: the lists are the reference's own ([22], [1, 6, 11, 20, 29], style_transfer.py:315-322).  It selects
+    // WHICH closure runs - loss_and_grad (st_closure.hip) for them, general_loss_and_grad (st_taps.hip) for every other
+    // configuration - and what follows from that: the terms array and its sum kernel (loss_terms, st_plan_term_losses),
+    // st_plan_set_loss_weights' refusal, and conv1_1's fused Gram with the one consumer of its partials outside the closure
+    // (run_forward, st_plan_moments).  Never which state is read.
+    bool reference_taps = true;
+    int n_content = 1, n_style = 5;
+    int content_op[16] = {12};
+    int style_op[16] = {0, 3, 6, 11, 16};
+    float content_weight[16] = {0.015f};             // per LISTED entry
+    float style_weight[16] = {256.f / 341, 64.f / 341, 16.f / 341, 4.f / 341, 1.f / 341};
     float tv_weight = 2.0f;
+    st::StyleHead head[st::kNumOps];                 // n / npix / npix_local of all 17 filled at create, buffers on first use;
+                                                     // bound word: the j-th listed head owns word 48 + j, an unlisted one is parked on 63
+    float* content_target[st::kNumOps] = {};         // allocated when a list first names the position ([12] at create)
+    bool content_set[st::kNumOps] = {};
+    float* tap_seed[st::kNumOps] = {};               // general closure: the heads' gradient of a tapped position, run_tap_backward's seed
+    float* terms = nullptr;                          // general closure on other lists than the reference's: [64], at most 16 + 16 + 1
+                                                     // used - the weighted terms in SumLoss order (st_plan_term_losses)
     float* grad_img = nullptr;       // [3][H][W] internal gradient for st_plan_step
     float* losses = nullptr;         // [8] device
     float* red_partials = nullptr;   // scratch for two-level reductions: TV [0, 4 kStreamBlocks), content MSE after it
@@ -238,23 +251,25 @@ struct st_plan {
     bool amax_clean = false;         // the update kernel has cleared amax_word: the next run_forward skips its memset
     const st::FoldUpdate* fold_update = nullptr;     // st_plan_step: conv1_1's fold kernel applies the update (and the tail)
     bool fold_updated = false;       // ... and has done so in this closure
-    // st_plan_set_taps: the configured content / style lists as kProgram positions.  taps_default: they are the reference's
-    // own ([22], [1, 6, 11, 20, 29]) - the plan runs loss_and_grad on style[] / content_target above; every other
-    // configuration runs general_loss_and_grad (st_taps.hip) on the per-position heads and targets below.
-    bool taps_default = true;
-    int n_content = 1, n_style = 5;
-    int content_op[16] = {12};
-    int style_op[16] = {0, 3, 6, 11, 16};
-    float tap_content_weight[16] = {};
-    float tap_style_weight[16] = {};
-    st::StyleHead tap_head[st::kNumOps];             // the W2 head of a position (allocated when a list first names it)
-    float* tap_content_target[st::kNumOps] = {};
-    bool tap_content_set[st::kNumOps] = {};
-    float* tap_seed[st::kNumOps] = {};               // the heads' gradient of a tapped position: run_tap_backward's seed
-    float* terms = nullptr;                          // [64], at most 16 + 16 + 1 used: the weighted terms in SumLoss order (st_plan_term_losses)
 };
 
 namespace st {
+
+// the node of kProgram[op]
+inline Node& node_at(st_plan* p, int op) { return kProgram[op].kind == 0 ? p->conv[kProgram[op].index] : p->pool[kProgram[op].index]; }
+inline const Node& node_at(const st_plan* p, int op) { return node_at(const_cast<st_plan*>(p), op); }
+// the k-th listed style layer is conv `conv_index`'s ReLU
+inline bool head_taps_conv(const st_plan* p, int k, int conv_index) {
+    return kProgram[p->style_op[k]].kind == 0 && kProgram[p->style_op[k]].index == conv_index;
+}
+// The heads' bound words (plan creation, st_plan_set_taps): the j-th listed head owns word 48 + j, and every unlisted head is
+// parked on word 63, which a listed one owns only in a list of 16.  A parked head commits no bound (st_plan_moments reads
+// the tap's, not the head's), so nothing aliases; heads that move to side streams must keep it that way.
+inline void assign_head_bounds(st_plan* p) {
+    unsigned int* words = reinterpret_cast<unsigned int*>(p->amax_word);
+    for (StyleHead& h : p->head) h.s_amax = words + (size_t)63 * kAmaxWordUints;
+    for (int j = 0; j < p->n_style; ++j) p->head[p->style_op[j]].s_amax = words + (size_t)(48 + j) * kAmaxWordUints;
+}
 
 constexpr int kHaloTrailer = 16;            // floats; word 0 = the sender's max |row| (raw bits), the rest unused (64-byte alignment)
 
@@ -281,18 +296,13 @@ int hbm_profiled(st_plan* p, int cat, double bytes, hipStream_t s, F&& launch) {
 
 void invalidate_graph(st_plan* p);
 int ensure_streams(st_plan* p, hipStream_t caller = nullptr);
-int ensure_style_alloc(st_plan* p, int idx);
 int ensure_style_alloc(st_plan* p, StyleHead& h);
 int ensure_grad_alloc(st_plan* p);
-HeadSite head_site(st_plan* p, int idx);
-int moments_of_tap(st_plan* p, int idx, float* mean_out, float* srm_out, hipStream_t s, float* cov_out = nullptr);
+HeadSite head_site(st_plan* p, int j);
 int moments_of_tap(st_plan* p, const HeadSite& at, float* mean_out, float* srm_out, hipStream_t s, float* cov_out = nullptr);
-int moment_sums_of_tap(st_plan* p, int idx, float* sums, hipStream_t s);
-int style_head(st_plan* p, int idx, hipStream_t s);
+int moment_sums_of_tap(st_plan* p, int j, float* sums, hipStream_t s);
 int style_head(st_plan* p, const HeadSite& at, hipStream_t s);
-int style_head_chain(st_plan* p, int idx, hipStream_t s, bool cov_ready = false);
 int style_head_chain(st_plan* p, const HeadSite& at, hipStream_t s, bool cov_ready = false);
-int style_head_gradient(st_plan* p, int idx, hipStream_t s);
 int style_head_gradient(st_plan* p, const HeadSite& at, hipStream_t s);
 int join_head_for_conv(st_plan* p, int conv_index, hipStream_t s);
 int require_targets(const st_plan* p);
@@ -315,7 +325,7 @@ int general_loss_and_grad(st_plan* p, const float* image, float* grad_out, float
 int tap_position(int layer);          // kProgram position of features[layer], -1: not one of the 17 taps
 int closure_top_op(const st_plan* p); // the deepest kProgram position the plan's closure runs
 bool targets_ready(const st_plan* p);
-StyleHead& tap_head_at(st_plan* p, int op);
+float* loss_terms(st_plan* p);        // the array the closure's weighted terms go to, in SumLoss order
 
 // ---- st_strip.hip
 int halo_alloc(st_plan* p, float** out, size_t floats);

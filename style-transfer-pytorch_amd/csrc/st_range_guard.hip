@@ -142,7 +142,7 @@ int plan_range_guard(st_plan* p, const float* image, hipStream_t s, int* new_fwd
         bool flagged = false;
         for (int i = 0; i < kNumOps && !flagged; ++i) {
             const OpDesc& op = kProgram[i];
-            const Node& n = op.kind == 0 ? p->conv[op.index] : p->pool[op.index];
+            const Node& n = node_at(p, i);
             if (op.kind == 0 && op.index > 0 && !net->wide_fwd[op.index]) {
                 if (ensure_wide_planes(net, op.index, false)) return finish(1);
                 // (pre-activations: with the ReLU in place a nearly dead channel differs between any two arithmetics in WHICH
@@ -177,8 +177,7 @@ int plan_range_guard(st_plan* p, const float* image, hipStream_t s, int* new_fwd
         for (int i = closure_top_op(p); i >= 0 && !flagged; --i) {
             const OpDesc& op = kProgram[i];
             if (op.kind != 0 || op.index == 0 || op.index >= lowest_checked) continue;
-            const OpDesc& pop = kProgram[i - 1];
-            const Node& in = (pop.kind == 0) ? p->conv[pop.index] : p->pool[pop.index];
+            const Node& in = node_at(p, i - 1);
             if (net->wide_bwd[op.index]) { lowest_checked = op.index; continue; }
             if (ensure_wide_planes(net, op.index, true)) return finish(1);
             for (int mode = 0; mode < 3; ++mode) {

@@ -144,7 +144,7 @@ bool heads_owned(const st_plan* p) {
 
 // Sharded plans: the head's OWNER rank has run style_head_chain; (Ssym | b | loss term) travel in one block.
 int style_head_result_pack(st_plan* p, int idx, hipStream_t s) {          // owner, before the broadcast
-    StyleHead& h = p->style[idx];
+    StyleHead& h = p->head[p->style_op[idx]];
     const size_t nn = (size_t)h.n * h.n;
     float* r = p->head_result[idx];
     ST_HIP(hipMemcpyAsync(r, h.ssym, nn * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -153,7 +153,7 @@ int style_head_result_pack(st_plan* p, int idx, hipStream_t s) {          // own
     return 0;
 }
 int style_head_result_unpack(st_plan* p, int idx, hipStream_t s) {        // every rank, after the broadcast
-    StyleHead& h = p->style[idx];
+    StyleHead& h = p->head[p->style_op[idx]];
     const size_t nn = (size_t)h.n * h.n;
     const float* r = p->head_result[idx];
     ST_HIP(hipMemcpyAsync(h.ssym, r, nn * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -270,11 +270,11 @@ void build_forward_phases(st_plan* p, PhaseBuilder& b, const float* image, int l
         }
         prev = n;
         if (fork_heads && op.kind == 0) {
-            for (int k = 0; k < 5; ++k) {
-                if (kStyleConv[k] != op.index) continue;
+            for (int k = 0; k < p->n_style; ++k) {
+                if (p->style_op[k] != i) continue;
                 const bool owned = heads_owned(p);
                 const int owner = head_owner(p, k);
-                const long long nn = (long long)p->style[k].n * p->style[k].n;
+                const long long ch = p->head[i].n, nn = ch * ch;
                 b.add([=](hipStream_t s) {
                     if (ensure_streams(p)) return 1;
                     hipStream_t hs = p->head_stream[k];
@@ -284,11 +284,11 @@ void build_forward_phases(st_plan* p, PhaseBuilder& b, const float* image, int l
                 });
                 // (the first phase of a closure has created the streams; before that the handle is null and the
                 // descriptor is rebuilt - see st_plan_closure_begin)
-                st_exchange ex = owned ? rooted_exchange(4, p->gram_raw[k], nn + p->style[k].n, owner)
-                                       : allreduce_exchange(p->gram_raw[k], nn + p->style[k].n);
+                st_exchange ex = owned ? rooted_exchange(4, p->gram_raw[k], nn + ch, owner)
+                                       : allreduce_exchange(p->gram_raw[k], nn + ch);
                 b.flush(on_stream(ex, p->head_stream[k], 1));
                 b.add([=](hipStream_t) {
-                    StyleHead& h = p->style[k];
+                    StyleHead& h = p->head[i];
                     if (owned && p->rank != owner) return 0;               // the owner's result arrives by broadcast
                     // the chain runs on the chain stream (compact layout) behind this head's reduction
                     hipStream_t hs = p->chain_stream ? p->chain_stream : p->head_stream[k];
@@ -296,13 +296,13 @@ void build_forward_phases(st_plan* p, PhaseBuilder& b, const float* image, int l
                     ST_HIP(hipStreamWaitEvent(hs, p->moments_ready[k], 0));
                     if (launch_div_by_scalar(p->gram_raw[k], (float)h.npix, h.srm, nn, hs)) return 1;
                     if (launch_div_by_scalar(p->gram_raw[k] + nn, (float)h.npix, h.mean, h.n, hs)) return 1;
-                    if (style_head_chain(p, k, hs)) return 1;
+                    if (style_head_chain(p, head_site(p, k), hs)) return 1;
                     if (owned) {
                         if (style_head_result_pack(p, k, hs)) return 1;
                         ST_HIP(hipEventRecord(p->chain_done[k], hs));      // (the broadcast on the head's stream waits for it)
                         return 0;
                     }
-                    if (style_head_gradient(p, k, hs)) return 1;
+                    if (style_head_gradient(p, head_site(p, k), hs)) return 1;
                     ST_HIP(hipEventRecord(p->head_done[k], hs));
                     return 0;
                 });
@@ -337,16 +337,17 @@ int build_closure_phases(st_plan* p, const float* image, float* grad_out) {
         StripInfo si{p->row0, p->Hg, p->has_up, p->has_down, p->img_halo};
         return launch_tv_strip(image, p->H, p->W, si, p->tv_weight, grad_out, p->red_partials, p->lossbuf + 1, s);
     });
-    Node* ct = &p->conv[kContentConv];
+    Node* ct = &node_at(p, p->content_op[0]);
+    const float* content_target = p->content_target[p->content_op[0]];
     b.add([=](hipStream_t s) {
         const long long global_count = (long long)ct->c * ct->hg * ct->w;
-        return launch_content_mse_strip(ct->y, p->content_target, (long long)ct->count(), global_count,
-                                        p->content_weight, ct->g, p->red_partials + 4 * kStreamBlocks, p->lossbuf, s);
+        return launch_content_mse_strip(ct->y, content_target, (long long)ct->count(), global_count,
+                                        p->content_weight[0], ct->g, p->red_partials + 4 * kStreamBlocks, p->lossbuf, s);
     });
     b.flush(allreduce_exchange(p->lossbuf, 5));
     b.add([=](hipStream_t s) {
         const long long global_count = (long long)ct->c * ct->hg * ct->w;
-        if (launch_content_mse_final(p->lossbuf, global_count, p->content_weight, p->losses + 0, s)) return 1;
+        if (launch_content_mse_final(p->lossbuf, global_count, p->content_weight[0], p->losses + 0, s)) return 1;
         return launch_tv_final(p->lossbuf + 1, p->Hg, p->W, p->tv_weight, p->losses + 6, s);
     });
     // The style heads were forked tap by tap during the forward phases.  With owned heads the broadcasts are issued
@@ -354,10 +355,11 @@ int build_closure_phases(st_plan* p, const float* image, float* grad_out) {
     // order, so a broadcast issued at tap time would hold every later head's reduction behind the owner's chain.
     const bool owned = heads_owned(p);
     auto join_head = [&](int conv_index) {
-        for (int k = 0; k < 5; ++k) {
-            if (kStyleConv[k] != conv_index || !owned || p->style[k].joined_in_build) continue;
-            p->style[k].joined_in_build = true;
-            const long long cnt = (long long)p->style[k].n * p->style[k].n + p->style[k].n + 1;
+        for (int k = 0; k < p->n_style; ++k) {
+            StyleHead& h = p->head[p->style_op[k]];
+            if (!head_taps_conv(p, k, conv_index) || !owned || h.joined_in_build) continue;
+            h.joined_in_build = true;
+            const long long cnt = (long long)h.n * h.n + h.n + 1;
             if (p->rank == head_owner(p, k))
                 b.add([=](hipStream_t) {
                     ST_HIP(hipStreamWaitEvent(p->head_stream[k], p->chain_done[k], 0));
@@ -367,13 +369,13 @@ int build_closure_phases(st_plan* p, const float* image, float* grad_out) {
             b.add([=](hipStream_t) {
                 hipStream_t hs = p->head_stream[k];
                 if (style_head_result_unpack(p, k, hs)) return 1;
-                if (style_head_gradient(p, k, hs)) return 1;
+                if (style_head_gradient(p, head_site(p, k), hs)) return 1;
                 ST_HIP(hipEventRecord(p->head_done[k], hs));
                 return 0;
             });
         }
     };
-    for (int k = 0; k < 5; ++k) p->style[k].joined_in_build = false;
+    for (int k = 0; k < p->n_style; ++k) p->head[p->style_op[k]].joined_in_build = false;
     // backward trunk: before each data gradient the masked boundary rows of its operand are exchanged
     const st_net* net = p->net;
     for (int i = kNumOps - 1; i >= 0; --i) {
@@ -434,8 +436,8 @@ int st_plan_closure_begin(st_plan* p, const float* image, float* grad_out) {
     ST_REQUIRE(p && image && grad_out, "st_plan_closure_begin: null argument");
     ST_REQUIRE(p->strip, "st_plan_closure_begin: not a strip plan (use st_plan_create_strip)");
     if (require_targets(p) || ensure_grad_alloc(p)) return 1;
-    for (int i = 0; i < 5; ++i)
-        if (ensure_style_alloc(p, i)) return 1;
+    for (int k = 0; k < p->n_style; ++k)
+        if (ensure_style_alloc(p, p->head[p->style_op[k]])) return 1;
     // (the tile / overlap / ownership decisions of the phase sequence depend on the library's switches)
     if (p->ph_image != image || p->ph_grad != grad_out || p->ph_last_layer != -1 || p->phases.empty() ||
         p->ph_option_gen != option_generation()) {

@@ -1,6 +1,10 @@
 // Configured taps (st_plan_set_taps): the reference's content_layers / style_layers / style_weights (style_transfer.py:315-322,
 // read by every scale at :425-453) on any of the trunk's 17 taps, and the GENERAL closure that serves them.
 //
+// A plan describes its loss terms once (st_plan.h): the two lists as kProgram positions, a weight per listed entry, and the
+// head, content target and seed buffer of a POSITION.  Both closures, the strips and the entry points below read that one
+// store; st_plan::reference_taps only says which closure runs.
+//
 // The reference's own configuration - content [22], style [1, 6, 11, 20, 29] - stays on loss_and_grad (st_closure.hip): the
 // fused conv1_1 Gram, the pools' argmax codes, the shallow heads in lockstep, the heads' streams.  Every other one runs
 // general_loss_and_grad below, put together from the same parts without those specialisations:
@@ -22,9 +26,10 @@
 namespace st {
 
 namespace {
-Node& node_at(st_plan* p, int op) { return kProgram[op].kind == 0 ? p->conv[kProgram[op].index] : p->pool[kProgram[op].index]; }
-const int kDefaultStyleOp[5] = {0, 3, 6, 11, 16};
-constexpr int kDefaultContentOp = 12;
+// the reference's own lists and weights (style_transfer.py:315-322, :366): what a fresh plan holds
+constexpr int kContentFeat = 22;
+const int kStyleFeat[5] = {1, 6, 11, 20, 29};
+const float kStyleWeight[5] = {256.f / 341, 64.f / 341, 16.f / 341, 4.f / 341, 1.f / 341};
 }  // namespace
 
 int tap_position(int layer) {
@@ -35,7 +40,7 @@ int tap_position(int layer) {
 
 bool general_taps(const st_plan* p) {
     static Option force("ST_GENERAL_TAPS", 0);
-    return !p->strip && (!p->taps_default || force.get() != 0);
+    return !p->strip && (!p->reference_taps || force.get() != 0);
 }
 
 int closure_top_op(const st_plan* p) {
@@ -47,36 +52,27 @@ int closure_top_op(const st_plan* p) {
 }
 
 bool targets_ready(const st_plan* p) {
-    if (p->taps_default) {
-        bool ok = p->content_set;
-        for (int i = 0; i < 5; ++i) ok = ok && p->style[i].target_set;
-        return ok;
-    }
     bool ok = true;
-    for (int i = 0; i < p->n_content; ++i) ok = ok && p->tap_content_set[p->content_op[i]];
-    for (int i = 0; i < p->n_style; ++i) ok = ok && p->tap_head[p->style_op[i]].target_set;
+    for (int i = 0; i < p->n_content; ++i) ok = ok && p->content_set[p->content_op[i]];
+    for (int j = 0; j < p->n_style; ++j) ok = ok && p->head[p->style_op[j]].target_set;
     return ok;
 }
 
-// the W2 head of a position that is not one of the default closure's five (shapes from the node; buffers when first needed).
-// Bound words: st_plan_set_taps gives the j-th listed head word 48 + j and parks every unlisted one on word 63, which a
-// listed head owns only in a list of 16.  A parked head commits no bound (st_plan_moments reads the tap's, not the head's),
-// so nothing aliases today; heads that move to side streams must keep it that way.
-StyleHead& tap_head_at(st_plan* p, int op) {
-    StyleHead& h = p->tap_head[op];
-    if (h.n == 0) {
-        const Node& tap = node_at(p, op);
-        h.n = tap.c;
-        h.npix = (long long)tap.hg * tap.w;
-        h.npix_local = (long long)tap.h * tap.w;
-        h.s_amax = reinterpret_cast<unsigned int*>(p->amax_word) + (size_t)(48 + 15) * kAmaxWordUints;
-    }
-    return h;
-}
+// the reference's configuration: the 8-float array IS the terms in SumLoss order, whichever closure runs
+float* loss_terms(st_plan* p) { return p->reference_taps ? p->losses : p->terms; }
 
 namespace {
 
-StyleHead& configured_head(st_plan* p, int j) { return p->taps_default ? p->style[j] : tap_head_at(p, p->style_op[j]); }
+// the j-th listed head as THIS closure runs it: dF goes to the position's seed buffer (run_tap_backward commits the bound),
+// the term behind the content terms, and none of the default closure's slot-keyed specialisations apply
+HeadSite general_head_site(st_plan* p, int j) {
+    HeadSite at = head_site(p, j);
+    at.loss = loss_terms(p) + p->n_content + j;
+    at.grad = p->tap_seed[p->style_op[j]];
+    at.grad_amax = nullptr;
+    at.slot = -1;
+    return at;
+}
 
 // seed buffers of the tapped positions and the terms' array
 int ensure_tap_buffers(st_plan* p) {
@@ -97,8 +93,7 @@ int ensure_tap_buffers(st_plan* p) {
 int general_loss_and_grad(st_plan* p, const float* image, float* grad_out, float* losses_out, hipStream_t s) {
     if (require_targets(p) || ensure_grad_alloc(p) || ensure_streams(p, s) || ensure_tap_buffers(p)) return 1;
     const int nc = p->n_content, ns = p->n_style;
-    // the reference's configuration (ST_GENERAL_TAPS): the 8-float array IS the terms in SumLoss order
-    float* terms = p->taps_default ? p->losses : p->terms;
+    float* terms = loss_terms(p);
     // TVLoss on the un-normalised image (style_transfer.py:376): WRITES grad_out; conv1_1's data gradient adds to it
     if (hbm_profiled(p, HBM_TV, 2.0 * 3 * 4.0 * p->H * p->W, s, [&] {
             return launch_tv(image, p->H, p->W, p->tv_weight, grad_out, p->red_partials, terms + nc + ns, s, p->tickets + 0);
@@ -112,29 +107,20 @@ int general_loss_and_grad(st_plan* p, const float* image, float* grad_out, float
     std::sort(order, order + ns, [&](int a, int b) { return p->style_op[a] > p->style_op[b]; });
     bool styled[kNumOps] = {};
     for (int k = 0; k < ns; ++k) {
-        const int j = order[k], op = p->style_op[j];
-        HeadSite at;
-        at.h = &configured_head(p, j);
-        at.tap = &node_at(p, op);
-        at.weight = p->taps_default ? p->style_weight[j] : p->tap_style_weight[j];
-        at.loss = terms + nc + j;
-        at.grad = p->tap_seed[op];
-        if (style_head(p, at, s)) return 1;
-        styled[op] = true;
+        if (style_head(p, general_head_site(p, order[k]), s)) return 1;
+        styled[p->style_op[order[k]]] = true;
     }
     // ContentLossMSE per content layer (style_transfer.py:425-429), behind the style head of the same layer where there is one
     for (int i = 0; i < nc; ++i) {
         const int op = p->content_op[i];
         const Node& ct = node_at(p, op);
-        const float* target = p->taps_default ? p->content_target : p->tap_content_target[op];
-        const float weight = p->taps_default ? p->content_weight : p->tap_content_weight[i];
         if (hbm_profiled(p, HBM_CONTENT, 3.0 * 4.0 * ct.count(), s, [&] {
-                return launch_content_mse(ct.y, target, (long long)ct.count(), weight, p->tap_seed[op],
+                return launch_content_mse(ct.y, p->content_target[op], (long long)ct.count(), p->content_weight[i], p->tap_seed[op],
                                           p->red_partials + 4 * kStreamBlocks, terms + i, s, p->tickets + 64, styled[op] ? 1 : 0);
             }))
             return 1;
     }
-    if (p->taps_default) {
+    if (p->reference_taps) {
         if (!p->defer_sum && launch_sum_losses(p->losses, s, losses_out)) return 1;
     } else if (launch_sum_terms(terms, nc, ns, p->losses, s, p->defer_sum ? nullptr : losses_out)) {
         // (a step's tail sums the 8-float array once more - the same additions - and fills losses_out)
@@ -174,53 +160,48 @@ int st_plan_set_taps(st_plan* p, int n_content, const int* content_layers, int n
                            pass ? "style" : "content");
         }
     }
-    bool dflt = n_content == 1 && cop[0] == kDefaultContentOp && n_style == 5;
-    for (int i = 0; dflt && i < 5; ++i) dflt = sop[i] == kDefaultStyleOp[i];
-    if (!dflt) {
-        // everything the configuration needs, now: a failed allocation leaves the plan as it was
-        for (int i = 0; i < n_content; ++i)
-            if (!p->tap_content_target[cop[i]] && plan_alloc(p, &p->tap_content_target[cop[i]], node_at(p, cop[i]).count())) return 1;
-        for (int j = 0; j < n_style; ++j)
-            if (ensure_style_alloc(p, tap_head_at(p, sop[j]))) return 1;
-    }
-    p->taps_default = dflt;
+    bool ref = n_content == 1 && content_layers[0] == kContentFeat && n_style == 5;
+    for (int j = 0; ref && j < 5; ++j) ref = style_layers[j] == kStyleFeat[j];
+    // everything the configuration needs, now (the reference's lists too, whose heads a plan that was never configured
+    // allocates when their targets are set): a failed allocation leaves the plan as it was
+    for (int i = 0; i < n_content; ++i)
+        if (!p->content_target[cop[i]] && plan_alloc(p, &p->content_target[cop[i]], node_at(p, cop[i]).count())) return 1;
+    for (int j = 0; j < n_style; ++j)
+        if (ensure_style_alloc(p, p->head[sop[j]])) return 1;
+    // the weights: the reference's lists named again keep theirs; every other change of lists starts from the new lists'
+    // defaults - the reference's content_weight split over the layers (:366) and equal style weights, or, for the reference's
+    // own lists, its own style weights
+    const bool keep_weights = ref && p->reference_taps;
+    p->reference_taps = ref;
     p->n_content = n_content;
     p->n_style = n_style;
     for (int i = 0; i < 16; ++i) {
         p->content_op[i] = i < n_content ? cop[i] : 0;
         p->style_op[i] = i < n_style ? sop[i] : 0;
-        // (the reference's content_weight split over the layers, :366; its style weights belong to its own five layers)
-        p->tap_content_weight[i] = i < n_content ? 0.015f / (float)n_content : 0.f;
-        p->tap_style_weight[i] = i < n_style ? 1.f / (float)n_style : 0.f;
+        if (keep_weights) continue;
+        p->content_weight[i] = i < n_content ? 0.015f / (float)n_content : 0.f;
+        p->style_weight[i] = i >= n_style ? 0.f : ref ? kStyleWeight[i] : 1.f / (float)n_style;
     }
-    for (StyleHead& h : p->tap_head)                 // (unlisted heads, a former list's included: parked - see tap_head_at)
-        h.s_amax = reinterpret_cast<unsigned int*>(p->amax_word) + (size_t)(48 + 15) * kAmaxWordUints;
-    if (!dflt)
-        for (int j = 0; j < n_style; ++j)
-            p->tap_head[sop[j]].s_amax = reinterpret_cast<unsigned int*>(p->amax_word) + (size_t)(48 + j) * kAmaxWordUints;
-    // every target set before is gone
-    p->content_set = false;
-    for (StyleHead& h : p->style) h.target_set = false;
-    for (int i = 0; i < kNumOps; ++i) {
-        p->tap_head[i].target_set = false;
-        p->tap_content_set[i] = false;
+    // a head or target buffer serves whichever lists name its position: every target set before is gone, every bound word
+    // is dealt again, and nothing built on the former lists survives
+    for (int op = 0; op < kNumOps; ++op) {
+        p->head[op].target_set = false;
+        p->content_set[op] = false;
     }
+    assign_head_bounds(p);
     invalidate_graph(p);
+    p->phases.clear();
     return 0;
 }
 
 int st_plan_set_tap_weights(st_plan* p, const float* content_weights, const float* style_weights, float tv_weight) {
     ST_REQUIRE(p, "st_plan_set_tap_weights: null plan");
     ST_REQUIRE((p->n_content == 0 || content_weights) && (p->n_style == 0 || style_weights), "st_plan_set_tap_weights: null list");
-    for (int i = 0; i < p->n_content; ++i) p->tap_content_weight[i] = content_weights[i];
-    for (int j = 0; j < p->n_style; ++j) p->tap_style_weight[j] = style_weights[j];
-    if (p->taps_default) {
-        p->content_weight = content_weights[0];
-        for (int j = 0; j < 5; ++j) p->style_weight[j] = style_weights[j];
-    }
+    for (int i = 0; i < p->n_content; ++i) p->content_weight[i] = content_weights[i];
+    for (int j = 0; j < p->n_style; ++j) p->style_weight[j] = style_weights[j];
     p->tv_weight = tv_weight;
     invalidate_graph(p);       // the weights are baked into kernel arguments
-    p->phases.clear();
+    p->phases.clear();         // (a strip's phase sequence is rebuilt by its next closure)
     return 0;
 }
 
@@ -229,16 +210,14 @@ int st_plan_set_content_target_at(st_plan* p, int index, const float* feat, void
     ST_REQUIRE(index >= 0 && index < p->n_content, "st_plan_set_content_target_at: index %d out of range (%d content layers)", index,
                p->n_content);
     const int op = p->content_op[index];
-    float* dst = p->taps_default ? p->content_target : p->tap_content_target[op];
-    ST_HIP(hipMemcpyAsync(dst, feat, node_at(p, op).count() * sizeof(float), hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
-    if (p->taps_default) p->content_set = true;     // (buffer contents only: a captured graph stays valid)
-    else p->tap_content_set[op] = true;
+    ST_HIP(hipMemcpyAsync(p->content_target[op], feat, node_at(p, op).count() * sizeof(float), hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
+    p->content_set[op] = true;     // (buffer contents only: a captured graph stays valid)
     return 0;
 }
 
 int st_plan_term_losses(st_plan* p, float** terms, int* count) {
     ST_REQUIRE(p && terms && count, "st_plan_term_losses: null argument");
-    if (p->taps_default) {
+    if (p->reference_taps) {
         *terms = p->losses;
         *count = 7;
         return 0;

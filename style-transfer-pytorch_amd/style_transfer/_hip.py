@@ -276,8 +276,9 @@ class Plan:
 
     def set_taps(self, content_layers, style_layers):
         """The layers of the closure's content / style terms (st_plan_set_taps): any of ``TAPS``, 0 to 16 per list, each once
-        per list, at least one in all.  Drops every target set before and resets a non-default configuration's weights
-        (``set_loss_weights`` afterwards).  Anything but the default lists runs the general closure."""
+        per list, at least one in all.  Drops every target set before and resets the weights to the lists'
+        defaults (``set_loss_weights`` afterwards; only the default lists named again on a plan that has them keep
+        theirs).  Anything but the default lists runs the general closure."""
         content_layers, style_layers = [int(v) for v in content_layers], [int(v) for v in style_layers]
         ca = (ctypes.c_int * max(len(content_layers), 1))(*content_layers)
         sa = (ctypes.c_int * max(len(style_layers), 1))(*style_layers)
@@ -383,18 +384,17 @@ class Plan:
 
     def set_loss_weights(self, content_weight, style_layer_weights, tv_weight):
         """``content_weight``: one float for every content layer, or one per layer; ``style_layer_weights``: one per style
-        layer (st_plan_set_tap_weights; a plan with the default layers: st_plan_set_loss_weights)."""
+        layer (st_plan_set_tap_weights)."""
         nc, ns = len(self.content_layers), len(self.style_layers)
         try:                                        # any sequence (list, tuple, numpy array, tensor), or one number
             cws = [float(w) for w in content_weight]
         except TypeError:
             cws = [float(content_weight)] * nc
         sws = [float(w) for w in style_layer_weights]
+        # One entry serves every configuration.  The lists are still compared, for one reason: with the default layers fewer
+        # than 5 style weights have always meant "the rest are zero", while for any other lists a count mismatch is an error.
         if (tuple(self.content_layers), tuple(self.style_layers)) == (DEFAULT_CONTENT_LAYERS, DEFAULT_STYLE_LAYERS):
-            # (as before this entry took lists: fewer than 5 style weights leave the rest at zero)
-            sa = (ctypes.c_float * 5)(*sws)
-            _check(self.lib.st_plan_set_loss_weights(self.handle, cws[0], sa, float(tv_weight)))
-            return
+            sws += [0.0] * (ns - len(sws))
         if len(cws) != nc or len(sws) != ns:
             raise ValueError(f'{len(cws)} content and {len(sws)} style weights for {nc} content and {ns} style layers')
         ca, sa = (ctypes.c_float * max(nc, 1))(*cws), (ctypes.c_float * max(ns, 1))(*sws)

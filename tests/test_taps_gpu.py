@@ -112,13 +112,17 @@ def _configured_plan(size, pooling, precision, content_layers, style_layers, con
     plan = hip.Plan(net, *size)
     if configure:
         plan.set_taps(content_layers, style_layers)
+    _set_targets(plan, size, pooling, content_layers, style_layers)
+    plan.set_loss_weights(*_layer_weights(content_layers, style_layers), TV_WEIGHT)
+    return net, plan
+
+
+def _set_targets(plan, size, pooling, content_layers, style_layers):
     ctargets, moments = _targets(size, pooling, content_layers, style_layers)
     for i, layer in enumerate(content_layers):
         plan.set_content_target(ctargets[layer].to(DEV), i)
     for i, layer in enumerate(style_layers):
         plan.set_style_target(i, moments[layer][0].to(DEV), moments[layer][1].to(DEV))
-    plan.set_loss_weights(*_layer_weights(content_layers, style_layers), TV_WEIGHT)
-    return net, plan
 
 
 def _judge(tag, plan, img, image, pooling, content_layers, style_layers, closure):
@@ -307,7 +311,123 @@ def test_errors():
         plan.loss_and_grad(img)
 
 
-# ---- 6. stylize() -----------------------------------------------------------------------------------------------------------
+# ---- 6. one store of heads, targets and weights: what sharing a position between configurations must not change ----------------
+SIZE = (40, 48)
+SHARED = ([22], [1, 6])         # relu1_1 and relu2_1: heads of the default lists too, here with bound words 48 and 49
+
+
+def _leg(plan, img, steps):
+    """(losses, gradient, terms[, the three steps' losses, the state after them]) of `plan` as it is configured now."""
+    losses, grad = plan.loss_and_grad(img)
+    out = [losses.clone(), grad.clone(), plan.term_losses().clone()]
+    if steps:
+        state = _state(img)
+        out += [plan.step(*state, k, 0.02).clone() for k in (1, 2, 3)]
+        out += list(state)
+    torch.cuda.synchronize()
+    assert all(torch.isfinite(t).all() for t in out)
+    return out
+
+
+def _same(a, b):
+    return len(a) == len(b) and all(torch.equal(x, y) for x, y in zip(a, b))
+
+
+def test_a_head_that_two_configurations_share():
+    """Default lists, then SHARED, then the default lists again, on ONE plan: the outer legs are equal bit for bit and the
+    middle one is a fresh plan's - no target, bound word or fused Gram of a former configuration is left behind."""
+    img = _inputs(SIZE, 'max')['image'].to(DEV)
+    _, plan = _configured_plan(SIZE, 'max', 'fp16x3', *DEFAULT, configure=False)
+    first = _leg(plan, img, steps=True)
+    for lists, name in ((SHARED, 'middle'), (DEFAULT, 'last')):
+        plan.set_taps(*lists)
+        _set_targets(plan, SIZE, 'max', *lists)
+        plan.set_loss_weights(*_layer_weights(*lists), TV_WEIGHT)
+        if name == 'middle':
+            middle = _leg(plan, img, steps=False)
+        else:
+            last = _leg(plan, img, steps=True)
+    _, fresh = _configured_plan(SIZE, 'max', 'fp16x3', *SHARED)
+    want = _leg(fresh, img, steps=False)
+    assert len(middle[2]) == 4 and _same(middle, want)
+    assert len(first) == 10 and _same(first, last)
+    assert not torch.equal(first[6], img)
+
+
+def test_set_taps_drops_the_targets_of_shared_positions():
+    from style_transfer import _hip as hip
+    img = _inputs(SIZE, 'max')['image'].to(DEV)
+    _, plan = _configured_plan(SIZE, 'max', 'fp16x3', *DEFAULT, configure=False)
+    _leg(plan, img, steps=True)
+    plan.set_taps(*SHARED)          # relu4_2, relu1_1 and relu2_1 all had a target a moment ago
+    with pytest.raises(hip.HipLibraryError, match=r'content target 0 \(features\[22\]\)'):
+        plan.loss_and_grad(img)
+    ctargets, moments = _targets(SIZE, 'max', *SHARED)
+    plan.set_content_target(ctargets[22].to(DEV), 0)
+    with pytest.raises(hip.HipLibraryError, match=r'style target 0 \(features\[1\]\)'):
+        plan.loss_and_grad(img)
+    plan.set_style_target(0, moments[1][0].to(DEV), moments[1][1].to(DEV))
+    with pytest.raises(hip.HipLibraryError, match=r'style target 1 \(features\[6\]\)'):
+        plan.loss_and_grad(img)
+
+
+def test_moments_do_not_depend_on_the_configuration():
+    from style_transfer import _hip as hip
+    img = _inputs(SIZE, 'max')['image'].to(DEV)
+    net = hip.Net(_weights(), 'max', DEV, 'fp16x3')
+    plans = {name: hip.Plan(net, *SIZE) for name in ('plain', 'default', 'other')}
+    plans['default'].set_taps(*DEFAULT)
+    plans['other'].set_taps([20], [1, 29])
+    layers = (1, 6, 11, 20, 29, 4, 22)
+
+    def all_moments():
+        got = {}
+        for name, plan in plans.items():
+            plan.forward(img, 29)
+            got[name] = {layer: [t.clone() for t in plan.moments(layer)] for layer in layers}
+        torch.cuda.synchronize()
+        return got
+
+    unfused = all_moments()
+    for layer in layers:
+        assert all(torch.isfinite(t).all() for t in unfused['plain'][layer]), layer
+        assert _same(unfused['plain'][layer], unfused['default'][layer]), layer
+        assert _same(unfused['plain'][layer], unfused['other'][layer]), layer
+    # relu1_1's Gram out of conv1_1's launch: the reference's lists only, and then on both plans that have them
+    with hip.options(ST_CONV1_GRAM_IN_FORWARD=1):
+        fused = all_moments()
+    for layer in layers:
+        assert _same(fused['plain'][layer], fused['default'][layer]), layer
+        if layer != 1:
+            assert _same(fused['plain'][layer], fused['other'][layer]), layer
+    assert _same(fused['other'][1], unfused['other'][1])
+
+
+def test_weights_across_set_taps():
+    """The default lists named again keep the plan's weights; every other change of lists resets them to the new lists'
+    defaults (the tv weight is not a per-layer weight: set_taps leaves it alone)."""
+    img = _inputs(SIZE, 'max')['image'].to(DEV)
+    reference = _layer_weights(*DEFAULT)[1]
+    _, plan = _configured_plan(SIZE, 'max', 'fp16x3', *DEFAULT, configure=False)
+    plan.set_loss_weights(0.03, [2 * w for w in reference], 4.0)
+    before = _leg(plan, img, steps=False)
+    plan.set_taps(*DEFAULT)
+    _set_targets(plan, SIZE, 'max', *DEFAULT)
+    assert _same(_leg(plan, img, steps=False), before)
+    from style_transfer import _hip as hip
+    fresh = hip.Plan(plan.net, *SIZE)            # the weights a plan is created with: 0.015, 4^-k / 341, tv 2
+    _set_targets(fresh, SIZE, 'max', *DEFAULT)
+    want = _leg(fresh, img, steps=False)
+    assert not torch.equal(want[0], before[0])
+    _, plan = _configured_plan(SIZE, 'max', 'fp16x3', *DEFAULT, configure=False)
+    plan.set_loss_weights(0.03, [2 * w for w in reference], TV_WEIGHT)       # (TV_WEIGHT is a fresh plan's 2.0, so `want` holds)
+    plan.set_taps([20, 22], [3])
+    plan.set_taps(*DEFAULT)
+    _set_targets(plan, SIZE, 'max', *DEFAULT)
+    assert _same(_leg(plan, img, steps=False), want)
+
+
+# ---- 7. stylize() -----------------------------------------------------------------------------------------------------------
 def _pil(seed, w, h):
     """A smooth synthetic image with every pixel well inside (0, 1): no clamp engages during the few iterations below."""
     from PIL import Image
