@@ -163,6 +163,25 @@ int st_plan_set_taps(st_plan* plan, int n_content, const int* content_layers, in
  * style_weights[n_style], tv.  The general form of st_plan_set_loss_weights, which serves the default configuration only. */
 int st_plan_set_tap_weights(st_plan* plan, const float* content_weights, const float* style_weights, float tv_weight);
 
+/*
+ * WHAT the terms are: one loss kind per list, for every layer of that list.
+ *   content_kind  0 (default)  ContentLossMSE (style_transfer.py:119-126): mean((F - T)^2)
+ *                 1            ContentLoss (:109-116): ScaledMSELoss (:93-106) of the features,
+ *                              sum d^2 / (sum |d| + 1e-8) with d = F - T
+ *   style_kind    0 (default)  StyleLossW2 (:149-181)
+ *                 1            StyleLoss (:129-142), the Gatys loss: the same scaled MSE with d = F F^T / N - G_t, N the tap's
+ *                              GLOBAL position count
+ * The default kinds leave every configuration on the closure it has.  Any other kind sends every configuration - the
+ * default lists too - through the general closure (csrc/st_taps.hip), by the same entries: st_plan_loss_and_grad,
+ * st_plan_step, st_plan_lbfgs_step, st_plan_range_guard; such a plan always launches eagerly.  A Gram head runs no
+ * Newton-Schulz chain and allocates no workspace for one.  The terms keep SumLoss order and the 8-float array its layout
+ * (st_plan_term_losses).  The call drops every target set before (a style target is kept in the form its kind reads),
+ * deals the heads' bound words again and invalidates a captured graph; the lists and all weights stay, and the kinds
+ * survive a later st_plan_set_taps.  Fails for an unknown code, and on strip plans for any kind but the defaults.  Synchronous.
+ */
+int st_plan_set_loss_kinds(st_plan* plan, int content_kind, int style_kind);
+int st_plan_loss_kinds(const st_plan* plan, int* content_kind, int* style_kind);
+
 /* ContentLossMSE target (style_transfer.py:425-429): copies feat [512][H/8][W/8] into the plan (a configured plan: the
  * target of content layer 0, shaped like that layer). */
 int st_plan_set_content_target(st_plan* plan, const float* feat, void* stream);
@@ -173,6 +192,8 @@ int st_plan_set_content_target_at(st_plan* plan, int index, const float* feat, v
  * StyleLossW2.__init__ (style_transfer.py:152-160) for style layer `index` of the configured list (default: 0..4 =
  * relu1_1..relu5_1): cov = srm - mean mean^T + 1e-4 I, cov_sqrt = sqrtm_ns(cov, 12) (sqrtm.py:9-25).
  * mean[C], srm[C*C] are the (already blended, :442-450) targets.
+ * With style kind 1 (st_plan_set_loss_kinds) the target is StyleLoss.get_target's (:136-139): srm is stored as the Gram
+ * target G_t, mean is not read and no square root runs.
  */
 int st_plan_set_style_target(st_plan* plan, int index, const float* mean, const float* srm, void* stream);
 /* Scale factors (style_transfer.py:320-322,366,376,429,453): content, 5 style layers, tv.  Default configuration only. */

@@ -434,7 +434,7 @@ int st_plan_moments(st_plan* p, int layer, float* mean_out, float* srm_out, void
     at.h = &p->head[op];
     at.tap = &node_at(p, op);
     if (j >= 0 && p->reference_taps) at = head_site(p, j);
-    if (ensure_style_alloc(p, *at.h)) return 1;
+    if (ensure_moment_alloc(p, *at.h)) return 1;
     return moments_of_tap(p, at, mean_out, srm_out, static_cast<hipStream_t>(stream));
 }
 
@@ -449,6 +449,11 @@ int st_plan_set_style_target(st_plan* p, int index, const float* mean, const flo
     hipStream_t s = static_cast<hipStream_t>(stream);
     StyleHead& h = p->head[p->style_op[index]];
     if (ensure_style_alloc(p, h)) return 1;
+    if (p->style_kind == 1) {           // StyleLoss.get_target (:136-139): the second raw moment IS the Gram target; no root
+        ST_HIP(hipMemcpyAsync(h.gram_t, srm, (size_t)h.n * h.n * sizeof(float), hipMemcpyDeviceToDevice, s));
+        h.target_set = true;
+        return 0;
+    }
     ST_HIP(hipMemcpyAsync(h.mean_t, mean, h.n * sizeof(float), hipMemcpyDeviceToDevice, s));
     if (launch_cov_from_moments(mean, srm, h.cov_t, h.n, kCovEps, s)) return 1;
     if (ns_sqrt_forward(h.cov_t, h.root_t, h.n, h.ns, s)) return 1;

@@ -347,21 +347,12 @@ int run_forward(st_plan* p, const float* image, int last_layer, hipStream_t s, b
     return 0;
 }
 
-int ensure_style_alloc(st_plan* p, StyleHead& h) {
+// the moments of a tap and the step back onto it: what a head of either kind needs, and all that st_plan_moments does
+int ensure_moment_alloc(st_plan* p, StyleHead& h) {
     if (h.allocated) return 0;
     const size_t nn = (size_t)h.n * h.n;
-    float** mats[] = {&h.cov_t, &h.root_t, &h.srm, &h.cov, &h.tmat, &h.mmat, &h.root,
-                      &h.gm,    &h.dt,     &h.dcov, &h.ssym};
-    for (float** m : mats)
-        if (plan_alloc(p, m, nn)) return 1;
-    if (plan_alloc(p, &h.mean_t, h.n) || plan_alloc(p, &h.mean, h.n) || plan_alloc(p, &h.bvec, h.n) ||
-        plan_alloc(p, &h.gdiag, 64))
+    if (plan_alloc(p, &h.srm, nn) || plan_alloc(p, &h.ssym, nn) || plan_alloc(p, &h.mean, h.n) || plan_alloc(p, &h.bvec, h.n))
         return 1;
-    float* nsbase = nullptr;
-    if (plan_alloc(p, &nsbase, ns_workspace_floats(h.n))) return 1;
-    ns_workspace_carve(h.ns, nsbase, h.n);
-    if (ns_workspace_reset(h.ns, nullptr)) return 1;
-    ST_HIP(hipStreamSynchronize(nullptr));        // (the heads' streams are non-blocking: nothing orders them behind the null stream)
     long long splits = (16ll << 20) / (long long)nn;
     if (splits > 1024) splits = 1024;
     if (splits < 8) splits = 8;
@@ -379,6 +370,26 @@ int ensure_style_alloc(st_plan* p, StyleHead& h) {
         if (plan_alloc(p, &h.conv_scratch, need)) return 1;
     }
     h.allocated = true;
+    return 0;
+}
+
+// ... and the rest by the plan's style kind: a Gram head (st_plan::style_kind == 1) holds its target and nothing else - no
+// covariance, no root, no Newton-Schulz workspace; a W2 head all of those
+int ensure_style_alloc(st_plan* p, StyleHead& h) {
+    if (ensure_moment_alloc(p, h)) return 1;
+    const size_t nn = (size_t)h.n * h.n;
+    if (p->style_kind == 1) return h.gram_t ? 0 : plan_alloc(p, &h.gram_t, nn);
+    if (h.w2_allocated) return 0;
+    float** mats[] = {&h.cov_t, &h.root_t, &h.cov, &h.tmat, &h.mmat, &h.root, &h.gm, &h.dt, &h.dcov};
+    for (float** m : mats)
+        if (!*m && plan_alloc(p, m, nn)) return 1;
+    if ((!h.mean_t && plan_alloc(p, &h.mean_t, h.n)) || (!h.gdiag && plan_alloc(p, &h.gdiag, 64))) return 1;
+    float* nsbase = nullptr;
+    if (plan_alloc(p, &nsbase, ns_workspace_floats(h.n))) return 1;
+    ns_workspace_carve(h.ns, nsbase, h.n);
+    if (ns_workspace_reset(h.ns, nullptr)) return 1;
+    ST_HIP(hipStreamSynchronize(nullptr));        // (the heads' streams are non-blocking: nothing orders them behind the null stream)
+    h.w2_allocated = true;
     return 0;
 }
 

@@ -599,6 +599,18 @@ int launch_scaled_identity_div(const float* diag_value, const float* scalar, flo
 constexpr int kStreamBlocks = 2048;
 int launch_content_mse(const float* feat, const float* target, long long count, float weight, float* grad,
                        float* partials, float* loss_out, hipStream_t s, unsigned int* ticket = nullptr, int accumulate = 0);
+// ScaledMSELoss (ContentLoss on features, StyleLoss on Gram matrices) in two launches on `count` floats, see st_pointwise.hip:
+// the sums - totals[0] = sum d^2, totals[1] = sum |d| + eps, loss_out[0] = weight totals[0] / totals[1]; partials: 2 floats
+// per block, at most 2 kStreamBlocks; ticket: a zeroed device word - then the content seed from them,
+// grad = weight (2 d - L sgn d) / S1 (accumulate != 0: added to what grad holds)
+constexpr float kScaledMseEps = 1e-8f;            // ScaledMSELoss eps (style_transfer.py:97)
+int launch_scaled_mse_sums(const float* x, const float* target, long long count, float weight, float* partials, float* totals,
+                           float* loss_out, hipStream_t s, unsigned int* ticket);
+int launch_scaled_mse_grad(const float* feat, const float* target, long long count, float weight, const float* totals,
+                           float* grad, hipStream_t s, int accumulate = 0);
+// ... or, for a Gram head, (Ssym, b) of its 1x1 step: ssym = (weight / npix) (D + D^T), D = dL/dG from the totals; bvec = 0
+int launch_gram_grad_finish(const float* gram, const float* gram_t, const float* totals, int n, float weight, long long npix,
+                            float* ssym, float* bvec, hipStream_t s, unsigned int* ssym_amax = nullptr);
 // st_plan_backward's seeding: g = ext (accumulate == 0) or g += ext over `count` elements; relu_out (optional): the result
 // is masked by (relu_out > 0); bound (optional): max |g| folded into that device bound for an fp16x3 consumer
 int launch_seed_grad(const float* ext, const float* relu_out, float* g, long long count, int accumulate, unsigned int* bound,

@@ -59,9 +59,11 @@ struct StyleHead {
     float *mean = nullptr, *srm = nullptr, *cov = nullptr, *tmat = nullptr, *mmat = nullptr, *root = nullptr,
           *gm = nullptr, *dt = nullptr, *dcov = nullptr, *ssym = nullptr, *bvec = nullptr, *gdiag = nullptr;
     float* conv_scratch = nullptr;     // split-K workspace of the head's 1x1 gradient conv (small taps only)
+    float* gram_t = nullptr;           // Gram kind (st_plan::style_kind == 1): the target Gram matrix [n][n]
     NSWorkspace ns{};
     GramWorkspace gram{};
-    bool allocated = false;
+    bool allocated = false;            // what every kind needs: the moments, their workspace, (Ssym, b), the 1x1 step's scratch
+    bool w2_allocated = false;         // ... and what only the W2 kind does: the target's root, the chains' matrices and workspace
 };
 
 // Where a W2 style head sits: head_site(p, j) for the j-th LISTED style layer in the default and strip closures, the same
@@ -130,10 +132,10 @@ struct st_plan {
     // per LISTED entry, and the W2 head, content target and seed buffer of a position, indexed by kProgram position.
     // st_plan_set_taps replaces the lists; a head or target buffer serves whichever configuration names its position.
     // reference_taps: the lists are the reference's own ([22], [1, 6, 11, 20, 29], style_transfer.py:315-322).  It selects
-    // WHICH closure runs - loss_and_grad (st_closure.hip) for them, general_loss_and_grad (st_taps.hip) for every other
-    // configuration - and what follows from that: the terms array and its sum kernel (loss_terms, st_plan_term_losses),
-    // st_plan_set_loss_weights' refusal, and conv1_1's fused Gram with the one consumer of its partials outside the closure
-    // (run_forward, st_plan_moments).  Never which state is read.
+    // WHICH closure runs - loss_and_grad (st_closure.hip) for them under the default loss kinds, general_loss_and_grad
+    // (st_taps.hip) for every other configuration (general_taps) - and what follows from the LISTS: the terms array and its
+    // sum kernel (loss_terms, st_plan_term_losses), st_plan_set_loss_weights' refusal, and conv1_1's fused Gram with the one
+    // consumer of its partials outside the closure (run_forward, st_plan_moments).  Never which state is read.
     bool reference_taps = true;
     int n_content = 1, n_style = 5;
     int content_op[16] = {12};
@@ -141,6 +143,12 @@ struct st_plan {
     float content_weight[16] = {0.015f};             // per LISTED entry
     float style_weight[16] = {256.f / 341, 64.f / 341, 16.f / 341, 4.f / 341, 1.f / 341};
     float tv_weight = 2.0f;
+    // WHAT the terms are, one kind per list (st_plan_set_loss_kinds): content 0 = ContentLossMSE, 1 = ContentLoss (the features
+    // under ScaledMSELoss); style 0 = StyleLossW2, 1 = StyleLoss (the Gram matrix under ScaledMSELoss).  Any non-default kind
+    // runs the general closure (general_taps), on the reference's lists too.
+    int content_kind = 0, style_kind = 0;
+    float* kind_scratch = nullptr;                   // non-default kinds: [2 kStreamBlocks] per-block (sum d^2, sum |d|) of the
+                                                     // term in flight, then [2] per term: sum d^2, sum |d| + eps (kind_totals)
     st::StyleHead head[st::kNumOps];                 // n / npix / npix_local of all 17 filled at create, buffers on first use;
                                                      // bound word: the j-th listed head owns word 48 + j, an unlisted one is parked on 63
     float* content_target[st::kNumOps] = {};         // allocated when a list first names the position ([12] at create)
@@ -296,7 +304,8 @@ int hbm_profiled(st_plan* p, int cat, double bytes, hipStream_t s, F&& launch) {
 
 void invalidate_graph(st_plan* p);
 int ensure_streams(st_plan* p, hipStream_t caller = nullptr);
-int ensure_style_alloc(st_plan* p, StyleHead& h);
+int ensure_moment_alloc(st_plan* p, StyleHead& h);      // what st_plan_moments needs (StyleHead::allocated)
+int ensure_style_alloc(st_plan* p, StyleHead& h);       // ... and what a head of the plan's style kind needs
 int ensure_grad_alloc(st_plan* p);
 HeadSite head_site(st_plan* p, int j);
 int moments_of_tap(st_plan* p, const HeadSite& at, float* mean_out, float* srm_out, hipStream_t s, float* cov_out = nullptr);

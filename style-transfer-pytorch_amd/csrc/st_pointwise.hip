@@ -192,6 +192,131 @@ __global__ __launch_bounds__(64) void content_mse_final_kernel(const float* __re
     if (threadIdx.x == 0) loss_out[0] = (s / count) * weight;
 }
 
+// ------------------------------------------------------------------------------------------------
+// ScaledMSELoss (style_transfer.py:93-106) under Scale(weight): the reference's ContentLoss (:109-116, x = the features, t =
+// their target) and StyleLoss (:129-142, x = the Gram matrix F F^T / N, t = the target Gram matrix).
+//   d = x - t,  S2 = sum d^2,  S1 = sum |d| + eps,  L = S2 / S1,  term = weight L
+// Gradient, derived once: dL/dd = (dS2/dd) / S1 - (S2 / S1^2) dS1/dd = 2 d / S1 - (L / S1) sgn d = (2 d - L sgn d) / S1, with
+// sgn 0 = 0 as torch's abs backward has it.  Where x and t are both zero (a ReLU's zeros) d is exactly zero and so is the
+// gradient; when EVERY d is zero S2 = 0, S1 = eps, L = 0 and every gradient is (0 - 0) / eps = 0: nothing becomes NaN.
+//   content:  the tap's seed is  weight (2 d - L sgn d) / S1
+//   Gram:     with D = dL/dG,  G = F F^T / N  gives  dF = (weight / N) (D + D^T) F.  D + D^T is formed explicitly
+//             (gram_grad_finish_kernel, as style_grad_finish_kernel forms a + b): the computed Gram matrix need not be
+//             symmetric bit for bit.  The product with F is the W2 heads' 1x1 step with a zero bias (style_head_gradient).
+// The totals need every element before any gradient can be formed, so a term is two launches: the sums - per-block partials,
+// then the last block by ticket adds them in block order, as content_mse_kernel does - and the gradient.  No floating-point
+// atomics: a given grid always adds in the same order.
+__device__ __forceinline__ float scaled_mse_slope(float d, float level, float s1) {
+#pragma clang fp contract(off)
+    const float sg = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
+    return (2.f * d - level * sg) / s1;
+}
+// totals[0] = S2, totals[1] = S1 (eps included); loss_out[0] = weight S2 / S1.  partials: 2 floats per block.
+__global__ __launch_bounds__(256) void scaled_mse_sums_kernel(const float* __restrict__ x, const float* __restrict__ target,
+                                                              long long count, float weight, float eps,
+                                                              float* __restrict__ partials, LastBlock lb,
+                                                              float* __restrict__ totals, float* __restrict__ loss_out) {
+#pragma clang fp contract(off)
+    __shared__ float scratch[4];
+    __shared__ bool is_last;
+    float s2 = 0.f, s1 = 0.f;
+    if ((count & 3) == 0) {           // 16-byte accesses: two streams of 4 B per element
+        const long long n4 = count >> 2;
+        const f32x4* x4 = reinterpret_cast<const f32x4*>(x);
+        const f32x4* t4 = reinterpret_cast<const f32x4*>(target);
+        for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
+            const f32x4 f = x4[i], t = t4[i];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float d = f[k] - t[k];
+                s2 += d * d;
+                s1 += fabsf(d);
+            }
+        }
+    } else {
+        for (long long i = blockIdx.x * 256ll + threadIdx.x; i < count; i += (long long)gridDim.x * 256) {
+            const float d = x[i] - target[i];
+            s2 += d * d;
+            s1 += fabsf(d);
+        }
+    }
+    s2 = block_sum_256(s2, scratch);
+    s1 = block_sum_256(s1, scratch);
+    if (threadIdx.x == 0) {
+        partials[2 * blockIdx.x] = s2;
+        partials[2 * blockIdx.x + 1] = s1;
+    }
+    if (!last_block_arrives(lb, &is_last)) return;
+    float t2 = 0.f, t1 = 0.f;
+    for (int i = threadIdx.x; i < (int)gridDim.x; i += 256) {
+        t2 += partials[2 * i];
+        t1 += partials[2 * i + 1];
+    }
+    t2 = block_sum_256(t2, scratch);
+    t1 = block_sum_256(t1, scratch);
+    if (threadIdx.x == 0) {
+        const float sum_abs = t1 + eps;
+        totals[0] = t2;
+        totals[1] = sum_abs;
+        loss_out[0] = (t2 / sum_abs) * weight;
+    }
+}
+// the content seed: grad = (or, ACC: +=) weight (2 d - L sgn d) / S1.  ACC as content_mse_kernel's.
+template <bool ACC>
+__global__ __launch_bounds__(256) void scaled_mse_grad_kernel(const float* __restrict__ feat, const float* __restrict__ target,
+                                                              long long count, float weight,
+                                                              const float* __restrict__ totals, float* __restrict__ grad) {
+#pragma clang fp contract(off)
+    const float s1 = totals[1];
+    const float level = totals[0] / s1;
+    if ((count & 3) == 0) {           // 16-byte accesses: three (ACC: four) streams of 4 B per element, HBM-bound
+        const long long n4 = count >> 2;
+        const f32x4* f4 = reinterpret_cast<const f32x4*>(feat);
+        const f32x4* t4 = reinterpret_cast<const f32x4*>(target);
+        f32x4* g4 = reinterpret_cast<f32x4*>(grad);
+        for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
+            const f32x4 f = f4[i], t = t4[i];
+            f32x4 g;
+            if (ACC) g = g4[i];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float v = scaled_mse_slope(f[k] - t[k], level, s1) * weight;
+                g[k] = ACC ? g[k] + v : v;
+            }
+            g4[i] = g;
+        }
+    } else {
+        for (long long i = blockIdx.x * 256ll + threadIdx.x; i < count; i += (long long)gridDim.x * 256) {
+            const float v = scaled_mse_slope(feat[i] - target[i], level, s1) * weight;
+            grad[i] = ACC ? grad[i] + v : v;
+        }
+    }
+}
+// The Gram head's (Ssym, b) for the 1x1 step, one workgroup per row c of the n x n matrix (n = 64 ... 512):
+//   ssym[c][d] = (weight / npix) (D[c][d] + D[d][c]),  D = (2 (G - G_t) - L sgn(G - G_t)) / S1;   bvec[c] = 0
+__global__ __launch_bounds__(256) void gram_grad_finish_kernel(const float* __restrict__ gram, const float* __restrict__ gram_t,
+                                                               const float* __restrict__ totals, int n, float weight,
+                                                               float npix, float* __restrict__ ssym, float* __restrict__ bvec,
+                                                               unsigned int* __restrict__ ssym_amax) {
+#pragma clang fp contract(off)
+    const int c = blockIdx.x;
+    const float s1 = totals[1];
+    const float level = totals[0] / s1;
+    const float wn = weight / npix;
+    unsigned int amax = 0;
+    for (int d = threadIdx.x; d < n; d += 256) {
+        const size_t cd = (size_t)c * n + d, dc = (size_t)d * n + c;
+        const float a = scaled_mse_slope(gram[cd] - gram_t[cd], level, s1);
+        const float b = scaled_mse_slope(gram[dc] - gram_t[dc], level, s1);
+        const float sv = (a + b) * wn;
+        ssym[cd] = sv;
+        const unsigned int bits = abs_bits(sv);
+        amax = bits > amax ? bits : amax;
+    }
+    if (ssym_amax) amax_commit(amax, ssym_amax);      // bound on max |Ssym| for the fp16x3 1x1 convolution (every lane arrives)
+    if (threadIdx.x == 0) bvec[c] = 0.f;
+}
+
 // The seeding of st_plan_backward (the backward of VGGFeatures.forward, style_transfer.py:78-90, for gradients that arrive
 // at the taps from outside): an external tap gradient enters the node's gradient buffer.
 //   ACC == false: g = ext.  Ahead of the data-gradient launch that accumulates into the node - that launch masks the total -
@@ -697,6 +822,35 @@ int launch_content_mse(const float* feat, const float* target, long long count, 
     if (ticket) return 0;                 // the last block wrote the loss
     hipLaunchKernelGGL(content_mse_final_kernel, dim3(1), dim3(64), 0, s, partials, blocks, (float)count,
                        weight, loss_out);
+    ST_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_scaled_mse_sums(const float* x, const float* target, long long count, float weight, float* partials, float* totals,
+                           float* loss_out, hipStream_t s, unsigned int* ticket) {
+    ST_REQUIRE(ticket, "scaled MSE sums: the last block finishes the sum, a ticket word is needed");
+    const int blocks = stream_blocks((count & 3) == 0 ? count / 4 : count);
+    hipLaunchKernelGGL(scaled_mse_sums_kernel, dim3(blocks), dim3(256), 0, s, x, target, count, weight, kScaledMseEps, partials,
+                       LastBlock{ticket}, totals, loss_out);
+    ST_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_scaled_mse_grad(const float* feat, const float* target, long long count, float weight, const float* totals,
+                           float* grad, hipStream_t s, int accumulate) {
+    const int blocks = stream_blocks((count & 3) == 0 ? count / 4 : count);
+    if (accumulate)
+        hipLaunchKernelGGL(scaled_mse_grad_kernel<true>, dim3(blocks), dim3(256), 0, s, feat, target, count, weight, totals, grad);
+    else
+        hipLaunchKernelGGL(scaled_mse_grad_kernel<false>, dim3(blocks), dim3(256), 0, s, feat, target, count, weight, totals, grad);
+    ST_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_gram_grad_finish(const float* gram, const float* gram_t, const float* totals, int n, float weight, long long npix,
+                            float* ssym, float* bvec, hipStream_t s, unsigned int* ssym_amax) {
+    hipLaunchKernelGGL(gram_grad_finish_kernel, dim3(n), dim3(256), 0, s, gram, gram_t, totals, n, weight, (float)npix, ssym, bvec,
+                       ssym_amax);
     ST_LAUNCH_CHECK();
     return 0;
 }

@@ -19,6 +19,15 @@
 // on the caller's stream, in that order.  Masking by the producer, accumulation into seeded nodes and the fp16x3 bounds are
 // run_tap_backward's, unchanged.  ST_GENERAL_TAPS=1 (st_set_option) sends the reference's configuration down this path too, so
 // that it can be compared with the default closure on the same plan.
+//
+// Loss kinds (st_plan_set_loss_kinds): one kind per list says WHAT the terms are.  The defaults - ContentLossMSE, StyleLossW2 -
+// are the lines above.  Kind 1 of either list is the reference's ScaledMSELoss (st_pointwise.hip has the formulas), on the
+// features (ContentLoss) or on the Gram matrix (StyleLoss); any non-default kind runs this closure, the reference's lists too:
+//   a Gram head             the tap's second raw moment (moments_of_tap: no mean, no covariance), the sums and the term, then
+//                           Ssym = (w / N) (D + D^T) with a zero b, and the W2 heads' own 1x1 step dF = Ssym F into the seed
+//                           buffer (gram_head: four launches, no Newton-Schulz chain)
+//   a scaled-MSE content term   the sums and the term, then the seed written or added  (launch_scaled_mse_sums / _grad)
+// Everything around the terms - TV, the forward, the terms' total, the tap backward, the step's fold - is unchanged.
 #include <algorithm>
 
 #include "st_plan.h"
@@ -40,7 +49,7 @@ int tap_position(int layer) {
 
 bool general_taps(const st_plan* p) {
     static Option force("ST_GENERAL_TAPS", 0);
-    return !p->strip && (!p->reference_taps || force.get() != 0);
+    return !p->strip && (!p->reference_taps || p->content_kind != 0 || p->style_kind != 0 || force.get() != 0);
 }
 
 int closure_top_op(const st_plan* p) {
@@ -74,8 +83,28 @@ HeadSite general_head_site(st_plan* p, int j) {
     return at;
 }
 
+// the totals (sum d^2, sum |d| + eps) of scaled-MSE term k in SumLoss order, behind the per-block partials
+float* kind_totals(st_plan* p, int k) { return p->kind_scratch + 2 * kStreamBlocks + 2 * k; }
+
+// StyleLoss (style_transfer.py:129-142) under Scale(weight) + its backward down to the tap's feature gradient.  The term's
+// scratch and ticket are shared with the content terms: every launch of this closure is on the caller's stream.
+int gram_head(st_plan* p, const HeadSite& at, int term, hipStream_t s) {
+    StyleHead& h = *at.h;
+    if (moments_of_tap(p, at, h.mean, h.srm, s)) return 1;
+    float* totals = kind_totals(p, term);
+    if (launch_scaled_mse_sums(h.srm, h.gram_t, (long long)h.n * h.n, at.weight, p->kind_scratch, totals, at.loss, s, p->tickets + 128))
+        return 1;
+    if (launch_gram_grad_finish(h.srm, h.gram_t, totals, h.n, at.weight, h.npix, h.ssym, h.bvec, s,
+                                p->net->conv_elem == 1 ? h.s_amax : nullptr))
+        return 1;
+    return style_head_gradient(p, at, s);
+}
+
 // seed buffers of the tapped positions and the terms' array
 int ensure_tap_buffers(st_plan* p) {
+    if ((p->content_kind != 0 || p->style_kind != 0) && !p->kind_scratch &&
+        plan_alloc(p, &p->kind_scratch, 2 * kStreamBlocks + 2 * 32))
+        return 1;
     if (!p->terms) {
         if (plan_alloc(p, &p->terms, 64)) return 1;
         ST_HIP(hipMemset(p->terms, 0, 64 * sizeof(float)));
@@ -107,13 +136,28 @@ int general_loss_and_grad(st_plan* p, const float* image, float* grad_out, float
     std::sort(order, order + ns, [&](int a, int b) { return p->style_op[a] > p->style_op[b]; });
     bool styled[kNumOps] = {};
     for (int k = 0; k < ns; ++k) {
-        if (style_head(p, general_head_site(p, order[k]), s)) return 1;
+        const HeadSite at = general_head_site(p, order[k]);
+        if (p->style_kind == 1 ? gram_head(p, at, nc + order[k], s) : style_head(p, at, s)) return 1;
         styled[p->style_op[order[k]]] = true;
     }
-    // ContentLossMSE per content layer (style_transfer.py:425-429), behind the style head of the same layer where there is one
+    // ContentLossMSE per content layer (style_transfer.py:425-429), behind the style head of the same layer where there is one;
+    // kind 1: ContentLoss, its sums and then its seed
     for (int i = 0; i < nc; ++i) {
         const int op = p->content_op[i];
         const Node& ct = node_at(p, op);
+        if (p->content_kind == 1) {
+            float* totals = kind_totals(p, i);
+            if (hbm_profiled(p, HBM_CONTENT, 2.0 * 4.0 * ct.count(), s, [&] {
+                    return launch_scaled_mse_sums(ct.y, p->content_target[op], (long long)ct.count(), p->content_weight[i],
+                                                  p->kind_scratch, totals, terms + i, s, p->tickets + 128);
+                }) ||
+                hbm_profiled(p, HBM_CONTENT, (styled[op] ? 4.0 : 3.0) * 4.0 * ct.count(), s, [&] {
+                    return launch_scaled_mse_grad(ct.y, p->content_target[op], (long long)ct.count(), p->content_weight[i], totals,
+                                                  p->tap_seed[op], s, styled[op] ? 1 : 0);
+                }))
+                return 1;
+            continue;
+        }
         if (hbm_profiled(p, HBM_CONTENT, 3.0 * 4.0 * ct.count(), s, [&] {
                 return launch_content_mse(ct.y, p->content_target[op], (long long)ct.count(), p->content_weight[i], p->tap_seed[op],
                                           p->red_partials + 4 * kStreamBlocks, terms + i, s, p->tickets + 64, styled[op] ? 1 : 0);
@@ -191,6 +235,43 @@ int st_plan_set_taps(st_plan* p, int n_content, const int* content_layers, int n
     assign_head_bounds(p);
     invalidate_graph(p);
     p->phases.clear();
+    return 0;
+}
+
+int st_plan_set_loss_kinds(st_plan* p, int content_kind, int style_kind) {
+    ST_REQUIRE(p, "st_plan_set_loss_kinds: null plan");
+    ST_REQUIRE(content_kind == 0 || content_kind == 1,
+               "st_plan_set_loss_kinds: unknown content loss kind %d (0: mse - ContentLossMSE, 1: scaled_mse - ContentLoss)", content_kind);
+    ST_REQUIRE(style_kind == 0 || style_kind == 1,
+               "st_plan_set_loss_kinds: unknown style loss kind %d (0: w2 - StyleLossW2, 1: gram - StyleLoss)", style_kind);
+    ST_REQUIRE(!p->strip || (content_kind == 0 && style_kind == 0),
+               "st_plan_set_loss_kinds: strip plans run the default loss kinds only (content mse, style w2)");
+    // what the listed heads need under the new kind, now: a failed allocation leaves the plan as it was
+    const int former = p->style_kind;
+    p->style_kind = style_kind;
+    for (int j = 0; j < p->n_style; ++j)
+        if (ensure_style_alloc(p, p->head[p->style_op[j]])) {
+            p->style_kind = former;
+            return 1;
+        }
+    p->content_kind = content_kind;
+    // a target is kept in the form its kind reads (a root, or a Gram matrix): as after st_plan_set_taps, every target set
+    // before is gone, every bound word is dealt again and nothing built on the former terms survives.  The lists and all
+    // weights stay.
+    for (int op = 0; op < kNumOps; ++op) {
+        p->head[op].target_set = false;
+        p->content_set[op] = false;
+    }
+    assign_head_bounds(p);
+    invalidate_graph(p);
+    p->phases.clear();
+    return 0;
+}
+
+int st_plan_loss_kinds(const st_plan* p, int* content_kind, int* style_kind) {
+    ST_REQUIRE(p, "st_plan_loss_kinds: null plan");
+    if (content_kind) *content_kind = p->content_kind;
+    if (style_kind) *style_kind = p->style_kind;
     return 0;
 }
 

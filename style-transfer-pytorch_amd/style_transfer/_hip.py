@@ -21,6 +21,8 @@ _c_float_p = ctypes.c_void_p      # device pointers travel as integers
 # features indices the trunk keeps: the 13 ReLU outputs and the 4 pool outputs (st_plan_feature)
 TAPS = (1, 3, 4, 6, 8, 9, 11, 13, 15, 17, 18, 20, 22, 24, 26, 27, 29)
 DEFAULT_CONTENT_LAYERS, DEFAULT_STYLE_LAYERS = (22,), (1, 6, 11, 20, 29)
+# the loss kind of each list (st_plan_set_loss_kinds), by the library's code: ContentLossMSE / ContentLoss, StyleLossW2 / StyleLoss
+CONTENT_LOSSES, STYLE_LOSSES = ('mse', 'scaled_mse'), ('w2', 'gram')
 _lib = None
 
 
@@ -65,6 +67,8 @@ def _declare(lib):
         'st_plan_set_loss_weights': (i32, [vp, f32, ctypes.POINTER(f32), f32]),
         'st_plan_set_taps': (i32, [vp, i32, ip, i32, ip]),
         'st_plan_set_tap_weights': (i32, [vp, ctypes.POINTER(f32), ctypes.POINTER(f32), f32]),
+        'st_plan_set_loss_kinds': (i32, [vp, i32, i32]),
+        'st_plan_loss_kinds': (i32, [vp, ip, ip]),
         'st_plan_set_content_target_at': (i32, [vp, i32, vp, vp]),
         'st_plan_term_losses': (i32, [vp, pp, ip]),
         'st_plan_loss_and_grad': (i32, [vp, vp, vp, vp, vp]),
@@ -252,6 +256,8 @@ class Plan:
     forward_count = 0
     # the configured layers (set_taps); strip plans keep the default
     content_layers, style_layers = DEFAULT_CONTENT_LAYERS, DEFAULT_STYLE_LAYERS
+    # the lists' loss kinds (set_loss_kinds)
+    content_loss, style_loss = CONTENT_LOSSES[0], STYLE_LOSSES[0]
 
     def __init__(self, net, height, width):
         self.lib = net.lib
@@ -285,6 +291,19 @@ class Plan:
         with torch.cuda.device(self.device):
             _check(self.lib.st_plan_set_taps(self.handle, len(content_layers), ca, len(style_layers), sa))
         self.content_layers, self.style_layers = content_layers, style_layers
+
+    def set_loss_kinds(self, content='mse', style='w2'):
+        """What the terms are, one kind per list (st_plan_set_loss_kinds): ``content`` one of ``CONTENT_LOSSES`` - 'mse'
+        (ContentLossMSE) or 'scaled_mse' (ContentLoss) - and ``style`` one of ``STYLE_LOSSES`` - 'w2' (StyleLossW2) or 'gram'
+        (StyleLoss on Gram matrices).  Drops every target set before; the layers and all weights stay.  Anything but the
+        defaults runs the general closure; strip plans refuse it."""
+        if content not in CONTENT_LOSSES:
+            raise ValueError(f'content loss {content!r}: must be one of {CONTENT_LOSSES}')
+        if style not in STYLE_LOSSES:
+            raise ValueError(f'style loss {style!r}: must be one of {STYLE_LOSSES}')
+        with torch.cuda.device(self.device):
+            _check(self.lib.st_plan_set_loss_kinds(self.handle, CONTENT_LOSSES.index(content), STYLE_LOSSES.index(style)))
+        self.content_loss, self.style_loss = content, style
 
     def term_losses(self):
         """The weighted terms of the last closure in SumLoss order - content layers, style layers, tv - as a device tensor

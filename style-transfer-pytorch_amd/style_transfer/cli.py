@@ -292,8 +292,18 @@ def build_parser():
                         "torch hub cache)")
     p.add_argument('--precision', type=str, default='fp16x3', choices=['fp16x3', 'bf16x6', 'fp32', 'bf16x3'],
                    help='arithmetic of the 3x3 trunk convolutions')
+    p.add_argument('--content-loss', type=str, default='mse', choices=['mse', 'scaled_mse'],
+                   help="the content term: 'mse' (ContentLossMSE) or 'scaled_mse' (ContentLoss: sum d^2 / sum |d|)")
+    p.add_argument('--style-loss', type=str, default='w2', choices=['w2', 'gram'],
+                   help="the style term: 'w2' (StyleLossW2) or 'gram' (StyleLoss: the scaled MSE of Gram matrices)")
     p.add_argument('--trace', type=str, default='trace.json', help='where to write the iteration trace')
     return p
+
+
+def apply_loss_kinds(st, args):
+    """--content-loss / --style-loss onto the StyleTransfer attributes that stylize() reads."""
+    st.content_loss, st.style_loss = args.content_loss, args.style_loss
+    return st
 
 
 def main(argv=None):
@@ -343,6 +353,7 @@ def main(argv=None):
     torch.manual_seed(args.random_seed)
     print('Loading model...')
     st = StyleTransfer(devices=devices, pooling=args.pooling, weights=args.weights, precision=args.precision)
+    apply_loss_kinds(st, args)
     callback = Callback(st, args, image_type=image_type, web_interface=web_interface)
     atexit.register(callback.close)
 

@@ -224,6 +224,23 @@ def _resolve_taps(content_layers, style_layers, style_weights, world=1):
     return content, style, [weight for _, weight in pairs]
 
 
+def _resolve_loss_kinds(content_loss, style_loss, world=1):
+    """``StyleTransfer.content_loss`` / ``style_loss`` as the fused closure takes them: returns the two names.  Raises
+    ``ValueError`` for an unknown name and for a non-default kind on several ranks, before any device work."""
+    if content_loss not in _hip.CONTENT_LOSSES:
+        raise ValueError(f'content_loss {content_loss!r}: must be one of {list(_hip.CONTENT_LOSSES)} '
+                         "('mse': ContentLossMSE, 'scaled_mse': ContentLoss)")
+    if style_loss not in _hip.STYLE_LOSSES:
+        raise ValueError(f'style_loss {style_loss!r}: must be one of {list(_hip.STYLE_LOSSES)} '
+                         "('w2': StyleLossW2, 'gram': StyleLoss on Gram matrices)")
+    default = (content_loss, style_loss) == (_hip.CONTENT_LOSSES[0], _hip.STYLE_LOSSES[0])
+    if world > 1 and not default:
+        raise ValueError(f'content_loss {content_loss!r} / style_loss {style_loss!r} on {world} ranks: row strips run the '
+                         "default kinds ('mse', 'w2') only; other loss kinds are out of scope for strips - run them on one "
+                         'device')
+    return content_loss, style_loss
+
+
 def _resolve_weights(weights):
     if isinstance(weights, (list, tuple)):
         return list(weights)
@@ -575,6 +592,11 @@ def _device_list_stylize(st, content_image, style_images, kw, callback):
 
 
 class StyleTransfer:
+    # what the terms are (read by stylize() next to the layer attributes): 'mse' (ContentLossMSE) or 'scaled_mse' (ContentLoss);
+    # 'w2' (StyleLossW2) or 'gram' (StyleLoss on Gram matrices)
+    content_loss = 'mse'
+    style_loss = 'w2'
+
     def __init__(self, devices=['cuda:0'], pooling='max', weights=None, precision='fp16x3'):
         # reference :310 defaults to ['cpu']; this build has no CPU path, so the default is the first HIP device
         self.devices = [torch.device(device) for device in devices]
@@ -802,6 +824,8 @@ class StyleTransfer:
         content_layers, style_layers, layer_weights = _resolve_taps(
             self.content_layers, self.style_layers, self.style_weights,
             world=max(len(self.devices), _dist_info()[1]))
+        content_loss, style_loss = _resolve_loss_kinds(self.content_loss, self.style_loss,
+                                                       world=max(len(self.devices), _dist_info()[1]))
         if len(self.devices) > 1 and self._job is None:
             return _device_list_stylize(self, content_image, style_images, dict(
                 style_weights=style_weights, content_weight=content_weight, tv_weight=tv_weight, optimizer=optimizer,
@@ -928,6 +952,8 @@ class StyleTransfer:
                 plan = self._plan = _hip.Plan(self.model.net, ch, cw)
                 if (content_layers, style_layers) != (list(plan.content_layers), list(plan.style_layers)):
                     plan.set_taps(content_layers, style_layers)
+                if (content_loss, style_loss) != (plan.content_loss, plan.style_loss):
+                    plan.set_loss_kinds(content_loss, style_loss)
                 self._build_targets(plan, content.to(device), style_images, style_weights, scale, style_scale_fac,
                                     style_size)
             plan.set_loss_weights(content_weights, layer_weights, tv_weight)
