@@ -469,6 +469,75 @@ int st_op_pool2x2_backward(const float* in, const float* grad_out, float* grad_i
                            int mode, void* stream);
 
 /* ==================================================================================================================
+ * NATIVE LOSS MODULES - what style_transfer/losses.py runs on an eligible HIP tensor instead of torch kernels: the
+ * reference's loss modules (style_transfer.py:93-195) outside any st_plan, inside autograd.  Each entry is the value OR the
+ * gradient of one module; the gradient entries take autograd's grad_output as a DEVICE scalar `upstream` (the product of
+ * Scale / SumLoss, style_transfer.py:198-221) and never read it on the host.  No float atomics: the same arguments give
+ * the same bits.  Every launch goes on `stream`; none of these entries allocates or synchronises, except st_head_create
+ * (allocates, synchronises) and st_head_destroy (hipFree synchronises the device).
+ * ================================================================================================================== */
+
+/* A standalone style head: StyleLossW2 (kind 0, style_transfer.py:149-181) or StyleLoss (kind 1, :129-142) on a dense
+ * [channels][height][width] fp32 tensor that no trunk kernel produced - signed values, all zeros and a single pixel
+ * included.  kind 2 is a MOMENTS-ONLY head: st_head_moments alone, none of the workspaces a forward or backward needs.
+ * channels in {64, 128, 256, 512}; height, width >= 1; precision 0 = exact fp32 MFMA, 4 = fp16x3 (the codes of
+ * st_op_conv1x1; fp16x3 measures max |feat| of the tensor it is given, where a plan gets the bound from the producer).
+ * precision governs the two steps that touch the tensor - the Gram moments and the 1x1 step dF = Ssym F + b 1^T; the C x C
+ * work is the plan's in every mode (fp32 products and forward chain; for C >= 256 the Lyapunov backward chain in fp16x3,
+ * csrc/st_nsgemm.hip).  Of the 1x1 step only a tap with more than 320 workgroups of 64 channels x 128 pixels runs the
+ * fp16x3 kernel; smaller ones split K (or take the small-tap kernel) on the exact fp32 MFMA in either mode.
+ * The head owns its workspaces - Gram partials, the 1x1 step's split-K scratch, the scaled (Ssym, b) of a backward, the
+ * reduction scratch and ticket of a Gram head, the covariance / chain matrices and Newton-Schulz workspace of a W2 head
+ * (a Gram head allocates none of those) - allocated here, freed by st_head_destroy, counted by st_head_device_bytes.
+ * Calls on one head are ordered by the stream they are given; a head serves one stream at a time. */
+typedef struct st_head st_head;
+int st_head_create(st_head** out, int kind, int channels, int height, int width, int precision);
+int st_head_destroy(st_head* head);
+long long st_head_device_bytes(const st_head* head);
+/* Floats of the per-call state st_head_forward leaves for st_head_backward: Ssym [C*C] | b [C] | the tensor's fp16x3
+ * operand bound.  The caller owns it (autograd: a tensor saved on the node), so a head may run forward any number of
+ * times before any backward. */
+long long st_head_state_floats(const st_head* head);
+/* StyleLossW2.get_target (style_transfer.py:162-168): mean_out [C] (may be NULL) and srm_out [C*C] = F F^T / (h w), exactly
+ * symmetric; srm_out alone is StyleLoss.get_target (:135-138).  Either kind of head. */
+int st_head_moments(st_head* head, const float* feat, float* mean_out, float* srm_out, void* stream);
+/* The module's forward, UNWEIGHTED, into loss_out[0] (device).  Targets are read in place - the module's own buffers:
+ * kind 0: mean_t [C], cov_t [C*C] (eps I included, :156), root_t [C*C] = sqrtm(cov_t); kind 1: gram_t [C*C]; the other
+ * kind's pointers are ignored.  eps: StyleLossW2's covariance eps (:152) or ScaledMSELoss's (:97).  state != NULL: also
+ * everything the gradient needs, dF = Ssym F + b 1^T, as (Ssym, b) into `state` (st_head_state_floats floats); NULL (no
+ * gradient will be asked for): the Lyapunov chain, the d cov products and (Ssym, b) are skipped.  The sequence is the
+ * plan's style head's with weight 1 (csrc/st_closure.hip style_head_chain, csrc/st_taps.hip gram_head). */
+int st_head_forward(st_head* head, const float* feat, const float* mean_t, const float* cov_t, const float* root_t,
+                    const float* gram_t, float eps, float* loss_out, float* state, void* stream);
+/* grad_feat [C][h][w] = upstream[0] * (Ssym F + b 1^T) from the state of a forward on the same `feat`.  upstream is folded
+ * into the C x C stage - (Ssym, b) and the fp16x3 bound of Ssym are scaled by one C-workgroup launch - so the tap-sized
+ * data is read once and written once, by the 1x1 step. */
+int st_head_backward(st_head* head, const float* feat, const float* state, const float* upstream, float* grad_feat,
+                     void* stream);
+
+/* Pointwise terms on `count` floats.  Reduction scratch is the CALLER's, per call: `scratch` = st_op_reduce_scratch_floats()
+ * floats that nothing else touches until the call's launches have run (two launches: per-workgroup partial sums, then one
+ * workgroup adds them in index order; no ticket word, nothing to keep zeroed). */
+long long st_op_reduce_scratch_floats(void);
+/* nn.MSELoss (ContentLossMSE, style_transfer.py:119-126): loss_out[0] = sum (x - t)^2 / count ... */
+int st_op_mse_loss(const float* x, const float* target, long long count, float* scratch, float* loss_out, void* stream);
+/* ... and grad[i] = upstream[0] * 2 (x - t)[i] / count. */
+int st_op_mse_loss_backward(const float* x, const float* target, long long count, const float* upstream, float* grad,
+                            void* stream);
+/* ScaledMSELoss (style_transfer.py:93-106; ContentLoss :109-116) with d = x - t: totals[0] = S2 = sum d^2, totals[1] = S1 =
+ * sum |d| + eps, loss_out[0] = L = S2 / S1.  The two totals are what the gradient needs (autograd: saved on the node) ... */
+int st_op_scaled_mse_loss(const float* x, const float* target, long long count, float eps, float* scratch, float* totals,
+                          float* loss_out, void* stream);
+/* ... grad[i] = upstream[0] * (2 d - L sgn d)[i] / S1, sgn 0 = 0: where every d is zero the gradient is zero, not NaN. */
+int st_op_scaled_mse_loss_backward(const float* x, const float* target, long long count, const float* totals,
+                                   const float* upstream, float* grad, void* stream);
+/* TVLoss (style_transfer.py:184-195) on a [3][H][W] image, H, W >= 1: the value alone (st_op_tv_loss writes the unit
+ * gradient with it) ... */
+int st_op_tv_value(const float* image, int height, int width, float* scratch, float* loss_out, void* stream);
+/* ... and grad [3][H][W] = upstream[0] * d TVLoss / d image. */
+int st_op_tv_loss_backward(const float* image, int height, int width, const float* upstream, float* grad, void* stream);
+
+/* ==================================================================================================================
  * MEASUREMENT AIDS - not part of the drop-in surface (no reference counterpart; a binding of the reference does not
  * need them).  They time the product's own kernels in isolation for tools/ and profiles/: st_op_sqrtm_time,
  * st_op_conv3x3_time, st_op_mfma_rate, st_op_mfma_valu_rate, st_op_grid_barrier_time (and the st_plan_profile_* hooks

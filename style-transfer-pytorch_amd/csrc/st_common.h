@@ -603,9 +603,9 @@ int launch_content_mse(const float* feat, const float* target, long long count, 
 // the sums - totals[0] = sum d^2, totals[1] = sum |d| + eps, loss_out[0] = weight totals[0] / totals[1]; partials: 2 floats
 // per block, at most 2 kStreamBlocks; ticket: a zeroed device word - then the content seed from them,
 // grad = weight (2 d - L sgn d) / S1 (accumulate != 0: added to what grad holds)
-constexpr float kScaledMseEps = 1e-8f;            // ScaledMSELoss eps (style_transfer.py:97)
+constexpr float kScaledMseEps = 1e-8f;            // ScaledMSELoss eps (style_transfer.py:97): what a plan passes; a standalone head its module's
 int launch_scaled_mse_sums(const float* x, const float* target, long long count, float weight, float* partials, float* totals,
-                           float* loss_out, hipStream_t s, unsigned int* ticket);
+                           float* loss_out, hipStream_t s, unsigned int* ticket, float eps = kScaledMseEps);
 int launch_scaled_mse_grad(const float* feat, const float* target, long long count, float weight, const float* totals,
                            float* grad, hipStream_t s, int accumulate = 0);
 // ... or, for a Gram head, (Ssym, b) of its 1x1 step: ssym = (weight / npix) (D + D^T), D = dL/dG from the totals; bvec = 0

@@ -827,10 +827,10 @@ int launch_content_mse(const float* feat, const float* target, long long count, 
 }
 
 int launch_scaled_mse_sums(const float* x, const float* target, long long count, float weight, float* partials, float* totals,
-                           float* loss_out, hipStream_t s, unsigned int* ticket) {
+                           float* loss_out, hipStream_t s, unsigned int* ticket, float eps) {
     ST_REQUIRE(ticket, "scaled MSE sums: the last block finishes the sum, a ticket word is needed");
     const int blocks = stream_blocks((count & 3) == 0 ? count / 4 : count);
-    hipLaunchKernelGGL(scaled_mse_sums_kernel, dim3(blocks), dim3(256), 0, s, x, target, count, weight, kScaledMseEps, partials,
+    hipLaunchKernelGGL(scaled_mse_sums_kernel, dim3(blocks), dim3(256), 0, s, x, target, count, weight, eps, partials,
                        LastBlock{ticket}, totals, loss_out);
     ST_LAUNCH_CHECK();
     return 0;

@@ -119,6 +119,20 @@ def _declare(lib):
         'st_op_conv1x1': (i32, [vp, vp, vp, vp, i32, i32, i64, i32, vp]),
         'st_op_pool2x2': (i32, [vp, vp, i32, i32, i32, i32, vp]),
         'st_op_pool2x2_backward': (i32, [vp, vp, vp, i32, i32, i32, i32, vp]),
+        'st_head_create': (i32, [pp, i32, i32, i32, i32, i32]),
+        'st_head_destroy': (i32, [vp]),
+        'st_head_device_bytes': (i64, [vp]),
+        'st_head_state_floats': (i64, [vp]),
+        'st_head_moments': (i32, [vp, vp, vp, vp, vp]),
+        'st_head_forward': (i32, [vp, vp, vp, vp, vp, vp, f32, vp, vp, vp]),
+        'st_head_backward': (i32, [vp, vp, vp, vp, vp, vp]),
+        'st_op_reduce_scratch_floats': (i64, []),
+        'st_op_mse_loss': (i32, [vp, vp, i64, vp, vp, vp]),
+        'st_op_mse_loss_backward': (i32, [vp, vp, i64, vp, vp, vp]),
+        'st_op_scaled_mse_loss': (i32, [vp, vp, i64, f32, vp, vp, vp, vp]),
+        'st_op_scaled_mse_loss_backward': (i32, [vp, vp, i64, vp, vp, vp, vp]),
+        'st_op_tv_value': (i32, [vp, i32, i32, vp, vp, vp]),
+        'st_op_tv_loss_backward': (i32, [vp, i32, i32, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)       # AttributeError here = header and library disagree
@@ -581,6 +595,69 @@ class LBFGS:
                 't': t.value, 'gtd': gtd.value}
 
 
+class Head:
+    """A standalone style head (st_head): StyleLossW2 (``kind='w2'``) or StyleLoss (``kind='gram'``) on a dense fp32
+    [C, h, w] tensor outside any plan - what style_transfer/losses.py runs on an eligible HIP tensor.  Every tensor
+    argument is a contiguous fp32 tensor on the head's device with a 16-byte aligned pointer; ``upstream`` is a 0-dim or
+    one-element DEVICE tensor (autograd's grad_output) that is never read on the host."""
+
+    KINDS = ('w2', 'gram', 'moments')       # 'moments': a head for ``moments`` alone (get_target), no forward / backward workspaces
+
+    def __init__(self, kind, channels, height, width, device, precision='fp16x3'):
+        self.lib = load_library()
+        self.kind, self.precision = kind, precision
+        self.shape = (int(channels), int(height), int(width))
+        self.device = torch.device(device)
+        h = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            _check(self.lib.st_head_create(ctypes.byref(h), self.KINDS.index(kind), *self.shape, Net.PRECISIONS[precision]))
+        self.handle = h
+        self.state_floats = int(self.lib.st_head_state_floats(h))
+
+    def __del__(self):
+        h, self.handle = getattr(self, 'handle', None), None
+        if h and self.lib is not None:
+            self.lib.st_head_destroy(h)
+
+    def device_bytes(self):
+        return int(self.lib.st_head_device_bytes(self.handle))
+
+    def _feat(self, feat):
+        assert feat.numel() == self.shape[0] * self.shape[1] * self.shape[2], (tuple(feat.shape), self.shape)
+        return _ptr(feat)
+
+    def moments(self, feat, mean=True):
+        """(mean [C] or None, srm [C, C]) of ``feat`` (st_head_moments): StyleLossW2.get_target / StyleLoss.get_target."""
+        c = self.shape[0]
+        mean_out = torch.empty(c, device=self.device, dtype=torch.float32) if mean else None
+        srm = torch.empty((c, c), device=self.device, dtype=torch.float32)
+        with torch.cuda.device(self.device):
+            _check(self.lib.st_head_moments(self.handle, self._feat(feat), _ptr(mean_out), _ptr(srm), _stream()))
+        return mean_out, srm
+
+    def forward(self, feat, targets, eps, need_grad=True):
+        """(loss [0-dim device tensor, unweighted], state or None) - st_head_forward.  ``targets``: (mean, cov, cov_sqrt) of
+        a StyleLossW2, (gram,) of a StyleLoss - the module's buffers, read in place.  ``state`` is what ``backward`` needs:
+        (Ssym, b) and the operand bound, one tensor of ``state_floats`` floats owned by the caller."""
+        loss = torch.empty((), device=self.device, dtype=torch.float32)
+        state = torch.empty(self.state_floats, device=self.device, dtype=torch.float32) if need_grad else None
+        if self.kind == 'w2':
+            mean_t, cov_t, root_t = targets
+            ptrs = (_ptr(mean_t), _ptr(cov_t), _ptr(root_t), None)
+        else:
+            ptrs = (None, None, None, _ptr(targets[0]))
+        with torch.cuda.device(self.device):
+            _check(self.lib.st_head_forward(self.handle, self._feat(feat), *ptrs, float(eps), _ptr(loss), _ptr(state), _stream()))
+        return loss, state
+
+    def backward(self, feat, state, upstream):
+        """upstream * (Ssym F + b 1^T) as a new tensor of ``feat``'s shape (st_head_backward)."""
+        grad = torch.empty(feat.shape, device=self.device, dtype=torch.float32)
+        with torch.cuda.device(self.device):
+            _check(self.lib.st_head_backward(self.handle, self._feat(feat), _ptr(state), _ptr(upstream), _ptr(grad), _stream()))
+        return grad
+
+
 def _copy_d2d(dst, src_ptr):
     """Device-to-device copy from a borrowed raw pointer into a torch tensor (same device)."""
     hip = _hip_runtime()
@@ -805,3 +882,65 @@ def op_conv3x3_dgrad(grad_out, relu_out, weight, precision=0):
                                        _ptr(weight.contiguous()), _ptr(gin), cin, cout, h, w, int(precision),
                                        _stream()))
     return gin
+
+
+# ---- the pointwise loss terms with a device-scalar upstream gradient (style_transfer/losses.py) -------------------------
+def _reduce_scratch(device):
+    """The per-call reduction scratch of the value entries (include/st_amd.h: the caller owns it)."""
+    return torch.empty(int(load_library().st_op_reduce_scratch_floats()), device=device, dtype=torch.float32)
+
+
+def op_mse_loss(x, target):
+    """nn.MSELoss value as a 0-dim device tensor (st_op_mse_loss)."""
+    lib = load_library()
+    loss = torch.empty((), device=x.device, dtype=torch.float32)
+    with torch.cuda.device(x.device):
+        _check(lib.st_op_mse_loss(_ptr(x), _ptr(target), x.numel(), _ptr(_reduce_scratch(x.device)), _ptr(loss), _stream()))
+    return loss
+
+
+def op_mse_loss_backward(x, target, upstream):
+    lib = load_library()
+    grad = torch.empty(x.shape, device=x.device, dtype=torch.float32)
+    with torch.cuda.device(x.device):
+        _check(lib.st_op_mse_loss_backward(_ptr(x), _ptr(target), x.numel(), _ptr(upstream), _ptr(grad), _stream()))
+    return grad
+
+
+def op_scaled_mse_loss(x, target, eps):
+    """(ScaledMSELoss value [0-dim], totals [2] = sum d^2, sum |d| + eps) - st_op_scaled_mse_loss."""
+    lib = load_library()
+    loss = torch.empty((), device=x.device, dtype=torch.float32)
+    totals = torch.empty(2, device=x.device, dtype=torch.float32)
+    with torch.cuda.device(x.device):
+        _check(lib.st_op_scaled_mse_loss(_ptr(x), _ptr(target), x.numel(), float(eps), _ptr(_reduce_scratch(x.device)),
+                                         _ptr(totals), _ptr(loss), _stream()))
+    return loss, totals
+
+
+def op_scaled_mse_loss_backward(x, target, totals, upstream):
+    lib = load_library()
+    grad = torch.empty(x.shape, device=x.device, dtype=torch.float32)
+    with torch.cuda.device(x.device):
+        _check(lib.st_op_scaled_mse_loss_backward(_ptr(x), _ptr(target), x.numel(), _ptr(totals), _ptr(upstream), _ptr(grad),
+                                                  _stream()))
+    return grad
+
+
+def op_tv_value(image):
+    """TVLoss value of a [..., 3, H, W] image (one image) as a 0-dim device tensor (st_op_tv_value)."""
+    lib = load_library()
+    h, w = image.shape[-2:]
+    loss = torch.empty((), device=image.device, dtype=torch.float32)
+    with torch.cuda.device(image.device):
+        _check(lib.st_op_tv_value(_ptr(image), h, w, _ptr(_reduce_scratch(image.device)), _ptr(loss), _stream()))
+    return loss
+
+
+def op_tv_loss_backward(image, upstream):
+    lib = load_library()
+    h, w = image.shape[-2:]
+    grad = torch.empty(image.shape, device=image.device, dtype=torch.float32)
+    with torch.cuda.device(image.device):
+        _check(lib.st_op_tv_loss_backward(_ptr(image), h, w, _ptr(upstream), _ptr(grad), _stream()))
+    return grad

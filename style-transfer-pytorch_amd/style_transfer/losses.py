@@ -5,11 +5,24 @@ section 2 row 2).
 libst_amd.so.  User code written against the reference can however import these names from
 ``style_transfer.style_transfer`` - ``ScaledMSELoss``, ``ContentLoss``, ``ContentLossMSE``, ``StyleLoss``,
 ``StyleLossW2``, ``TVLoss``, ``SumLoss``, ``Scale``, ``LayerApply``, ``eye_like`` (reference :93-234) - so they are
-provided here as plain torch modules with the reference's constructor arguments, buffers, static helpers and
-arithmetic.  They run wherever their tensors live; ``StyleLossW2`` reaches the library's Newton-Schulz operators
-through ``sqrtm.sqrtm_ns_lyap`` when its matrices sit on a HIP device.
+provided here with the reference's constructor arguments, buffers, static helpers and arithmetic.
+
+Native dispatch.  On an ELIGIBLE tensor (``eligible`` below: one dense fp32 tensor on a HIP device, batch 1 or absent, 64 /
+128 / 256 / 512 channels for the style modules, the module's buffers beside it in fp32) the five loss modules run in the
+library instead of torch kernels: a standalone style head (``_hip.Head``: st_head_* in include/st_amd.h) behind
+``StyleLossW2`` / ``StyleLoss``, the pointwise entries (st_op_mse_loss, st_op_scaled_mse_loss, st_op_tv_value and their
+``_backward`` twins) behind ``ContentLossMSE`` / ``ContentLoss`` / ``ScaledMSELoss`` / ``TVLoss`` - one
+``torch.autograd.Function`` per kind, whose backward hands autograd's ``grad_output`` to the library as a device scalar.
+Everything else - CPU tensors, float64, batches, other channel counts, a backward under ``create_graph=True`` - is the
+plain torch code below, unchanged.  What a call keeps for its backward lives on its autograd node (the input, and the
+C x C-sized (Ssym, b) of a style head or the two totals of a scaled MSE), so a module may be applied any number of times
+before ``backward()``; a module's head - workspaces only - is created on first use per (C, h, w), replaced when the shape
+changes, and is no part of ``state_dict()``.  ``native(enabled)`` switches the dispatch, also as a context manager.
+One host synchronisation per module, not per call: the kernels take ``eps`` as an argument, so a module's ``eps`` buffer is read
+back on its first native call (``_eps_of``).
 """
 
+import weakref
 from functools import partial
 
 import torch
@@ -17,6 +30,253 @@ from torch import nn
 from torch.nn import functional as F
 
 from . import sqrtm
+
+HEAD_CHANNELS = (64, 128, 256, 512)
+
+
+class native:
+    """``losses.native(False)`` sends every module down the torch path, ``losses.native(True)`` back to the library;
+    ``with losses.native(False): ...`` restores the former setting afterwards.  ``precision``: the arithmetic of the style
+    heads' matrix kernels, 'fp16x3' (the shipped default of the trunk) or 'fp32'."""
+
+    enabled = True
+    precision = 'fp16x3'
+
+    def __init__(self, enabled=True, precision=None):
+        if precision not in (None, 'fp16x3', 'fp32'):
+            raise ValueError(f"precision {precision!r}: must be 'fp16x3' or 'fp32'")
+        self._former = (native.enabled, native.precision)
+        native.enabled = bool(enabled)
+        if precision is not None:
+            native.precision = precision
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        native.enabled, native.precision = self._former
+
+
+# calls that went to the library, by kind ('w2', 'gram', 'mse', 'scaled_mse', 'tv', 'moments'): the native indicator of the
+# modules that hold no head
+native_calls = {}
+_heads = weakref.WeakKeyDictionary()       # module -> its _hip.Head (no module attribute: deepcopy / pickle / state_dict never see it)
+_target_heads = {}                         # get_target's moments-only heads (the static helpers have no module), the six most
+                                           # recent shapes; release_target_heads() frees them
+
+
+def _count(kind):
+    native_calls[kind] = native_calls.get(kind, 0) + 1
+
+
+def _one_dense_fp32(t, trailing):
+    """A strided fp32 tensor on a HIP device whose dimensions in front of the last ``trailing`` are absent or all 1."""
+    return (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.layout == torch.strided
+            and t.ndim >= trailing and t.numel() > 0 and all(d == 1 for d in t.shape[:t.ndim - trailing]))
+
+
+def _buffer_ok(b, like, numel):
+    return (torch.is_tensor(b) and b.device == like.device and b.dtype == torch.float32 and b.numel() == numel
+            and b.is_contiguous() and b.data_ptr() % 16 == 0 and not b.requires_grad)
+
+
+def eligible(input, kind, buffers=()):
+    """Can ``input`` take the native path of ``kind`` ('w2', 'gram', 'mse', 'scaled_mse', 'tv', 'moments')?  ``buffers``: the
+    module's tensors that the library would read in place - (mean, cov, cov_sqrt), (gram target,) or (target,).  Says nothing
+    about the ``native`` switch."""
+    if kind in ('w2', 'gram', 'moments'):
+        if not (_one_dense_fp32(input, 3) and input.ndim in (3, 4) and input.shape[-3] in HEAD_CHANNELS):
+            return False
+        if input.shape[-2] * input.shape[-1] >= 1 << 24:
+            return False
+        c = input.shape[-3]
+        sizes = {'w2': (c, c * c, c * c), 'gram': (c * c,), 'moments': ()}[kind]
+    elif kind == 'tv':
+        if not (_one_dense_fp32(input, 3) and input.ndim in (3, 4) and input.shape[-3] == 3 and input.numel() < 1 << 31):
+            return False
+        sizes = ()
+    else:
+        if not (torch.is_tensor(input) and _one_dense_fp32(input, min(input.ndim, 3))):
+            return False
+        sizes = (input.numel(),)
+        if len(buffers) != 1 or not torch.is_tensor(buffers[0]) or buffers[0].shape != input.shape:
+            return False
+    return len(buffers) == len(sizes) and all(_buffer_ok(b, input, n) for b, n in zip(buffers, sizes))
+
+
+def _wants_grad(t):
+    """Will autograd ask this call for a gradient?  (Under torch.no_grad() it will not, whatever t.requires_grad says.)"""
+    return torch.is_grad_enabled() and t.requires_grad
+
+
+def _dense(t):
+    """The tensor as the library reads it: contiguous, on a 16-byte boundary."""
+    t = t.detach().contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+def _torch_vjp(torch_forward, input, grad_output):
+    """A backward that is itself being differentiated (``create_graph=True``): the torch code's gradient, as a graph."""
+    with torch.enable_grad(), native(False):
+        (grad,) = torch.autograd.grad(torch_forward(input), input, grad_output, create_graph=True)
+    return grad
+
+
+def _eps_of(module):
+    """The module's ``eps`` buffer as a float (the kernels take it as an argument).  Reading it is a device-to-host copy,
+    i.e. a synchronisation: done on the module's first native call and again only when the buffer is another tensor object
+    (``.to()``, ``register_buffer``) or has been written in place (``load_state_dict``; the version counter).  The cache
+    holds the tensor itself, so no other buffer can turn up at its address.  (``module.eps.data = ...`` goes unnoticed.)"""
+    eps = module.eps
+    cached = module.__dict__.get('_eps_cache')
+    if cached is None or cached[0] is not eps or cached[1] != eps._version:
+        cached = module.__dict__['_eps_cache'] = (eps, eps._version, float(eps))
+    return cached[2]
+
+
+def _new_head(kind, x):
+    from . import _hip
+    return _hip.Head(kind, x.shape[-3], x.shape[-2], x.shape[-1], x.device, native.precision)
+
+
+def _head_matches(head, kind, x):
+    return (head is not None and head.kind == kind and head.shape == tuple(x.shape[-3:]) and head.device == x.device
+            and head.precision == native.precision)
+
+
+def _module_head(module, kind, x):
+    head = _heads.get(module)
+    if not _head_matches(head, kind, x):
+        head = _heads[module] = _new_head(kind, x)
+    return head
+
+
+def head_of(module):
+    """The style head a ``StyleLossW2`` / ``StyleLoss`` currently holds (``_hip.Head``), or None: it has not run natively."""
+    return _heads.get(module)
+
+
+def release_target_heads():
+    """Free the moments-only heads that ``get_target`` keeps for its six most recent shapes (a Gram workspace each, at most
+    64 MiB); the next call creates what it needs again."""
+    _target_heads.clear()
+
+
+def _native_moments(target, want_mean):
+    """(mean or None, srm) of an eligible tensor through a head's moments entry, in the shapes the torch code returns."""
+    x = _dense(target)
+    key = (tuple(x.shape[-3:]), x.device, native.precision)
+    head = _target_heads.pop(key, None) or _new_head('moments', x)
+    _target_heads[key] = head                      # most recent last
+    while len(_target_heads) > 6:
+        _target_heads.pop(next(iter(_target_heads)))
+    _count('moments')
+    mean, srm = head.moments(x, mean=want_mean)
+    c = x.shape[-3]
+    lead = tuple(target.shape[:-3])
+    return (mean.view(*lead, c) if want_mean else None), srm.view(*lead, c, c)
+
+
+class _HeadLoss(torch.autograd.Function):
+    """A style head's unweighted loss.  Saved on the node: the input (autograd's version check stays in force) and the
+    head's per-call state, (Ssym, b) + the operand bound; the tap-sized gradient is made in backward() only."""
+
+    @staticmethod
+    def forward(ctx, input, module, kind, targets, eps, need_grad):
+        # need_grad: decided by the module (_wants_grad) - grad mode is always off in here, and ctx.needs_input_grad says
+        # input.requires_grad whatever the caller's grad mode is
+        x = _dense(input)
+        head = _module_head(module, kind, x)
+        loss, state = head.forward(x, targets, eps, need_grad=need_grad)
+        _count(kind)
+        if need_grad:
+            ctx.save_for_backward(input, state)
+            ctx.head = head                        # (the module may move on to another shape before this node's backward)
+            ctx.torch_forward = module._forward_torch
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        input, state = ctx.saved_tensors
+        if torch.is_grad_enabled():
+            return _torch_vjp(ctx.torch_forward, input, grad_output), None, None, None, None, None
+        grad = ctx.head.backward(_dense(input), state, grad_output.contiguous())
+        return grad.view(input.shape), None, None, None, None, None
+
+
+class _W2HeadLoss(_HeadLoss):
+    """StyleLossW2.forward (reference :174-181) on the library's head."""
+
+
+class _GramHeadLoss(_HeadLoss):
+    """StyleLoss.forward (reference :141-142) on the library's head."""
+
+
+class _MSELoss(torch.autograd.Function):
+    """nn.MSELoss (reference :119-126): st_op_mse_loss / st_op_mse_loss_backward."""
+
+    @staticmethod
+    def forward(ctx, input, target):
+        from . import _hip
+        loss = _hip.op_mse_loss(_dense(input), target)
+        _count('mse')
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(input, target)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        from . import _hip
+        input, target = ctx.saved_tensors
+        if torch.is_grad_enabled():
+            return _torch_vjp(lambda x: F.mse_loss(x, target), input, grad_output), None
+        return _hip.op_mse_loss_backward(_dense(input), target, grad_output.contiguous()).view(input.shape), None
+
+
+class _ScaledMSELoss(torch.autograd.Function):
+    """ScaledMSELoss.forward (reference :104-106): st_op_scaled_mse_loss; the two totals stay on the node for
+    st_op_scaled_mse_loss_backward."""
+
+    @staticmethod
+    def forward(ctx, input, target, module, eps):
+        from . import _hip
+        loss, totals = _hip.op_scaled_mse_loss(_dense(input), target, eps)
+        _count('scaled_mse')
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(input, target, totals)
+            ctx.torch_forward = lambda x: module._forward_torch(x, target)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        from . import _hip
+        input, target, totals = ctx.saved_tensors
+        if torch.is_grad_enabled():
+            return _torch_vjp(ctx.torch_forward, input, grad_output), None, None, None
+        grad = _hip.op_scaled_mse_loss_backward(_dense(input), target, totals, grad_output.contiguous())
+        return grad.view(input.shape), None, None, None
+
+
+class _TVLoss(torch.autograd.Function):
+    """TVLoss.forward (reference :187-195): st_op_tv_value / st_op_tv_loss_backward."""
+
+    @staticmethod
+    def forward(ctx, input, module):
+        from . import _hip
+        loss = _hip.op_tv_value(_dense(input))
+        _count('tv')
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(input)
+            ctx.torch_forward = module._forward_torch
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        from . import _hip
+        input, = ctx.saved_tensors
+        if torch.is_grad_enabled():
+            return _torch_vjp(ctx.torch_forward, input, grad_output), None
+        return _hip.op_tv_loss_backward(_dense(input), grad_output.contiguous()).view(input.shape), None
 
 
 class ScaledMSELoss(nn.Module):
@@ -30,9 +290,14 @@ class ScaledMSELoss(nn.Module):
     def extra_repr(self):
         return f'eps={self.eps:g}'
 
-    def forward(self, input, target):
+    def _forward_torch(self, input, target):
         delta = input - target
         return delta.pow(2).sum() / delta.abs().sum().add(self.eps)
+
+    def forward(self, input, target):
+        if native.enabled and eligible(input, 'scaled_mse', (target,)) and _buffer_ok(self.eps, input, 1):
+            return _ScaledMSELoss.apply(input, target, self, _eps_of(self))
+        return self._forward_torch(input, target)
 
 
 class _TargetLoss(nn.Module):
@@ -60,6 +325,11 @@ class ContentLossMSE(_TargetLoss):
     def __init__(self, target):
         super().__init__(target, nn.MSELoss())
 
+    def forward(self, input):
+        if native.enabled and eligible(input, 'mse', (self.target,)):
+            return _MSELoss.apply(input, self.target)
+        return self.loss(input, self.target)
+
 
 class StyleLoss(_TargetLoss):
     """Gram-matrix style loss (reference :129-142); the Gram matrix is divided by the number of positions."""
@@ -69,11 +339,22 @@ class StyleLoss(_TargetLoss):
 
     @staticmethod
     def get_target(target):
+        if native.enabled and eligible(target, 'moments') and not _wants_grad(target):
+            return _native_moments(target, False)[1]
+        return StyleLoss._get_target_torch(target)
+
+    @staticmethod
+    def _get_target_torch(target):
         flat = target.flatten(-2)
         return flat @ flat.transpose(-2, -1) / flat.shape[-1]
 
+    def _forward_torch(self, input):
+        return self.loss._forward_torch(self._get_target_torch(input), self.target)
+
     def forward(self, input):
-        return self.loss(self.get_target(input), self.target)
+        if native.enabled and eligible(input, 'gram', (self.target,)) and _buffer_ok(self.loss.eps, input, 1):
+            return _GramHeadLoss.apply(input, self, 'gram', (self.target,), _eps_of(self.loss), _wants_grad(input))
+        return self._forward_torch(input)
 
 
 def eye_like(x):
@@ -98,6 +379,12 @@ class StyleLossW2(nn.Module):
     def get_target(target):
         """(mean, second raw moment) over the spatial positions - linear in the features' distribution, so targets
         of several style images can be blended."""
+        if native.enabled and eligible(target, 'moments') and not _wants_grad(target):
+            return _native_moments(target, True)
+        return StyleLossW2._get_target_torch(target)
+
+    @staticmethod
+    def _get_target_torch(target):
         positions = target.shape[-2] * target.shape[-1]
         mean = target.mean([-2, -1])
         srm = torch.einsum('...chw,...dhw->...cd', target, target) / positions
@@ -108,7 +395,12 @@ class StyleLossW2(nn.Module):
         return srm - torch.einsum('...c,...d->...cd', mean, mean)
 
     def forward(self, input):
-        mean, srm = self.get_target(input)
+        if native.enabled and eligible(input, 'w2', (self.mean, self.cov, self.cov_sqrt)) and _buffer_ok(self.eps, input, 1):
+            return _W2HeadLoss.apply(input, self, 'w2', (self.mean, self.cov, self.cov_sqrt), _eps_of(self), _wants_grad(input))
+        return self._forward_torch(input)
+
+    def _forward_torch(self, input):
+        mean, srm = self._get_target_torch(input)
         cov = self.srm_to_cov(mean, srm) + eye_like(srm) * self.eps
         mean_term = torch.mean((mean - self.mean) ** 2)
         cross = self.sqrtm(self.cov_sqrt @ cov @ self.cov_sqrt)
@@ -120,6 +412,11 @@ class TVLoss(nn.Module):
     """L2 total variation over a nine-point stencil (reference :184-195; in the library: tv_interior_kernel)."""
 
     def forward(self, input):
+        if native.enabled and eligible(input, 'tv'):
+            return _TVLoss.apply(input, self)
+        return self._forward_torch(input)
+
+    def _forward_torch(self, input):
         x = F.pad(input, (1, 1, 1, 1), 'replicate')
         centre = x[..., 1:-1, 1:-1]
         right = (x[..., 1:-1, 2:] - centre).pow(2).mean() / 3
