@@ -164,7 +164,7 @@ int st_plan_set_taps(st_plan* plan, int n_content, const int* content_layers, in
 int st_plan_set_tap_weights(st_plan* plan, const float* content_weights, const float* style_weights, float tv_weight);
 
 /*
- * WHAT the terms are: one loss kind per list, for every layer of that list.
+ * WHAT the terms are: one loss kind per list, for every layer of that list (per layer: st_plan_set_layer_loss_kinds below).
  *   content_kind  0 (default)  ContentLossMSE (style_transfer.py:119-126): mean((F - T)^2)
  *                 1            ContentLoss (:109-116): ScaledMSELoss (:93-106) of the features,
  *                              sum d^2 / (sum |d| + 1e-8) with d = F - T
@@ -178,9 +178,44 @@ int st_plan_set_tap_weights(st_plan* plan, const float* content_weights, const f
  * (st_plan_term_losses).  The call drops every target set before (a style target is kept in the form its kind reads),
  * deals the heads' bound words again and invalidates a captured graph; the lists and all weights stay, and the kinds
  * survive a later st_plan_set_taps.  Fails for an unknown code, and on strip plans for any kind but the defaults.  Synchronous.
+ * Every eps returns to its kind's default (st_plan_set_loss_eps).  st_plan_loss_kinds reports -1 for a list whose entries
+ * differ (st_plan_set_layer_loss_kinds).
  */
 int st_plan_set_loss_kinds(st_plan* plan, int content_kind, int style_kind);
 int st_plan_loss_kinds(const st_plan* plan, int* content_kind, int* style_kind);
+
+/*
+ * The same per LAYER, as the reference builds one loss module per layer (style_transfer.py:425-429 the content modules,
+ * :442-453 the style modules): content_kinds[n_content] and style_kinds[n_style] hold the codes above in list order; a null
+ * pointer is allowed for an empty list.  Lists whose entries agree are st_plan_set_loss_kinds' setting, bit for bit.  A plan
+ * whose entries are all of the default kinds, with every eps at its default, stays on the closure it has; any other runs
+ * the general closure, each head by its own kind - a W2 head its Newton-Schulz chains, a Gram head its four launches - and
+ * each head allocates what its own kind needs.  Everything else is as for st_plan_set_loss_kinds: the call drops every
+ * target, deals the heads' bound words again, invalidates a captured graph and resets every eps; the lists and weights
+ * stay; a failed allocation leaves the plan as it was; strip plans take the defaults only.  A later st_plan_set_taps keeps
+ * the kind of a list whose entries agree and returns a mixed list to kind 0.  st_plan_layer_loss_kinds writes n_content /
+ * n_style codes (either pointer may be null).
+ * Order of configuration: layers (st_plan_set_taps), kinds, eps (st_plan_set_loss_eps), weights, then the targets.
+ */
+int st_plan_set_layer_loss_kinds(st_plan* plan, const int* content_kinds, const int* style_kinds);
+int st_plan_layer_loss_kinds(const st_plan* plan, int* content_kinds, int* style_kinds);
+
+/*
+ * The eps of each layer's loss module: content_eps[n_content], style_eps[n_style] in list order.
+ *   w2          StyleLossW2(target, eps=1e-4) (style_transfer.py:152): cov + eps I, in the target's covariance and root
+ *               (st_plan_set_style_target) and in the input's covariance of every closure
+ *   gram        StyleLoss(target, eps=1e-8) (:130) and
+ *   scaled_mse  ContentLoss(target, eps=1e-8) (:110): ScaledMSELoss's sum |d| + eps (:97,:103)
+ *   mse         ContentLossMSE (:119-126) has none
+ * A negative value means the kind's default, and so does a value equal to it as a float; a null pointer sets every entry
+ * of that list to its default.  Any other value runs the general closure, on the default lists too.  The call drops every
+ * target set before (a W2 target's root depends on its eps) and invalidates a captured graph; either kinds setter and
+ * st_plan_set_taps return every eps to the default, so set the eps after the kinds and before the targets.  Fails for a
+ * non-negative eps on an mse content entry, for a NaN or an infinity, and on strip plans for any value but the defaults.
+ * st_plan_loss_eps writes the effective values, -1 for an mse entry (either pointer may be null).
+ */
+int st_plan_set_loss_eps(st_plan* plan, const float* content_eps, const float* style_eps);
+int st_plan_loss_eps(const st_plan* plan, float* content_eps, float* style_eps);
 
 /* ContentLossMSE target (style_transfer.py:425-429): copies feat [512][H/8][W/8] into the plan (a configured plan: the
  * target of content layer 0, shaped like that layer). */
@@ -192,7 +227,8 @@ int st_plan_set_content_target_at(st_plan* plan, int index, const float* feat, v
  * StyleLossW2.__init__ (style_transfer.py:152-160) for style layer `index` of the configured list (default: 0..4 =
  * relu1_1..relu5_1): cov = srm - mean mean^T + 1e-4 I, cov_sqrt = sqrtm_ns(cov, 12) (sqrtm.py:9-25).
  * mean[C], srm[C*C] are the (already blended, :442-450) targets.
- * With style kind 1 (st_plan_set_loss_kinds) the target is StyleLoss.get_target's (:136-139): srm is stored as the Gram
+ * The 1e-4 is the layer's eps (st_plan_set_loss_eps).
+ * With style kind 1 on that layer (st_plan_set_loss_kinds, st_plan_set_layer_loss_kinds) the target is StyleLoss.get_target's (:136-139): srm is stored as the Gram
  * target G_t, mean is not read and no square root runs.
  */
 int st_plan_set_style_target(st_plan* plan, int index, const float* mean, const float* srm, void* stream);

@@ -448,14 +448,14 @@ int st_plan_set_style_target(st_plan* p, int index, const float* mean, const flo
                p->n_style);
     hipStream_t s = static_cast<hipStream_t>(stream);
     StyleHead& h = p->head[p->style_op[index]];
-    if (ensure_style_alloc(p, h)) return 1;
-    if (p->style_kind == 1) {           // StyleLoss.get_target (:136-139): the second raw moment IS the Gram target; no root
+    if (ensure_style_alloc(p, h, p->style_kind[index])) return 1;
+    if (p->style_kind[index] == 1) {    // StyleLoss.get_target (:136-139): the second raw moment IS the Gram target; no root
         ST_HIP(hipMemcpyAsync(h.gram_t, srm, (size_t)h.n * h.n * sizeof(float), hipMemcpyDeviceToDevice, s));
         h.target_set = true;
         return 0;
     }
     ST_HIP(hipMemcpyAsync(h.mean_t, mean, h.n * sizeof(float), hipMemcpyDeviceToDevice, s));
-    if (launch_cov_from_moments(mean, srm, h.cov_t, h.n, kCovEps, s)) return 1;
+    if (launch_cov_from_moments(mean, srm, h.cov_t, h.n, style_eps_of(p, index), s)) return 1;
     if (ns_sqrt_forward(h.cov_t, h.root_t, h.n, h.ns, s)) return 1;
     h.target_set = true;
     return 0;
@@ -557,7 +557,7 @@ int st_plan_moment_sums(st_plan* p, int layer, float* sums, void* stream) {
     for (int k = 0; k < p->n_style; ++k)
         if (kProgram[p->style_op[k]].feat_index == layer) idx = k;
     ST_REQUIRE(idx >= 0, "st_plan_moment_sums: features[%d] is not a style layer", layer);
-    if (ensure_style_alloc(p, p->head[p->style_op[idx]])) return 1;
+    if (ensure_style_alloc(p, p->head[p->style_op[idx]], p->style_kind[idx])) return 1;
     return moment_sums_of_tap(p, idx, sums, static_cast<hipStream_t>(stream));
 }
 

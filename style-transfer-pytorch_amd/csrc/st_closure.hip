@@ -373,12 +373,12 @@ int ensure_moment_alloc(st_plan* p, StyleHead& h) {
     return 0;
 }
 
-// ... and the rest by the plan's style kind: a Gram head (st_plan::style_kind == 1) holds its target and nothing else - no
-// covariance, no root, no Newton-Schulz workspace; a W2 head all of those
-int ensure_style_alloc(st_plan* p, StyleHead& h) {
+// ... and the rest by the style kind of the entry that lists the head: a Gram head (st_plan::style_kind[j] == 1) holds its
+// target and nothing else - no covariance, no root, no Newton-Schulz workspace; a W2 head all of those
+int ensure_style_alloc(st_plan* p, StyleHead& h, int kind) {
     if (ensure_moment_alloc(p, h)) return 1;
     const size_t nn = (size_t)h.n * h.n;
-    if (p->style_kind == 1) return h.gram_t ? 0 : plan_alloc(p, &h.gram_t, nn);
+    if (kind == 1) return h.gram_t ? 0 : plan_alloc(p, &h.gram_t, nn);
     if (h.w2_allocated) return 0;
     float** mats[] = {&h.cov_t, &h.root_t, &h.cov, &h.tmat, &h.mmat, &h.root, &h.gm, &h.dt, &h.dcov};
     for (float** m : mats)
@@ -420,6 +420,7 @@ HeadSite head_site(st_plan* p, int j) {
     at.h = &p->head[op];
     at.tap = &tap;
     at.weight = p->style_weight[j];
+    at.eps = style_eps_of(p, j);
     at.loss = p->losses + 1 + j;
     at.grad = tap.g;
     at.grad_amax = tap.g_amax;
@@ -441,7 +442,7 @@ int moments_of_tap(st_plan* p, const HeadSite& at, float* mean_out, float* srm_o
             launch_gram_partial(tap.y, h.n, h.npix_local, splits, h.gram, s,
                                 (p->net->conv_elem == 1 && !gram_f32.get()) ? tap.y_amax : nullptr))
             return 1;
-        return launch_gram_finalize(h.gram, h.n, h.npix, splits, mean_out, srm_out, s, cov_out, kCovEps);
+        return launch_gram_finalize(h.gram, h.n, h.npix, splits, mean_out, srm_out, s, cov_out, at.eps);
     };
     // relu1_1's Gram (C = 64) reads its tap once and has 64 MACs per element on the 16-bit pipe: HBM-bound
     if (idx == 0 && !fused) return hbm_profiled(p, HBM_GRAM1, 4.0 * h.n * (double)h.npix_local, s, gram);
@@ -502,7 +503,7 @@ int style_head_chain(st_plan* p, const HeadSite& at, hipStream_t s, bool cov_rea
     hipEvent_t* tlh = idx == 4 ? p->tl_h4 : p->tl_h3;
     if (tl) ST_HIP(hipEventRecord(tlh[0], s));
     // (cov_ready: the Gram kernel's finalize pass wrote the covariance along with the moments)
-    if (!cov_ready && launch_cov_from_moments(h.mean, h.srm, h.cov, n, kCovEps, s)) return 1;
+    if (!cov_ready && launch_cov_from_moments(h.mean, h.srm, h.cov, n, at.eps, s)) return 1;
     // sqrt_term = sqrtm(cov_sqrt @ cov @ cov_sqrt)                       (style_transfer.py:179)
     if (launch_gemm_batch(one_gemm(n, h.root_t, h.cov, h.tmat, 0, 0), s)) return 1;
     // (n = 512: the Frobenius norms the two chains open with - of M and of the root, sqrtm.py:16,38 - come out of the
@@ -560,7 +561,7 @@ int style_heads_shallow_lockstep(st_plan* p, hipStream_t s, const int* idx, int 
         n[l] = h[l]->n;
         ST_HIP(hipStreamWaitEvent(s, defer ? p->aux_fwd : p->tap_ready[idx[l]], 0));
         if (moments_of_tap(p, at[l], h[l]->mean, h[l]->srm, s, with_cov ? h[l]->cov : nullptr)) return 1;
-        if (!with_cov && launch_cov_from_moments(h[l]->mean, h[l]->srm, h[l]->cov, n[l], kCovEps, s)) return 1;
+        if (!with_cov && launch_cov_from_moments(h[l]->mean, h[l]->srm, h[l]->cov, n[l], at[l].eps, s)) return 1;
     }
     auto batch3 = [&](auto make) {
         GemmBatch g{};

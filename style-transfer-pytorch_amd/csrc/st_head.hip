@@ -10,7 +10,7 @@
 // What the plan knows and a head must find out: the operand bound of the fp16x3 kernels.  A trunk kernel leaves max |y| of the
 // tap it writes; here the tensor is whatever autograd hands over - signed, possibly all zeros (bound 0: scale_exp gives 2^0,
 // the planes are exact zeros and the bias term alone makes the result) - so launch_amax measures it, once per forward, into
-// the per-call state that the backward reads.  eps is the module's, where the plan passes kCovEps / kScaledMseEps.
+// the per-call state that the backward reads.  eps is the module's, where the plan passes its entry's (kCovEps / kScaledMseEps by default).
 #include <cstdint>
 #include <vector>
 

@@ -59,7 +59,7 @@ struct StyleHead {
     float *mean = nullptr, *srm = nullptr, *cov = nullptr, *tmat = nullptr, *mmat = nullptr, *root = nullptr,
           *gm = nullptr, *dt = nullptr, *dcov = nullptr, *ssym = nullptr, *bvec = nullptr, *gdiag = nullptr;
     float* conv_scratch = nullptr;     // split-K workspace of the head's 1x1 gradient conv (small taps only)
-    float* gram_t = nullptr;           // Gram kind (st_plan::style_kind == 1): the target Gram matrix [n][n]
+    float* gram_t = nullptr;           // Gram kind (st_plan::style_kind[j] == 1): the target Gram matrix [n][n]
     NSWorkspace ns{};
     GramWorkspace gram{};
     bool allocated = false;            // what every kind needs: the moments, their workspace, (Ssym, b), the 1x1 step's scratch
@@ -72,6 +72,7 @@ struct HeadSite {
     StyleHead* h = nullptr;
     const Node* tap = nullptr;       // the tap's node (a conv's ReLU output or a pooled map)
     float weight = 0.f;
+    float eps = kCovEps;             // the entry's eps (style_eps_of): W2's covariance eps, a Gram head's ScaledMSELoss eps
     float* loss = nullptr;           // device word of the weighted loss term
     float* grad = nullptr;           // dF is WRITTEN here: the tap's gradient buffer, or its seed buffer (general closure)
     unsigned int* grad_amax = nullptr;   // fp16x3: bound of what is written (null: whoever consumes it next commits one)
@@ -143,10 +144,14 @@ struct st_plan {
     float content_weight[16] = {0.015f};             // per LISTED entry
     float style_weight[16] = {256.f / 341, 64.f / 341, 16.f / 341, 4.f / 341, 1.f / 341};
     float tv_weight = 2.0f;
-    // WHAT the terms are, one kind per list (st_plan_set_loss_kinds): content 0 = ContentLossMSE, 1 = ContentLoss (the features
-    // under ScaledMSELoss); style 0 = StyleLossW2, 1 = StyleLoss (the Gram matrix under ScaledMSELoss).  Any non-default kind
-    // runs the general closure (general_taps), on the reference's lists too.
-    int content_kind = 0, style_kind = 0;
+    // WHAT the terms are, one kind per LISTED entry (st_plan_set_loss_kinds for a whole list, st_plan_set_layer_loss_kinds per
+    // entry): content 0 = ContentLossMSE, 1 = ContentLoss (the features under ScaledMSELoss); style 0 = StyleLossW2,
+    // 1 = StyleLoss (the Gram matrix under ScaledMSELoss).  And the entry's eps (st_plan_set_loss_eps): negative = the kind's
+    // default (kCovEps for w2, kScaledMseEps for gram and scaled_mse; mse has none), which is also what a value equal to the
+    // default is stored as.  Any non-default kind or eps runs the general closure (general_taps), on the reference's lists too.
+    int content_kind[16] = {}, style_kind[16] = {};
+    float content_eps[16] = {-1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f};
+    float style_eps[16] = {-1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f};
     float* kind_scratch = nullptr;                   // non-default kinds: [2 kStreamBlocks] per-block (sum d^2, sum |d|) of the
                                                      // term in flight, then [2] per term: sum d^2, sum |d| + eps (kind_totals)
     st::StyleHead head[st::kNumOps];                 // n / npix / npix_local of all 17 filled at create, buffers on first use;
@@ -305,7 +310,7 @@ int hbm_profiled(st_plan* p, int cat, double bytes, hipStream_t s, F&& launch) {
 void invalidate_graph(st_plan* p);
 int ensure_streams(st_plan* p, hipStream_t caller = nullptr);
 int ensure_moment_alloc(st_plan* p, StyleHead& h);      // what st_plan_moments needs (StyleHead::allocated)
-int ensure_style_alloc(st_plan* p, StyleHead& h);       // ... and what a head of the plan's style kind needs
+int ensure_style_alloc(st_plan* p, StyleHead& h, int kind);   // ... and what a head of that style kind needs
 int ensure_grad_alloc(st_plan* p);
 HeadSite head_site(st_plan* p, int j);
 int moments_of_tap(st_plan* p, const HeadSite& at, float* mean_out, float* srm_out, hipStream_t s, float* cov_out = nullptr);
@@ -335,6 +340,8 @@ int tap_position(int layer);          // kProgram position of features[layer], -
 int closure_top_op(const st_plan* p); // the deepest kProgram position the plan's closure runs
 bool targets_ready(const st_plan* p);
 float* loss_terms(st_plan* p);        // the array the closure's weighted terms go to, in SumLoss order
+float style_eps_of(const st_plan* p, int j);   // effective eps of style entry j / content entry i (mse: -1)
+float content_eps_of(const st_plan* p, int i);
 
 // ---- st_strip.hip
 int halo_alloc(st_plan* p, float** out, size_t floats);

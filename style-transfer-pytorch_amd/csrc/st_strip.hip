@@ -437,7 +437,7 @@ int st_plan_closure_begin(st_plan* p, const float* image, float* grad_out) {
     ST_REQUIRE(p->strip, "st_plan_closure_begin: not a strip plan (use st_plan_create_strip)");
     if (require_targets(p) || ensure_grad_alloc(p)) return 1;
     for (int k = 0; k < p->n_style; ++k)
-        if (ensure_style_alloc(p, p->head[p->style_op[k]])) return 1;
+        if (ensure_style_alloc(p, p->head[p->style_op[k]], /*kind=*/0)) return 1;
     // (the tile / overlap / ownership decisions of the phase sequence depend on the library's switches)
     if (p->ph_image != image || p->ph_grad != grad_out || p->ph_last_layer != -1 || p->phases.empty() ||
         p->ph_option_gen != option_generation()) {

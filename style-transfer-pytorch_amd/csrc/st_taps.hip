@@ -20,15 +20,19 @@
 // run_tap_backward's, unchanged.  ST_GENERAL_TAPS=1 (st_set_option) sends the reference's configuration down this path too, so
 // that it can be compared with the default closure on the same plan.
 //
-// Loss kinds (st_plan_set_loss_kinds): one kind per list says WHAT the terms are.  The defaults - ContentLossMSE, StyleLossW2 -
-// are the lines above.  Kind 1 of either list is the reference's ScaledMSELoss (st_pointwise.hip has the formulas), on the
-// features (ContentLoss) or on the Gram matrix (StyleLoss); any non-default kind runs this closure, the reference's lists too:
+// Loss kinds (st_plan_set_loss_kinds for a whole list, st_plan_set_layer_loss_kinds per entry): a kind per LISTED entry says
+// WHAT its term is, as the reference builds one module per layer.  The defaults - ContentLossMSE, StyleLossW2 - are the lines
+// above.  Kind 1 of either list is the reference's ScaledMSELoss (st_pointwise.hip has the formulas), on the features
+// (ContentLoss) or on the Gram matrix (StyleLoss).  Each entry also has its module's eps (st_plan_set_loss_eps): W2's
+// covariance eps, in the target's root and the input's covariance, or ScaledMSELoss's, in the sums.  Any non-default kind
+// or eps on any entry runs this closure, the reference's lists too, and every head runs by its own entry's kind:
 //   a Gram head             the tap's second raw moment (moments_of_tap: no mean, no covariance), the sums and the term, then
 //                           Ssym = (w / N) (D + D^T) with a zero b, and the W2 heads' own 1x1 step dF = Ssym F into the seed
 //                           buffer (gram_head: four launches, no Newton-Schulz chain)
 //   a scaled-MSE content term   the sums and the term, then the seed written or added  (launch_scaled_mse_sums / _grad)
 // Everything around the terms - TV, the forward, the terms' total, the tap backward, the step's fold - is unchanged.
 #include <algorithm>
+#include <cmath>
 
 #include "st_plan.h"
 
@@ -39,6 +43,24 @@ namespace {
 constexpr int kContentFeat = 22;
 const int kStyleFeat[5] = {1, 6, 11, 20, 29};
 const float kStyleWeight[5] = {256.f / 341, 64.f / 341, 16.f / 341, 4.f / 341, 1.f / 341};
+
+// the kind of a list of n entries: the one they agree on (an empty list: what a later entry would get), -1: they differ
+int list_kind(const int* kinds, int n) {
+    for (int i = 1; i < n; ++i)
+        if (kinds[i] != kinds[0]) return -1;
+    return kinds[0];
+}
+
+// every target set before is gone, every bound word is dealt again, and nothing built on the former terms survives
+void drop_targets(st_plan* p) {
+    for (int op = 0; op < kNumOps; ++op) {
+        p->head[op].target_set = false;
+        p->content_set[op] = false;
+    }
+    assign_head_bounds(p);
+    invalidate_graph(p);
+    p->phases.clear();
+}
 }  // namespace
 
 int tap_position(int layer) {
@@ -47,9 +69,31 @@ int tap_position(int layer) {
     return -1;
 }
 
+// every listed entry is of the default kind (ContentLossMSE / StyleLossW2) ... and has its kind's default eps
+static bool default_kinds(const st_plan* p) {
+    bool ok = true;
+    for (int i = 0; i < p->n_content; ++i) ok = ok && p->content_kind[i] == 0;
+    for (int j = 0; j < p->n_style; ++j) ok = ok && p->style_kind[j] == 0;
+    return ok;
+}
+static bool default_eps(const st_plan* p) {
+    bool ok = true;
+    for (int i = 0; i < p->n_content; ++i) ok = ok && p->content_eps[i] < 0.f;
+    for (int j = 0; j < p->n_style; ++j) ok = ok && p->style_eps[j] < 0.f;
+    return ok;
+}
+
 bool general_taps(const st_plan* p) {
     static Option force("ST_GENERAL_TAPS", 0);
-    return !p->strip && (!p->reference_taps || p->content_kind != 0 || p->style_kind != 0 || force.get() != 0);
+    return !p->strip && (!p->reference_taps || !default_kinds(p) || !default_eps(p) || force.get() != 0);
+}
+
+float style_eps_of(const st_plan* p, int j) {
+    return p->style_eps[j] >= 0.f ? p->style_eps[j] : p->style_kind[j] == 1 ? kScaledMseEps : kCovEps;
+}
+
+float content_eps_of(const st_plan* p, int i) {
+    return p->content_kind[i] == 0 ? -1.f : p->content_eps[i] >= 0.f ? p->content_eps[i] : kScaledMseEps;
 }
 
 int closure_top_op(const st_plan* p) {
@@ -92,7 +136,8 @@ int gram_head(st_plan* p, const HeadSite& at, int term, hipStream_t s) {
     StyleHead& h = *at.h;
     if (moments_of_tap(p, at, h.mean, h.srm, s)) return 1;
     float* totals = kind_totals(p, term);
-    if (launch_scaled_mse_sums(h.srm, h.gram_t, (long long)h.n * h.n, at.weight, p->kind_scratch, totals, at.loss, s, p->tickets + 128))
+    if (launch_scaled_mse_sums(h.srm, h.gram_t, (long long)h.n * h.n, at.weight, p->kind_scratch, totals, at.loss, s, p->tickets + 128,
+                               at.eps))
         return 1;
     if (launch_gram_grad_finish(h.srm, h.gram_t, totals, h.n, at.weight, h.npix, h.ssym, h.bvec, s,
                                 p->net->conv_elem == 1 ? h.s_amax : nullptr))
@@ -102,7 +147,7 @@ int gram_head(st_plan* p, const HeadSite& at, int term, hipStream_t s) {
 
 // seed buffers of the tapped positions and the terms' array
 int ensure_tap_buffers(st_plan* p) {
-    if ((p->content_kind != 0 || p->style_kind != 0) && !p->kind_scratch &&
+    if (!default_kinds(p) && !p->kind_scratch &&
         plan_alloc(p, &p->kind_scratch, 2 * kStreamBlocks + 2 * 32))
         return 1;
     if (!p->terms) {
@@ -137,19 +182,19 @@ int general_loss_and_grad(st_plan* p, const float* image, float* grad_out, float
     bool styled[kNumOps] = {};
     for (int k = 0; k < ns; ++k) {
         const HeadSite at = general_head_site(p, order[k]);
-        if (p->style_kind == 1 ? gram_head(p, at, nc + order[k], s) : style_head(p, at, s)) return 1;
+        if (p->style_kind[order[k]] == 1 ? gram_head(p, at, nc + order[k], s) : style_head(p, at, s)) return 1;
         styled[p->style_op[order[k]]] = true;
     }
     // ContentLossMSE per content layer (style_transfer.py:425-429), behind the style head of the same layer where there is one;
-    // kind 1: ContentLoss, its sums and then its seed
+    // an entry of kind 1: ContentLoss, its sums and then its seed
     for (int i = 0; i < nc; ++i) {
         const int op = p->content_op[i];
         const Node& ct = node_at(p, op);
-        if (p->content_kind == 1) {
+        if (p->content_kind[i] == 1) {
             float* totals = kind_totals(p, i);
             if (hbm_profiled(p, HBM_CONTENT, 2.0 * 4.0 * ct.count(), s, [&] {
                     return launch_scaled_mse_sums(ct.y, p->content_target[op], (long long)ct.count(), p->content_weight[i],
-                                                  p->kind_scratch, totals, terms + i, s, p->tickets + 128);
+                                                  p->kind_scratch, totals, terms + i, s, p->tickets + 128, content_eps_of(p, i));
                 }) ||
                 hbm_profiled(p, HBM_CONTENT, (styled[op] ? 4.0 : 3.0) * 4.0 * ct.count(), s, [&] {
                     return launch_scaled_mse_grad(ct.y, p->content_target[op], (long long)ct.count(), p->content_weight[i], totals,
@@ -210,8 +255,11 @@ int st_plan_set_taps(st_plan* p, int n_content, const int* content_layers, int n
     // allocates when their targets are set): a failed allocation leaves the plan as it was
     for (int i = 0; i < n_content; ++i)
         if (!p->content_target[cop[i]] && plan_alloc(p, &p->content_target[cop[i]], node_at(p, cop[i]).count())) return 1;
+    // (the kinds: a list whose entries agree keeps that kind for its new entries, a mixed one returns to kind 0; every eps
+    // returns to its kind's default)
+    const int ckind = std::max(list_kind(p->content_kind, p->n_content), 0), skind = std::max(list_kind(p->style_kind, p->n_style), 0);
     for (int j = 0; j < n_style; ++j)
-        if (ensure_style_alloc(p, p->head[sop[j]])) return 1;
+        if (ensure_style_alloc(p, p->head[sop[j]], skind)) return 1;
     // the weights: the reference's lists named again keep theirs; every other change of lists starts from the new lists'
     // defaults - the reference's content_weight split over the layers (:366) and equal style weights, or, for the reference's
     // own lists, its own style weights
@@ -222,21 +270,39 @@ int st_plan_set_taps(st_plan* p, int n_content, const int* content_layers, int n
     for (int i = 0; i < 16; ++i) {
         p->content_op[i] = i < n_content ? cop[i] : 0;
         p->style_op[i] = i < n_style ? sop[i] : 0;
+        p->content_kind[i] = ckind;
+        p->style_kind[i] = skind;
+        p->content_eps[i] = p->style_eps[i] = -1.f;
         if (keep_weights) continue;
         p->content_weight[i] = i < n_content ? 0.015f / (float)n_content : 0.f;
         p->style_weight[i] = i >= n_style ? 0.f : ref ? kStyleWeight[i] : 1.f / (float)n_style;
     }
     // a head or target buffer serves whichever lists name its position: every target set before is gone, every bound word
     // is dealt again, and nothing built on the former lists survives
-    for (int op = 0; op < kNumOps; ++op) {
-        p->head[op].target_set = false;
-        p->content_set[op] = false;
-    }
-    assign_head_bounds(p);
-    invalidate_graph(p);
-    p->phases.clear();
+    drop_targets(p);
     return 0;
 }
+
+namespace {
+
+// what both kinds setters do once the codes are checked: `ck` / `sk` hold 16 codes each, the listed entries first
+int apply_loss_kinds(st_plan* p, const int* ck, const int* sk) {
+    // what the listed heads need under their new kinds, now: a failed allocation leaves the plan as it was
+    for (int j = 0; j < p->n_style; ++j)
+        if (ensure_style_alloc(p, p->head[p->style_op[j]], sk[j])) return 1;
+    for (int i = 0; i < 16; ++i) {
+        p->content_kind[i] = ck[i];
+        p->style_kind[i] = sk[i];
+        p->content_eps[i] = p->style_eps[i] = -1.f;      // an eps belongs to a module of one kind: set it after the kinds
+    }
+    // a target is kept in the form its kind reads (a root, or a Gram matrix): as after st_plan_set_taps, every target set
+    // before is gone, every bound word is dealt again and nothing built on the former terms survives.  The lists and all
+    // weights stay.
+    drop_targets(p);
+    return 0;
+}
+
+}  // namespace
 
 int st_plan_set_loss_kinds(st_plan* p, int content_kind, int style_kind) {
     ST_REQUIRE(p, "st_plan_set_loss_kinds: null plan");
@@ -246,32 +312,89 @@ int st_plan_set_loss_kinds(st_plan* p, int content_kind, int style_kind) {
                "st_plan_set_loss_kinds: unknown style loss kind %d (0: w2 - StyleLossW2, 1: gram - StyleLoss)", style_kind);
     ST_REQUIRE(!p->strip || (content_kind == 0 && style_kind == 0),
                "st_plan_set_loss_kinds: strip plans run the default loss kinds only (content mse, style w2)");
-    // what the listed heads need under the new kind, now: a failed allocation leaves the plan as it was
-    const int former = p->style_kind;
-    p->style_kind = style_kind;
-    for (int j = 0; j < p->n_style; ++j)
-        if (ensure_style_alloc(p, p->head[p->style_op[j]])) {
-            p->style_kind = former;
-            return 1;
-        }
-    p->content_kind = content_kind;
-    // a target is kept in the form its kind reads (a root, or a Gram matrix): as after st_plan_set_taps, every target set
-    // before is gone, every bound word is dealt again and nothing built on the former terms survives.  The lists and all
-    // weights stay.
-    for (int op = 0; op < kNumOps; ++op) {
-        p->head[op].target_set = false;
-        p->content_set[op] = false;
-    }
-    assign_head_bounds(p);
-    invalidate_graph(p);
-    p->phases.clear();
-    return 0;
+    int ck[16], sk[16];
+    std::fill(ck, ck + 16, content_kind);
+    std::fill(sk, sk + 16, style_kind);
+    return apply_loss_kinds(p, ck, sk);
 }
 
 int st_plan_loss_kinds(const st_plan* p, int* content_kind, int* style_kind) {
     ST_REQUIRE(p, "st_plan_loss_kinds: null plan");
-    if (content_kind) *content_kind = p->content_kind;
-    if (style_kind) *style_kind = p->style_kind;
+    if (content_kind) *content_kind = list_kind(p->content_kind, p->n_content);
+    if (style_kind) *style_kind = list_kind(p->style_kind, p->n_style);
+    return 0;
+}
+
+int st_plan_set_layer_loss_kinds(st_plan* p, const int* content_kinds, const int* style_kinds) {
+    ST_REQUIRE(p, "st_plan_set_layer_loss_kinds: null plan");
+    ST_REQUIRE((p->n_content == 0 || content_kinds) && (p->n_style == 0 || style_kinds), "st_plan_set_layer_loss_kinds: null list");
+    int ck[16], sk[16];
+    bool all_default = true;
+    for (int i = 0; i < p->n_content; ++i) {
+        ST_REQUIRE(content_kinds[i] == 0 || content_kinds[i] == 1,
+                   "st_plan_set_layer_loss_kinds: unknown content loss kind %d for content layer %d (0: mse - ContentLossMSE, "
+                   "1: scaled_mse - ContentLoss)", content_kinds[i], i);
+        ck[i] = content_kinds[i];
+        all_default = all_default && ck[i] == 0;
+    }
+    for (int j = 0; j < p->n_style; ++j) {
+        ST_REQUIRE(style_kinds[j] == 0 || style_kinds[j] == 1,
+                   "st_plan_set_layer_loss_kinds: unknown style loss kind %d for style layer %d (0: w2 - StyleLossW2, 1: gram - StyleLoss)",
+                   style_kinds[j], j);
+        sk[j] = style_kinds[j];
+        all_default = all_default && sk[j] == 0;
+    }
+    ST_REQUIRE(!p->strip || all_default,
+               "st_plan_set_layer_loss_kinds: strip plans run the default loss kinds only (content mse, style w2)");
+    // the unlisted entries: what st_plan_set_loss_kinds would leave there for a list whose entries agree (an empty list keeps
+    // what it has), kind 0 for a mixed one
+    const int cu = p->n_content ? std::max(list_kind(ck, p->n_content), 0) : p->content_kind[0];
+    const int su = p->n_style ? std::max(list_kind(sk, p->n_style), 0) : p->style_kind[0];
+    std::fill(ck + p->n_content, ck + 16, cu);
+    std::fill(sk + p->n_style, sk + 16, su);
+    return apply_loss_kinds(p, ck, sk);
+}
+
+int st_plan_layer_loss_kinds(const st_plan* p, int* content_kinds, int* style_kinds) {
+    ST_REQUIRE(p, "st_plan_layer_loss_kinds: null plan");
+    for (int i = 0; content_kinds && i < p->n_content; ++i) content_kinds[i] = p->content_kind[i];
+    for (int j = 0; style_kinds && j < p->n_style; ++j) style_kinds[j] = p->style_kind[j];
+    return 0;
+}
+
+int st_plan_set_loss_eps(st_plan* p, const float* content_eps, const float* style_eps) {
+    ST_REQUIRE(p, "st_plan_set_loss_eps: null plan");
+    float ce[16], se[16];
+    std::fill(ce, ce + 16, -1.f);
+    std::fill(se, se + 16, -1.f);
+    bool all_default = true;
+    for (int pass = 0; pass < 2; ++pass) {
+        const float* given = pass ? style_eps : content_eps;
+        const int n = pass ? p->n_style : p->n_content;
+        for (int i = 0; given && i < n; ++i) {
+            const float e = given[i];
+            ST_REQUIRE(std::isfinite(e), "st_plan_set_loss_eps: eps of %s layer %d is not finite", pass ? "style" : "content", i);
+            if (e < 0.f) continue;                   // negative: the kind's default
+            ST_REQUIRE(pass || p->content_kind[i] != 0,
+                       "st_plan_set_loss_eps: content layer %d is of kind mse (ContentLossMSE), which has no eps: pass a negative value", i);
+            const float dflt = pass ? (p->style_kind[i] == 1 ? kScaledMseEps : kCovEps) : kScaledMseEps;
+            if (e == dflt) continue;                 // the default, given as a number, IS the default
+            (pass ? se : ce)[i] = e;
+            all_default = false;
+        }
+    }
+    ST_REQUIRE(!p->strip || all_default, "st_plan_set_loss_eps: strip plans run the loss modules' default eps only");
+    std::copy(ce, ce + 16, p->content_eps);
+    std::copy(se, se + 16, p->style_eps);
+    // a W2 target is kept as the root of cov_t + eps I: every target set before is gone
+    drop_targets(p);
+    return 0;
+}
+
+int st_plan_loss_eps(const st_plan* p, float* content_eps, float* style_eps) {
+    ST_REQUIRE(p, "st_plan_loss_eps: null plan");
+    for (int i = 0; content_eps && i < p->n_content; ++i) content_eps[i] = content_eps_of(p, i);
+    for (int j = 0; style_eps && j < p->n_style; ++j) style_eps[j] = style_eps_of(p, j);
     return 0;
 }
 

@@ -69,6 +69,10 @@ def _declare(lib):
         'st_plan_set_tap_weights': (i32, [vp, ctypes.POINTER(f32), ctypes.POINTER(f32), f32]),
         'st_plan_set_loss_kinds': (i32, [vp, i32, i32]),
         'st_plan_loss_kinds': (i32, [vp, ip, ip]),
+        'st_plan_set_layer_loss_kinds': (i32, [vp, ip, ip]),
+        'st_plan_layer_loss_kinds': (i32, [vp, ip, ip]),
+        'st_plan_set_loss_eps': (i32, [vp, ctypes.POINTER(f32), ctypes.POINTER(f32)]),
+        'st_plan_loss_eps': (i32, [vp, ctypes.POINTER(f32), ctypes.POINTER(f32)]),
         'st_plan_set_content_target_at': (i32, [vp, i32, vp, vp]),
         'st_plan_term_losses': (i32, [vp, pp, ip]),
         'st_plan_loss_and_grad': (i32, [vp, vp, vp, vp, vp]),
@@ -270,7 +274,8 @@ class Plan:
     forward_count = 0
     # the configured layers (set_taps); strip plans keep the default
     content_layers, style_layers = DEFAULT_CONTENT_LAYERS, DEFAULT_STYLE_LAYERS
-    # the lists' loss kinds (set_loss_kinds)
+    # the lists' loss kinds (set_loss_kinds): the name while a list's layers agree, the tuple of names once they differ
+    # (set_layer_loss_kinds); per layer: content_losses / style_losses
     content_loss, style_loss = CONTENT_LOSSES[0], STYLE_LOSSES[0]
 
     def __init__(self, net, height, width):
@@ -305,6 +310,7 @@ class Plan:
         with torch.cuda.device(self.device):
             _check(self.lib.st_plan_set_taps(self.handle, len(content_layers), ca, len(style_layers), sa))
         self.content_layers, self.style_layers = content_layers, style_layers
+        self._read_loss_kinds()         # (a mixed list has returned to its default kind)
 
     def set_loss_kinds(self, content='mse', style='w2'):
         """What the terms are, one kind per list (st_plan_set_loss_kinds): ``content`` one of ``CONTENT_LOSSES`` - 'mse'
@@ -318,6 +324,78 @@ class Plan:
         with torch.cuda.device(self.device):
             _check(self.lib.st_plan_set_loss_kinds(self.handle, CONTENT_LOSSES.index(content), STYLE_LOSSES.index(style)))
         self.content_loss, self.style_loss = content, style
+
+    def set_layer_loss_kinds(self, content, style):
+        """The same per layer (st_plan_set_layer_loss_kinds): one name of ``CONTENT_LOSSES`` per content layer and one of
+        ``STYLE_LOSSES`` per style layer, in list order.  Lists whose names agree are ``set_loss_kinds``' setting; on any
+        other, every head runs by its own kind in the general closure, and ``content_loss`` / ``style_loss`` become the
+        tuple.  Drops every target and returns every eps to its default."""
+        content, style = list(content), list(style)
+        if len(content) != len(self.content_layers) or len(style) != len(self.style_layers):
+            raise ValueError(f'{len(content)} content and {len(style)} style loss kinds for {len(self.content_layers)} content and '
+                             f'{len(self.style_layers)} style layers: one per layer')
+        for name in content:
+            if name not in CONTENT_LOSSES:
+                raise ValueError(f'content loss {name!r}: must be one of {CONTENT_LOSSES}')
+        for name in style:
+            if name not in STYLE_LOSSES:
+                raise ValueError(f'style loss {name!r}: must be one of {STYLE_LOSSES}')
+        ca = (ctypes.c_int * max(len(content), 1))(*[CONTENT_LOSSES.index(name) for name in content])
+        sa = (ctypes.c_int * max(len(style), 1))(*[STYLE_LOSSES.index(name) for name in style])
+        with torch.cuda.device(self.device):
+            _check(self.lib.st_plan_set_layer_loss_kinds(self.handle, ca, sa))
+        self._read_loss_kinds()
+
+    def set_loss_eps(self, content=None, style=None):
+        """The eps of each layer's loss module (st_plan_set_loss_eps): per list None (every layer's default), a number
+        (every layer) or a sequence with a number or None per layer.  The defaults are the reference's constructors': 1e-4
+        for 'w2', 1e-8 for 'gram' and 'scaled_mse'; 'mse' has none.  Anything but the defaults runs the general closure;
+        drops every target.  Either kinds setter and ``set_taps`` return every eps to its default: kinds first, then eps,
+        then the targets."""
+        arrays = []
+        for given, layers, what in ((content, self.content_layers, 'content'), (style, self.style_layers, 'style')):
+            if given is None or isinstance(given, (int, float)):
+                given = [given] * len(layers)
+            given = list(given)
+            if len(given) != len(layers):
+                raise ValueError(f'{len(given)} {what} eps for {len(layers)} {what} layers: one per layer')
+            for v in given:
+                if v is not None and not float(v) >= 0:
+                    raise ValueError(f'{what} eps {v!r}: must be None or a non-negative number')
+            arrays.append((ctypes.c_float * max(len(given), 1))(*[-1.0 if v is None else float(v) for v in given]))
+        with torch.cuda.device(self.device):
+            _check(self.lib.st_plan_set_loss_eps(self.handle, *arrays))
+
+    def _layer_values(self, entry, ctype):
+        ca, sa = (ctype * max(len(self.content_layers), 1))(), (ctype * max(len(self.style_layers), 1))()
+        _check(entry(self.handle, ca, sa))
+        return tuple(ca[:len(self.content_layers)]), tuple(sa[:len(self.style_layers)])
+
+    def _read_loss_kinds(self):
+        c, s = ctypes.c_int(), ctypes.c_int()
+        _check(self.lib.st_plan_loss_kinds(self.handle, ctypes.byref(c), ctypes.byref(s)))
+        self.content_loss = CONTENT_LOSSES[c.value] if c.value >= 0 else self.content_losses
+        self.style_loss = STYLE_LOSSES[s.value] if s.value >= 0 else self.style_losses
+
+    @property
+    def content_losses(self):
+        """The loss kind of each content layer, a tuple of names (st_plan_layer_loss_kinds)."""
+        return tuple(CONTENT_LOSSES[k] for k in self._layer_values(self.lib.st_plan_layer_loss_kinds, ctypes.c_int)[0])
+
+    @property
+    def style_losses(self):
+        """The loss kind of each style layer."""
+        return tuple(STYLE_LOSSES[k] for k in self._layer_values(self.lib.st_plan_layer_loss_kinds, ctypes.c_int)[1])
+
+    @property
+    def content_eps(self):
+        """The effective eps of each content layer's module (st_plan_loss_eps), None for an 'mse' layer."""
+        return tuple(None if v < 0 else v for v in self._layer_values(self.lib.st_plan_loss_eps, ctypes.c_float)[0])
+
+    @property
+    def style_eps(self):
+        """The effective eps of each style layer's module."""
+        return self._layer_values(self.lib.st_plan_loss_eps, ctypes.c_float)[1]
 
     def term_losses(self):
         """The weighted terms of the last closure in SumLoss order - content layers, style layers, tv - as a device tensor

@@ -292,17 +292,46 @@ def build_parser():
                         "torch hub cache)")
     p.add_argument('--precision', type=str, default='fp16x3', choices=['fp16x3', 'bf16x6', 'fp32', 'bf16x3'],
                    help='arithmetic of the 3x3 trunk convolutions')
-    p.add_argument('--content-loss', type=str, default='mse', choices=['mse', 'scaled_mse'],
-                   help="the content term: 'mse' (ContentLossMSE) or 'scaled_mse' (ContentLoss: sum d^2 / sum |d|)")
-    p.add_argument('--style-loss', type=str, default='w2', choices=['w2', 'gram'],
-                   help="the style term: 'w2' (StyleLossW2) or 'gram' (StyleLoss: the scaled MSE of Gram matrices)")
+    p.add_argument('--content-loss', type=_loss_names(['mse', 'scaled_mse']), default='mse', metavar='{mse,scaled_mse}[,...]',
+                   help="the content term: 'mse' (ContentLossMSE) or 'scaled_mse' (ContentLoss: sum d^2 / sum |d|); "
+                        'a comma-separated list gives one per content layer')
+    p.add_argument('--style-loss', type=_loss_names(['w2', 'gram']), default='w2', metavar='{w2,gram}[,...]',
+                   help="the style term: 'w2' (StyleLossW2) or 'gram' (StyleLoss: the scaled MSE of Gram matrices); "
+                        "a comma-separated list gives one per style layer, e.g. 'w2,w2,w2,gram,gram'")
+    p.add_argument('--content-eps', type=_loss_eps, default=None, metavar='EPS[,...]',
+                   help="the eps of the content term's module (default: 1e-8 for 'scaled_mse'; 'mse' has none); a "
+                        'comma-separated list gives one per content layer, an empty item the default')
+    p.add_argument('--style-eps', type=_loss_eps, default=None, metavar='EPS[,...]',
+                   help="the eps of the style term's module (default: 1e-4 for 'w2', 1e-8 for 'gram'); a comma-separated "
+                        "list gives one per style layer, an empty item the default, e.g. '1e-2,,,,1e-3'")
     p.add_argument('--trace', type=str, default='trace.json', help='where to write the iteration trace')
     return p
 
 
+def _loss_names(choices):
+    """argparse type of --content-loss / --style-loss: one name stays the string, a comma-separated list becomes the list."""
+    def parse(text):
+        names = text.split(',')
+        for name in names:
+            if name not in choices:
+                raise argparse.ArgumentTypeError(f"invalid choice: {name!r} (choose from {', '.join(map(repr, choices))})")
+        return names[0] if len(names) == 1 else names
+    return parse
+
+
+def _loss_eps(text):
+    """argparse type of --content-eps / --style-eps: a number, or a comma-separated list in which an empty item is None."""
+    try:
+        values = [float(item) if item.strip() else None for item in text.split(',')]
+    except ValueError:
+        raise argparse.ArgumentTypeError(f'invalid eps: {text!r} (a number, or a comma-separated list of numbers)') from None
+    return values[0] if len(values) == 1 else values
+
+
 def apply_loss_kinds(st, args):
-    """--content-loss / --style-loss onto the StyleTransfer attributes that stylize() reads."""
+    """--content-loss / --style-loss / --content-eps / --style-eps onto the StyleTransfer attributes that stylize() reads."""
     st.content_loss, st.style_loss = args.content_loss, args.style_loss
+    st.content_eps, st.style_eps = args.content_eps, args.style_eps
     return st
 
 

@@ -15,6 +15,7 @@ Python keeps only the cold path: the multi-scale pyramid, PIL resizing, target b
 scale-to-scale resampling of the optimiser state.
 """
 
+import math
 import os
 import time
 import warnings
@@ -239,6 +240,54 @@ def _resolve_loss_kinds(content_loss, style_loss, world=1):
                          "default kinds ('mse', 'w2') only; other loss kinds are out of scope for strips - run them on one "
                          'device')
     return content_loss, style_loss
+
+
+# the eps of each kind's module as the reference's constructors default it (StyleLossW2 :152, StyleLoss :130, ContentLoss :110)
+_LOSS_EPS = {'w2': 1e-4, 'gram': 1e-8, 'scaled_mse': 1e-8}
+
+
+def _resolve_layer_losses(content_loss, style_loss, content_eps, style_eps, n_content, n_style, world=1):
+    """``StyleTransfer.content_loss`` / ``style_loss`` / ``content_eps`` / ``style_eps`` per LAYER, as the fused closure takes
+    them: returns (content kinds, style kinds, content eps, style eps), one entry per layer of the list, an eps None where
+    the layer has its kind's default.  A kind is a name - every layer of the list - or a sequence with one name per layer;
+    an eps is None, a number - every layer - or a sequence of None / number per layer.  Raises ``ValueError`` naming the
+    attribute for a wrong length, an unknown name, an eps on an 'mse' layer, a negative or non-finite eps, and for any
+    non-default entry on several ranks, before any device work."""
+    kinds = []
+    for attr, given, n in (('content_loss', content_loss, n_content), ('style_loss', style_loss, n_style)):
+        single = not isinstance(given, (list, tuple))        # (anything else is taken as ONE name, and refused as unknown)
+        names = [given] * n if single else list(given)
+        if len(names) != n:
+            raise ValueError(f'{attr} {given!r}: {len(names)} names for {n} layers; give one name, or exactly one per entry '
+                             f'of {attr.split("_")[0]}_layers')
+        for name in names if names or not single else [given]:
+            # (the unknown-name messages are _resolve_loss_kinds')
+            _resolve_loss_kinds(*((name, _hip.STYLE_LOSSES[0]) if attr == 'content_loss' else (_hip.CONTENT_LOSSES[0], name)))
+        kinds.append(names)
+    epses = []
+    for attr, given, names in (('content_eps', content_eps, kinds[0]), ('style_eps', style_eps, kinds[1])):
+        values = [given] * len(names) if given is None or isinstance(given, (int, float)) else list(given)
+        if len(values) != len(names):
+            raise ValueError(f'{attr} {given!r}: {len(values)} values for {len(names)} layers; give None, one number, or '
+                             f'exactly one (None for the default) per entry of {attr.split("_")[0]}_layers')
+        for i, (value, name) in enumerate(zip(values, names)):
+            if value is None:
+                continue
+            if isinstance(value, str) or not math.isfinite(value) or value < 0:
+                raise ValueError(f'{attr} {given!r}: {value!r} is not a finite non-negative number (None: the default)')
+            if name not in _LOSS_EPS:
+                raise ValueError(f"{attr} {given!r}: layer {i} has the loss {name!r} (ContentLossMSE), which has no eps; "
+                                 'give None for it')
+            # (the library's eps is a float: a number that IS the default there counts as the default)
+            values[i] = None if np.float32(value) == np.float32(_LOSS_EPS[name]) else float(value)
+        epses.append(values)
+    default = (all(name == _hip.CONTENT_LOSSES[0] for name in kinds[0]) and all(name == _hip.STYLE_LOSSES[0] for name in kinds[1])
+               and all(value is None for value in epses[0] + epses[1]))
+    if world > 1 and not default:
+        raise ValueError(f'content_loss {content_loss!r} / style_loss {style_loss!r} / content_eps {content_eps!r} / style_eps '
+                         f"{style_eps!r} on {world} ranks: row strips run the default kinds ('mse', 'w2') with their default eps "
+                         'only; other loss kinds are out of scope for strips - run them on one device')
+    return kinds[0], kinds[1], epses[0], epses[1]
 
 
 def _resolve_weights(weights):
@@ -593,9 +642,14 @@ def _device_list_stylize(st, content_image, style_images, kw, callback):
 
 class StyleTransfer:
     # what the terms are (read by stylize() next to the layer attributes): 'mse' (ContentLossMSE) or 'scaled_mse' (ContentLoss);
-    # 'w2' (StyleLossW2) or 'gram' (StyleLoss on Gram matrices)
+    # 'w2' (StyleLossW2) or 'gram' (StyleLoss on Gram matrices).  A name is every layer of the list; a sequence holds exactly
+    # one name per entry of content_layers / style_layers, as the reference builds one module per layer.
     content_loss = 'mse'
     style_loss = 'w2'
+    # the eps of those modules: None (each kind's default: 1e-4 for 'w2', 1e-8 for 'gram' and 'scaled_mse'; 'mse' has none), a
+    # number for every layer of the list, or a sequence with a number or None per layer
+    content_eps = None
+    style_eps = None
 
     def __init__(self, devices=['cuda:0'], pooling='max', weights=None, precision='fp16x3'):
         # reference :310 defaults to ['cpu']; this build has no CPU path, so the default is the first HIP device
@@ -824,8 +878,9 @@ class StyleTransfer:
         content_layers, style_layers, layer_weights = _resolve_taps(
             self.content_layers, self.style_layers, self.style_weights,
             world=max(len(self.devices), _dist_info()[1]))
-        content_loss, style_loss = _resolve_loss_kinds(self.content_loss, self.style_loss,
-                                                       world=max(len(self.devices), _dist_info()[1]))
+        content_loss, style_loss, content_eps, style_eps = _resolve_layer_losses(
+            self.content_loss, self.style_loss, self.content_eps, self.style_eps, len(content_layers), len(style_layers),
+            world=max(len(self.devices), _dist_info()[1]))
         if len(self.devices) > 1 and self._job is None:
             return _device_list_stylize(self, content_image, style_images, dict(
                 style_weights=style_weights, content_weight=content_weight, tv_weight=tv_weight, optimizer=optimizer,
@@ -952,8 +1007,10 @@ class StyleTransfer:
                 plan = self._plan = _hip.Plan(self.model.net, ch, cw)
                 if (content_layers, style_layers) != (list(plan.content_layers), list(plan.style_layers)):
                     plan.set_taps(content_layers, style_layers)
-                if (content_loss, style_loss) != (plan.content_loss, plan.style_loss):
-                    plan.set_loss_kinds(content_loss, style_loss)
+                if (tuple(content_loss), tuple(style_loss)) != (plan.content_losses, plan.style_losses):
+                    plan.set_layer_loss_kinds(content_loss, style_loss)
+                if any(value is not None for value in content_eps + style_eps):
+                    plan.set_loss_eps(content_eps, style_eps)
                 self._build_targets(plan, content.to(device), style_images, style_weights, scale, style_scale_fac,
                                     style_size)
             plan.set_loss_weights(content_weights, layer_weights, tv_weight)
