@@ -142,6 +142,31 @@ int st_plan_backward(st_plan* plan, int count, const int* layers, const float* c
 int st_plan_moments(st_plan* plan, int layer, float* mean_out, float* srm_out, void* stream);
 
 /*
+ * A spatial mask for the style statistics: which pixels of the plan's image the style terms see.  The reference has no such
+ * control; the semantics are fixed here.  `mask` is [H][W] fp32 on the device with values in [0, 1], at the plan's image
+ * size; NULL clears it.  A pyramid of five levels is kept: level 0 is the mask, level k + 1 the plain mean of the 2 x 2 cells
+ * of level k at floor sizes (avg_pool2d(m, 2): the geometry of the trunk's pools, whatever the pooling mode), and a tap takes
+ * the level of the number of pools at or before it - features 1, 3: level 0; 4, 6, 8: 1; 9 ... 17: 2; 18 ... 26: 3; 27, 29: 4.
+ * While a mask is in force, with m the tap's level and M the sum of m, every style head takes the WEIGHTED moments
+ *     mean = sum_p m_p f_p / M,   srm = sum_p m_p f_p f_p^T / M
+ * in the place of StyleLossW2.get_target(input) inside StyleLossW2.forward (style_transfer.py:175-181) and of F F^T / N
+ * inside StyleLoss.forward (:141-142), and its gradient is that of those formulas: dF = (Ssym F + b 1^T) diag(m) with M in
+ * the place of N in (Ssym, b).  Targets, eps, weights, the Newton-Schulz chains and their backward are untouched; the content
+ * and TV terms see no mask.  It applies to every closure and step (st_plan_loss_and_grad, st_plan_step, st_plan_lbfgs_step,
+ * st_plan_range_guard) and to st_plan_moments - which is how the style of only a part of a style image is taken: set the
+ * mask on the style plan, take the moments, clear it.  A masked plan runs the general closure (csrc/st_taps.hip), on the
+ * default configuration too, and launches eagerly; a plan whose mask is cleared is, bit for bit, one that never had one.
+ * The lists, kinds, eps, weights and targets all stay.  The call is synchronous (the levels' sums are read back here, once:
+ * no closure reads anything back) and invalidates a captured graph.  It fails, naming the cause, on a strip plan, for a NaN
+ * or a value outside [0, 1], and when a level sums to 0 (the level is named: a mask can be non-zero only in a row or column
+ * that a floor-sized level drops); a refused mask leaves the plan without one.
+ */
+int st_plan_set_style_mask(st_plan* plan, const float* mask_or_null, void* stream);
+/* Borrow level `level` (0 .. 4) of the mask in force, as the plan keeps it: the SQUARE ROOT of the level, dense [h][w] fp32 on
+ * the device, with the level's sum M.  Any output pointer may be null.  Fails when no mask is set. */
+int st_plan_style_mask(const st_plan* plan, int level, const float** sqrt_mask, int* h, int* w, double* sum);
+
+/*
  * StyleTransfer.content_layers / style_layers (style_transfer.py:315-317, read by every scale at :425-453): the layers the
  * plan's closure puts its ContentLossMSE and StyleLossW2 terms on.  Each entry is a features index that st_plan_feature
  * accepts - the 13 ReLU outputs 1 3 6 8 11 13 15 17 20 22 24 26 29 and the 4 pool outputs 4 9 18 27; the reference also

@@ -434,6 +434,7 @@ int st_plan_moments(st_plan* p, int layer, float* mean_out, float* srm_out, void
     at.h = &p->head[op];
     at.tap = &node_at(p, op);
     if (j >= 0 && p->reference_taps) at = head_site(p, j);
+    mask_head_site(p, at, op);       // (a style mask in force: the weighted moments, st_plan_set_style_mask)
     if (ensure_moment_alloc(p, *at.h)) return 1;
     return moments_of_tap(p, at, mean_out, srm_out, static_cast<hipStream_t>(stream));
 }

@@ -312,7 +312,9 @@ int run_forward(st_plan* p, const float* image, int last_layer, hipStream_t s, b
                 // (reference_taps: relu1_1's head serves other lists too, whose closure does not read these partials)
                 StyleHead& h0 = p->head[0];
                 static Option fwd_too("ST_CONV1_GRAM_IN_FORWARD", 0);      // tests: st_plan_forward + st_plan_moments as well
-                p->gram1_fused = (fork_heads || fwd_too.get() != 0) && last_layer >= 1 && bounds && p->reference_taps && h0.allocated &&
+                // (nor under a style mask: the fused kernel takes plain sums)
+                p->gram1_fused = (fork_heads || fwd_too.get() != 0) && last_layer >= 1 && bounds && p->reference_taps && !p->style_mask &&
+                                 h0.allocated &&
                                  conv_first_gram_applies(p->H, p->W, image, n.y, h0.gram.max_splits);
                 if (hbm_profiled(p, HBM_CONV1_FWD, (3 + 64) * hw4, s, [&] {
                         if (p->gram1_fused)
@@ -425,7 +427,16 @@ HeadSite head_site(st_plan* p, int j) {
     at.grad = tap.g;
     at.grad_amax = tap.g_amax;
     at.slot = j;
+    mask_head_site(p, at, op);
     return at;
+}
+
+void mask_head_site(const st_plan* p, HeadSite& at, int op) {
+    if (!p->style_mask) return;
+    int level = 0;
+    for (int i = 0; i <= op; ++i) level += kProgram[i].kind == 1;
+    at.sqrt_mask = p->mask_sqrt[level];
+    at.mask_sum = (float)p->mask_sum[level];
 }
 
 int moments_of_tap(st_plan* p, const HeadSite& at, float* mean_out, float* srm_out, hipStream_t s, float* cov_out) {
@@ -433,16 +444,17 @@ int moments_of_tap(st_plan* p, const HeadSite& at, float* mean_out, float* srm_o
     const Node& tap = *at.tap;
     const int idx = at.slot;
     // (relu1_1 in the closure: conv1_1's launch has left the partials of its workgroups - run_forward)
-    const bool fused = idx == 0 && p->gram1_fused;
+    // (a mask set since that forward: the partials are plain sums, take the masked ones)
+    const bool fused = idx == 0 && p->gram1_fused && !at.sqrt_mask;
     const int splits = fused ? p->gram1_splits : gram_choose_splits(h.n, h.npix_local, h.gram.max_splits);
     // ST_GRAM_F32=1 (attribution runs, tools/grad_attribution.py): the moments on the exact fp32 matrix pipe in every mode
     static Option gram_f32("ST_GRAM_F32", 0);
     auto gram = [&] {
         if (!fused && !(ablate_side() & 1) &&
             launch_gram_partial(tap.y, h.n, h.npix_local, splits, h.gram, s,
-                                (p->net->conv_elem == 1 && !gram_f32.get()) ? tap.y_amax : nullptr))
+                                (p->net->conv_elem == 1 && !gram_f32.get()) ? tap.y_amax : nullptr, at.sqrt_mask))
             return 1;
-        return launch_gram_finalize(h.gram, h.n, h.npix, splits, mean_out, srm_out, s, cov_out, at.eps);
+        return launch_gram_finalize(h.gram, h.n, h.npix, splits, mean_out, srm_out, s, cov_out, at.eps, at.mask_sum);
     };
     // relu1_1's Gram (C = 64) reads its tap once and has 64 MACs per element on the 16-bit pipe: HBM-bound
     if (idx == 0 && !fused) return hbm_profiled(p, HBM_GRAM1, 4.0 * h.n * (double)h.npix_local, s, gram);
@@ -535,7 +547,7 @@ int style_head_chain(st_plan* p, const HeadSite& at, hipStream_t s, bool cov_rea
     if (launch_gemm_batch(one_gemm(n, h.gm, h.root_t, h.dt, 0, 1), s)) return 1;
     if (launch_gemm_batch(one_gemm(n, h.root_t, h.dt, h.dcov, 1, 0), s)) return 1;
     const bool f16 = p->net->conv_elem == 1;
-    return launch_style_grad_finish(h.dcov, h.mean, h.mean_t, n, w, h.npix, h.ssym, h.bvec, s, f16 ? h.s_amax : nullptr);
+    return launch_style_grad_finish(h.dcov, h.mean, h.mean_t, n, w, h.npix, h.ssym, h.bvec, s, f16 ? h.s_amax : nullptr, at.mask_sum);
 }
 
 // The three shallow heads (relu1_1, relu2_1, relu3_1: C = 64, 128, 256) with their Newton-Schulz chains in LOCKSTEP on one

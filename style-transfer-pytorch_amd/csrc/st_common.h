@@ -402,11 +402,15 @@ struct GramWorkspace {
 int gram_choose_splits(int channels, long long npix, int max_splits);
 // partial[s] = F[:, ks:ke] F[:, ks:ke]^T, partial_sum[s] = row sums; F is [C][npix]
 // bound != nullptr: fp16x3 arithmetic, scaled by the device bound on max |feat| (see ConvProblem::amax_word)
+// sqrt_mask (optional, [npix]): s = sqrt(m) of a spatial mask m - the staged values become F diag(s), the partials
+// F diag(m) F^T and F m (st_mask.hip has the pyramid that makes s)
 int launch_gram_partial(const float* feat, int channels, long long npix, int splits, GramWorkspace ws,
-                        hipStream_t s, const unsigned int* bound = nullptr);
-// mean = sum/npix, srm = sum/npix (fixed-order reduction over splits)
+                        hipStream_t s, const unsigned int* bound = nullptr, const float* sqrt_mask = nullptr);
+// mean = sum/npix, srm = sum/npix (fixed-order reduction over splits); mask_sum > 0: the normaliser of masked partials, the
+// sum of m, in the place of npix
 int launch_gram_finalize(GramWorkspace ws, int channels, long long npix, int splits, float* mean, float* srm,
-                         hipStream_t s, float* cov = nullptr, float cov_eps = 0.f);   // cov: also srm - mean mean^T + eps I
+                         hipStream_t s, float* cov = nullptr, float cov_eps = 0.f,   // cov: also srm - mean mean^T + eps I
+                         float mask_sum = 0.f);
 
 // ---- small dense algebra for the W2 style loss (st_smallgemm.hip) ------------------------------
 enum GemmEpilogue {
@@ -609,8 +613,9 @@ int launch_scaled_mse_sums(const float* x, const float* target, long long count,
 int launch_scaled_mse_grad(const float* feat, const float* target, long long count, float weight, const float* totals,
                            float* grad, hipStream_t s, int accumulate = 0);
 // ... or, for a Gram head, (Ssym, b) of its 1x1 step: ssym = (weight / npix) (D + D^T), D = dL/dG from the totals; bvec = 0
+// (mask_sum > 0, here and in launch_style_grad_finish: a masked head's normaliser in the place of npix)
 int launch_gram_grad_finish(const float* gram, const float* gram_t, const float* totals, int n, float weight, long long npix,
-                            float* ssym, float* bvec, hipStream_t s, unsigned int* ssym_amax = nullptr);
+                            float* ssym, float* bvec, hipStream_t s, unsigned int* ssym_amax = nullptr, float mask_sum = 0.f);
 // st_plan_backward's seeding: g = ext (accumulate == 0) or g += ext over `count` elements; relu_out (optional): the result
 // is masked by (relu_out > 0); bound (optional): max |g| folded into that device bound for an fp16x3 consumer
 int launch_seed_grad(const float* ext, const float* relu_out, float* g, long long count, int accumulate, unsigned int* bound,
@@ -624,7 +629,18 @@ int launch_style_loss_value(const float* mean, const float* mean_t, const float*
 //   ssym[c][d] = (dcov[c][d] + dcov[d][c]) / npix,  bvec[c] = (2 weight (mu-mu_t)[c]/n - sum_d (dcov+dcov^T)[c][d] mu[d]) / npix
 int launch_style_grad_finish(const float* g, const float* mean, const float* mean_t, int n, float weight,
                              long long npix, float* ssym, float* bvec, hipStream_t s,
-                             unsigned int* ssym_amax = nullptr);
+                             unsigned int* ssym_amax = nullptr, float mask_sum = 0.f);
+// ---- spatial style masks (st_mask.hip) ----------------------------------------------------------
+constexpr int kMaskLevels = 5;                    // the image's resolution and one level per pooling of the trunk
+constexpr int kMaskPyramidBlocks = 64;            // workgroups per level: their partial sums are added in a fixed order
+// From mask [h[0]][w[0]] (values in [0, 1]): level k + 1 is the plain mean of the 2 x 2 cells of level k at floor sizes
+// (h[k + 1] = h[k] / 2: avg_pool2d(m, 2)); sqrt_level[k] receives sqrt of level k.  stats (device, 8 doubles): [0..4] the sum
+// of each level, [5] min and [6] max of the mask, [7] the number of NaNs in it; partials: kMaskLevels x kMaskPyramidBlocks x 4
+// doubles.  Fixed-order sums, no atomics: two calls give the same bits.
+int launch_mask_pyramid(const float* mask, const int* h, const int* w, float* const* sqrt_level, double* partials, double* stats,
+                        hipStream_t s);
+// buf [c][npix] *= sqrt_mask[npix]^2 per pixel column: the masked heads' gradient step dF = (Ssym F + b 1^T) diag(m)
+int launch_mask_columns(float* buf, const float* sqrt_mask, int channels, long long npix, hipStream_t s);
 // TV loss partial sums + gradient (optionally scaled by `weight`): see st_pointwise.hip
 int launch_tv(const float* image, int height, int width, float weight, float* grad, float* partials,
               float* loss_out, hipStream_t s, unsigned int* ticket = nullptr);

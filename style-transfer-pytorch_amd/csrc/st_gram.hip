@@ -20,6 +20,8 @@
 //   and accumulated as h0 h0^T + h0 h1^T + h1 h0^T with v_mfma_f32_32x32x16_f16 -- fp32-class accuracy at
 //   3/16 of the fp32 matrix-pipe time, which turns the kernel from MFMA-bound into a streaming read of F.
 //   The row sums (the mean) are always taken from the fp32 values.
+// Each pass-1 kernel also has a MASKED instantiation for spatially weighted moments (st_mask.hip): F diag(m) F^T and F m from
+// a per-pixel operand sqrt(m) applied to both staged operands; pass 2 then divides by sum(m) instead of N.
 //
 // fp32 variant: LDS tile [64 ch][64 px] with a row pitch of 68 floats: ds_read_b128 (4 consecutive pixels of one
 // channel per lane) is then conflict-free (16-lane groups hit 16 distinct 16-byte slots), and one
@@ -69,10 +71,16 @@ __device__ __forceinline__ void store_tile_pair(float* __restrict__ out, int C, 
     }
 }
 
+// MASKED (all three pass-1 kernels): `smask` holds s = sqrt(m) per pixel (the plan's style mask at the tap's level); a staged
+// value is v = f s for BOTH operands - so a diagonal tile pair still shares one LDS operand, the result stays exactly symmetric
+// and F diag(m) F^T needs no masked copy of the tap - and the row sums add v s = f m, from the fp32 values.  s <= 1: the
+// fp16x3 scale stays the producing convolution's bound.  The unmasked instantiations are the kernels as they were.
+template <bool MASKED>
 __global__ __launch_bounds__(256) void gram_partial_kernel(const float* __restrict__ feat, int C,
                                                            long long N, int splits, long long per_split,
                                                            float* __restrict__ partial,
-                                                           float* __restrict__ partial_sum, int xcd_remap) {
+                                                           float* __restrict__ partial_sum, int xcd_remap,
+                                                           const float* __restrict__ smask) {
     __shared__ __attribute__((aligned(16))) float lds[2][2][GT * GP];   // [buffer][operand][64 x 68]
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -91,9 +99,19 @@ __global__ __launch_bounds__(256) void gram_partial_kernel(const float* __restri
     // staging map: thread -> (row = tid/16 + 16 r, 4 consecutive pixels at col 4*(tid%16))
     const int srow = tid >> 4, scol = (tid & 15) * 4;
     f32x4 ra[4], rb[4];
+    f32x4 rs = {0.f, 0.f, 0.f, 0.f};      // MASKED: s of this thread's 4 pixels (the same for its 4 rows)
     float rowsum[4] = {0.f, 0.f, 0.f, 0.f};
 
     auto load_tile = [&](long long k0) {
+        if constexpr (MASKED) {
+            const long long k = k0 + scol;
+            if (vec_ok && k + 3 < k_end) {
+                rs = *reinterpret_cast<const f32x4*>(smask + k);
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) rs[e] = (k + e < k_end) ? smask[k + e] : 0.f;
+            }
+        }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int row = srow + 16 * r;
@@ -113,6 +131,10 @@ __global__ __launch_bounds__(256) void gram_partial_kernel(const float* __restri
                     }
                 }
             }
+            if constexpr (MASKED) {
+                va = va * rs;
+                vb = vb * rs;
+            }
             ra[r] = va;
             rb[r] = vb;
         }
@@ -123,7 +145,10 @@ __global__ __launch_bounds__(256) void gram_partial_kernel(const float* __restri
             const int row = srow + 16 * r;
             *reinterpret_cast<f32x4*>(&lds[buf][0][row * GP + scol]) = ra[r];
             if (!diag) *reinterpret_cast<f32x4*>(&lds[buf][1][row * GP + scol]) = rb[r];
-            rowsum[r] += (ra[r][0] + ra[r][1]) + (ra[r][2] + ra[r][3]);
+            if constexpr (MASKED)
+                rowsum[r] += (ra[r][0] * rs[0] + ra[r][1] * rs[1]) + (ra[r][2] * rs[2] + ra[r][3] * rs[3]);
+            else
+                rowsum[r] += (ra[r][0] + ra[r][1]) + (ra[r][2] + ra[r][3]);
         }
     };
 
@@ -171,11 +196,13 @@ __global__ __launch_bounds__(256) void gram_partial_kernel(const float* __restri
 }
 
 // fp16x3 variant (see the header).  Staging map: thread -> (row = tid/4, 8 consecutive pixels at 8*(tid%4)).
+template <bool MASKED>
 __global__ __launch_bounds__(256) void gram_partial_f16_kernel(const float* __restrict__ feat, int C, long long N,
                                                                int splits, long long per_split,
                                                                const unsigned int* __restrict__ bound,
                                                                float* __restrict__ partial,
-                                                               float* __restrict__ partial_sum, int xcd_remap) {
+                                                               float* __restrict__ partial_sum, int xcd_remap,
+                                                               const float* __restrict__ smask) {
     __shared__ __attribute__((aligned(16))) _Float16 lds[2][2][2][GT * HP];   // [buffer][operand][plane][64 x 40]
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -195,6 +222,7 @@ __global__ __launch_bounds__(256) void gram_partial_f16_kernel(const float* __re
 
     const int srow = tid >> 2, scol = (tid & 3) * 8;
     float va[8], vb[8];
+    float vs[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};      // MASKED: s of this thread's 8 pixels
     float rowsum = 0.f;
 
     auto load_row = [&](const float* p, long long k, float (&v)[8]) {
@@ -214,6 +242,14 @@ __global__ __launch_bounds__(256) void gram_partial_f16_kernel(const float* __re
         const long long k = k0 + scol;
         load_row(feat + (size_t)(ti * GT + srow) * N + k, k, va);
         if (!diag) load_row(feat + (size_t)(tj * GT + srow) * N + k, k, vb);
+        if constexpr (MASKED) {
+            load_row(smask + k, k, vs);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                va[e] *= vs[e];
+                if (!diag) vb[e] *= vs[e];
+            }
+        }
     };
     auto split_store = [&](const float (&v)[8], _Float16* p0, _Float16* p1) {
         f16x8 h0, h1;
@@ -231,7 +267,11 @@ __global__ __launch_bounds__(256) void gram_partial_f16_kernel(const float* __re
         const int off = srow * HP + scol;
         split_store(va, &lds[buf][0][0][off], &lds[buf][0][1][off]);
         if (!diag) split_store(vb, &lds[buf][1][0][off], &lds[buf][1][1][off]);
-        rowsum += ((va[0] + va[1]) + (va[2] + va[3])) + ((va[4] + va[5]) + (va[6] + va[7]));
+        if constexpr (MASKED)
+            rowsum += ((va[0] * vs[0] + va[1] * vs[1]) + (va[2] * vs[2] + va[3] * vs[3])) +
+                      ((va[4] * vs[4] + va[5] * vs[5]) + (va[6] * vs[6] + va[7] * vs[7]));
+        else
+            rowsum += ((va[0] + va[1]) + (va[2] + va[3])) + ((va[4] + va[5]) + (va[6] + va[7]));
     };
 
     f32x16 acc;
@@ -298,11 +338,13 @@ __global__ __launch_bounds__(256) void gram_partial_f16_kernel(const float* __re
 // per 3).  One LDS buffer (40 KB), the next stage's global loads in flight during the MFMAs, two barriers per stage.
 // Symmetry: a wave writes the 32 x 32 blocks on or above the diagonal and their mirrors from the SAME accumulators
 // (entry (j, i) is defined as entry (i, j), i <= j), so the result is exactly symmetric without the LDS mirror pass.
+template <bool MASKED>
 __global__ __launch_bounds__(256, 2) void gram_partial_f16_wide_kernel(const float* __restrict__ feat, int C, long long N,
                                                                        int splits, long long per_split,
                                                                        const unsigned int* __restrict__ bound,
                                                                        float* __restrict__ partial,
-                                                                       float* __restrict__ partial_sum, int xcd_remap) {
+                                                                       float* __restrict__ partial_sum, int xcd_remap,
+                                                                       const float* __restrict__ smask) {
     constexpr int TS = 128;
     __shared__ __attribute__((aligned(16))) _Float16 lds[2][2][TS * HP];        // [operand][plane][128 x 40]
     const int tid = threadIdx.x, lane = tid & 63;
@@ -322,6 +364,7 @@ __global__ __launch_bounds__(256, 2) void gram_partial_f16_wide_kernel(const flo
 
     const int srow = tid >> 2, scol = (tid & 3) * 8;        // rows srow and srow + 64, 8 consecutive pixels
     float va[2][8], vb[2][8];
+    float vs[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};      // MASKED: s of this thread's 8 pixels (the same for both rows)
     float rowsum[2] = {0.f, 0.f};
     auto load_row = [&](const float* p, long long k, float (&v)[8]) __attribute__((always_inline)) {
 #pragma unroll
@@ -343,6 +386,16 @@ __global__ __launch_bounds__(256, 2) void gram_partial_f16_wide_kernel(const flo
             load_row(feat + (size_t)(ti * TS + h * 64 + srow) * N + k, k, va[h]);
             if (!diag) load_row(feat + (size_t)(tj * TS + h * 64 + srow) * N + k, k, vb[h]);
         }
+        if constexpr (MASKED) {
+            load_row(smask + k, k, vs);
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    va[h][e] *= vs[e];
+                    if (!diag) vb[h][e] *= vs[e];
+                }
+        }
     };
     auto split_store = [&](const float (&v)[8], _Float16* p0, _Float16* p1) __attribute__((always_inline)) {
         f16x8 h0, h1;
@@ -362,7 +415,11 @@ __global__ __launch_bounds__(256, 2) void gram_partial_f16_wide_kernel(const flo
             const int off = (h * 64 + srow) * HP + scol;
             split_store(va[h], &lds[0][0][off], &lds[0][1][off]);
             if (!diag) split_store(vb[h], &lds[1][0][off], &lds[1][1][off]);
-            rowsum[h] += ((va[h][0] + va[h][1]) + (va[h][2] + va[h][3])) + ((va[h][4] + va[h][5]) + (va[h][6] + va[h][7]));
+            if constexpr (MASKED)
+                rowsum[h] += ((va[h][0] * vs[0] + va[h][1] * vs[1]) + (va[h][2] * vs[2] + va[h][3] * vs[3])) +
+                             ((va[h][4] * vs[4] + va[h][5] * vs[5]) + (va[h][6] * vs[6] + va[h][7] * vs[7]));
+            else
+                rowsum[h] += ((va[h][0] + va[h][1]) + (va[h][2] + va[h][3])) + ((va[h][4] + va[h][5]) + (va[h][6] + va[h][7]));
         }
     };
 
@@ -447,7 +504,7 @@ __global__ __launch_bounds__(256, 2) void gram_partial_f16_wide_kernel(const flo
     }
 }
 
-// Fixed-order reduction over the splits.  A workgroup owns 32 consecutive outputs; its 8 thread
+// Fixed-order reduction over the splits; n: the normaliser - the pixel count as a float, or a masked head's sum of the mask.  A workgroup owns 32 consecutive outputs; its 8 thread
 // groups take every 8th split (independent loads, several in flight), then combine in a fixed tree.
 // cov != nullptr: the workgroups that own second-moment entries also write cov = srm - mean mean^T + eps I
 // (StyleLossW2.srm_to_cov + eye_like * eps, style_transfer.py:156,170-177) - they reduce the row sums of their row and of
@@ -455,12 +512,11 @@ __global__ __launch_bounds__(256, 2) void gram_partial_f16_wide_kernel(const flo
 // this kernel's outputs, bit for bit, without being a launch of its own in front of every head's chain.
 __global__ __launch_bounds__(256) void gram_finalize_kernel(const float* __restrict__ partial,
                                                             const float* __restrict__ partial_sum, int C,
-                                                            long long N, int splits, float* __restrict__ mean,
+                                                            float n, int splits, float* __restrict__ mean,
                                                             float* __restrict__ srm, float* __restrict__ cov, float eps) {
 #pragma clang fp contract(off)
     __shared__ float red[8][32];
     const long long total = (long long)C * C;
-    const float n = (float)N;
     const int e = threadIdx.x & 31, grp = threadIdx.x >> 5;
     const long long i = (long long)blockIdx.x * 32 + e;
     const bool is_srm = i < total;
@@ -533,7 +589,7 @@ int gram_choose_splits(int channels, long long npix, int max_splits) {
 }
 
 int launch_gram_partial(const float* feat, int channels, long long npix, int splits, GramWorkspace ws,
-                        hipStream_t s, const unsigned int* bound) {
+                        hipStream_t s, const unsigned int* bound, const float* sqrt_mask) {
     ST_REQUIRE(channels % GT == 0, "gram: channel count must be a multiple of 64");
     ST_REQUIRE(splits >= 1 && splits <= ws.max_splits, "gram: bad split count %d", splits);
     long long per_split = (npix + splits - 1) / splits;
@@ -542,28 +598,38 @@ int launch_gram_partial(const float* feat, int channels, long long npix, int spl
     const int remap = remap_opt.get();
     if (bound && gram_wide_tiles(channels, npix)) {
         const int wide = (channels / 128) * (channels / 128 + 1) / 2;
-        hipLaunchKernelGGL(gram_partial_f16_wide_kernel, dim3(wide, splits), dim3(256), 0, s, feat, channels, npix, splits,
-                           per_split, bound, ws.partial, ws.partial_sum, remap);
+        if (sqrt_mask)
+            hipLaunchKernelGGL(gram_partial_f16_wide_kernel<true>, dim3(wide, splits), dim3(256), 0, s, feat, channels, npix, splits,
+                               per_split, bound, ws.partial, ws.partial_sum, remap, sqrt_mask);
+        else
+            hipLaunchKernelGGL(gram_partial_f16_wide_kernel<false>, dim3(wide, splits), dim3(256), 0, s, feat, channels, npix, splits,
+                               per_split, bound, ws.partial, ws.partial_sum, remap, sqrt_mask);
         ST_LAUNCH_CHECK();
         return 0;
     }
     const int tiles = (channels / GT) * (channels / GT + 1) / 2;
-    if (bound)
-        hipLaunchKernelGGL(gram_partial_f16_kernel, dim3(tiles, splits), dim3(256), 0, s, feat, channels, npix,
-                           splits, per_split, bound, ws.partial, ws.partial_sum, remap);
+    if (bound && sqrt_mask)
+        hipLaunchKernelGGL(gram_partial_f16_kernel<true>, dim3(tiles, splits), dim3(256), 0, s, feat, channels, npix,
+                           splits, per_split, bound, ws.partial, ws.partial_sum, remap, sqrt_mask);
+    else if (bound)
+        hipLaunchKernelGGL(gram_partial_f16_kernel<false>, dim3(tiles, splits), dim3(256), 0, s, feat, channels, npix,
+                           splits, per_split, bound, ws.partial, ws.partial_sum, remap, sqrt_mask);
+    else if (sqrt_mask)
+        hipLaunchKernelGGL(gram_partial_kernel<true>, dim3(tiles, splits), dim3(256), 0, s, feat, channels, npix,
+                           splits, per_split, ws.partial, ws.partial_sum, remap, sqrt_mask);
     else
-        hipLaunchKernelGGL(gram_partial_kernel, dim3(tiles, splits), dim3(256), 0, s, feat, channels, npix,
-                           splits, per_split, ws.partial, ws.partial_sum, remap);
+        hipLaunchKernelGGL(gram_partial_kernel<false>, dim3(tiles, splits), dim3(256), 0, s, feat, channels, npix,
+                           splits, per_split, ws.partial, ws.partial_sum, remap, sqrt_mask);
     ST_LAUNCH_CHECK();
     return 0;
 }
 
 int launch_gram_finalize(GramWorkspace ws, int channels, long long npix, int splits, float* mean, float* srm,
-                         hipStream_t s, float* cov, float cov_eps) {
+                         hipStream_t s, float* cov, float cov_eps, float mask_sum) {
     const long long total = (long long)channels * channels + channels;
     const int blocks = (int)((total + 31) / 32);
     hipLaunchKernelGGL(gram_finalize_kernel, dim3(blocks), dim3(256), 0, s, ws.partial, ws.partial_sum,
-                       channels, npix, splits, mean, srm, cov, cov_eps);
+                       channels, mask_sum > 0.f ? mask_sum : (float)npix, splits, mean, srm, cov, cov_eps);
     ST_LAUNCH_CHECK();
     return 0;
 }

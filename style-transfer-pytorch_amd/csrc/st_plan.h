@@ -1,5 +1,5 @@
 // Internal to libst_amd.so: the VGG-19 program, the plan's nodes and style heads, st_net / st_plan, and the plan helpers
-// that more than one of st_api.hip, st_closure.hip, st_taps.hip, st_strip.hip and st_range_guard.hip call.
+// that more than one of st_api.hip, st_closure.hip, st_taps.hip, st_mask.hip, st_strip.hip and st_range_guard.hip call.
 #pragma once
 
 #include <functional>
@@ -78,6 +78,8 @@ struct HeadSite {
     unsigned int* grad_amax = nullptr;   // fp16x3: bound of what is written (null: whoever consumes it next commits one)
     int slot = -1;                   // 0 .. 4: the default closure's head of that index (relu1_1's fused Gram, relu5_1's mask,
                                      // the timeline events, the persistent chain's mask); -1: none of these
+    const float* sqrt_mask = nullptr;    // a style mask is in force (st_plan::style_mask): sqrt of it at the tap's level ...
+    float mask_sum = 0.f;                // ... and that level's sum, the moments' and the gradient step's normaliser (mask_head_site)
 };
 
 struct ProfileEvent {
@@ -161,6 +163,15 @@ struct st_plan {
     float* tap_seed[st::kNumOps] = {};               // general closure: the heads' gradient of a tapped position, run_tap_backward's seed
     float* terms = nullptr;                          // general closure on other lists than the reference's: [64], at most 16 + 16 + 1
                                                      // used - the weighted terms in SumLoss order (st_plan_term_losses)
+    // Spatial style mask (st_plan_set_style_mask, st_mask.hip): while style_mask is set every style head takes WEIGHTED moments
+    // of its tap - the mask at the tap's level (the number of pools at or before it), as its square root, which the Gram
+    // kernels put on both operands - and multiplies its gradient's pixel columns by the mask.  The general closure runs then
+    // (general_taps), on the reference's configuration too.  The sums are read back once, by the setter.
+    bool style_mask = false;
+    float* mask_sqrt[st::kMaskLevels] = {};          // [h][w] of mask_h / mask_w, allocated by the first setter call
+    int mask_h[st::kMaskLevels] = {}, mask_w[st::kMaskLevels] = {};
+    double mask_sum[st::kMaskLevels] = {};
+    double* mask_stats = nullptr;                    // the pyramid kernel's partials and, behind them, its 8 results
     float* grad_img = nullptr;       // [3][H][W] internal gradient for st_plan_step
     float* losses = nullptr;         // [8] device
     float* red_partials = nullptr;   // scratch for two-level reductions: TV [0, 4 kStreamBlocks), content MSE after it
@@ -313,6 +324,7 @@ int ensure_moment_alloc(st_plan* p, StyleHead& h);      // what st_plan_moments 
 int ensure_style_alloc(st_plan* p, StyleHead& h, int kind);   // ... and what a head of that style kind needs
 int ensure_grad_alloc(st_plan* p);
 HeadSite head_site(st_plan* p, int j);
+void mask_head_site(const st_plan* p, HeadSite& at, int op);   // the style mask's level of kProgram[op], if one is in force
 int moments_of_tap(st_plan* p, const HeadSite& at, float* mean_out, float* srm_out, hipStream_t s, float* cov_out = nullptr);
 int moment_sums_of_tap(st_plan* p, int j, float* sums, hipStream_t s);
 int style_head(st_plan* p, const HeadSite& at, hipStream_t s);

@@ -848,9 +848,9 @@ int launch_scaled_mse_grad(const float* feat, const float* target, long long cou
 }
 
 int launch_gram_grad_finish(const float* gram, const float* gram_t, const float* totals, int n, float weight, long long npix,
-                            float* ssym, float* bvec, hipStream_t s, unsigned int* ssym_amax) {
-    hipLaunchKernelGGL(gram_grad_finish_kernel, dim3(n), dim3(256), 0, s, gram, gram_t, totals, n, weight, (float)npix, ssym, bvec,
-                       ssym_amax);
+                            float* ssym, float* bvec, hipStream_t s, unsigned int* ssym_amax, float mask_sum) {
+    hipLaunchKernelGGL(gram_grad_finish_kernel, dim3(n), dim3(256), 0, s, gram, gram_t, totals, n, weight,
+                       mask_sum > 0.f ? mask_sum : (float)npix, ssym, bvec, ssym_amax);
     ST_LAUNCH_CHECK();
     return 0;
 }
@@ -880,9 +880,9 @@ int launch_style_loss_value(const float* mean, const float* mean_t, const float*
 }
 
 int launch_style_grad_finish(const float* g, const float* mean, const float* mean_t, int n, float weight,
-                             long long npix, float* ssym, float* bvec, hipStream_t s, unsigned int* ssym_amax) {
+                             long long npix, float* ssym, float* bvec, hipStream_t s, unsigned int* ssym_amax, float mask_sum) {
     hipLaunchKernelGGL(style_grad_finish_kernel, dim3(n), dim3(256), 0, s, g, mean, mean_t, n, weight,
-                       (float)npix, ssym, bvec, ssym_amax);
+                       mask_sum > 0.f ? mask_sum : (float)npix, ssym, bvec, ssym_amax);
     ST_LAUNCH_CHECK();
     return 0;
 }

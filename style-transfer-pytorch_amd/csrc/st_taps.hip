@@ -31,6 +31,11 @@
 //                           buffer (gram_head: four launches, no Newton-Schulz chain)
 //   a scaled-MSE content term   the sums and the term, then the seed written or added  (launch_scaled_mse_sums / _grad)
 // Everything around the terms - TV, the forward, the terms' total, the tap backward, the step's fold - is unchanged.
+//
+// A style mask (st_plan_set_style_mask, st_mask.hip) also runs this closure, the reference's configuration under the default
+// kinds and eps included: every head's site carries sqrt(m) at its tap's level and the level's sum (mask_head_site), the Gram
+// launch and the normalisers read them, and the head's seed buffer is multiplied by m per pixel column (launch_mask_columns)
+// right behind the head's 1x1 step, before a content term of the same layer adds onto it.
 #include <algorithm>
 #include <cmath>
 
@@ -85,7 +90,7 @@ static bool default_eps(const st_plan* p) {
 
 bool general_taps(const st_plan* p) {
     static Option force("ST_GENERAL_TAPS", 0);
-    return !p->strip && (!p->reference_taps || !default_kinds(p) || !default_eps(p) || force.get() != 0);
+    return !p->strip && (!p->reference_taps || !default_kinds(p) || !default_eps(p) || p->style_mask || force.get() != 0);
 }
 
 float style_eps_of(const st_plan* p, int j) {
@@ -140,7 +145,7 @@ int gram_head(st_plan* p, const HeadSite& at, int term, hipStream_t s) {
                                at.eps))
         return 1;
     if (launch_gram_grad_finish(h.srm, h.gram_t, totals, h.n, at.weight, h.npix, h.ssym, h.bvec, s,
-                                p->net->conv_elem == 1 ? h.s_amax : nullptr))
+                                p->net->conv_elem == 1 ? h.s_amax : nullptr, at.mask_sum))
         return 1;
     return style_head_gradient(p, at, s);
 }
@@ -183,6 +188,9 @@ int general_loss_and_grad(st_plan* p, const float* image, float* grad_out, float
     for (int k = 0; k < ns; ++k) {
         const HeadSite at = general_head_site(p, order[k]);
         if (p->style_kind[order[k]] == 1 ? gram_head(p, at, nc + order[k], s) : style_head(p, at, s)) return 1;
+        // a style mask: dF's pixel columns times m, on the seed as the head's 1x1 step left it and BEFORE a content term of the
+        // same layer adds onto it
+        if (at.sqrt_mask && launch_mask_columns(at.grad, at.sqrt_mask, at.h->n, at.h->npix, s)) return 1;
         styled[p->style_op[order[k]]] = true;
     }
     // ContentLossMSE per content layer (style_transfer.py:425-429), behind the style head of the same layer where there is one;

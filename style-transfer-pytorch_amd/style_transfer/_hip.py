@@ -62,6 +62,8 @@ def _declare(lib):
         'st_plan_feature': (i32, [vp, i32, pp, ip, ip, ip]),
         'st_plan_backward': (i32, [vp, i32, ip, pp, vp, vp]),
         'st_plan_moments': (i32, [vp, i32, vp, vp, vp]),
+        'st_plan_set_style_mask': (i32, [vp, vp, vp]),
+        'st_plan_style_mask': (i32, [vp, i32, pp, ip, ip, ctypes.POINTER(f64)]),
         'st_plan_set_content_target': (i32, [vp, vp, vp]),
         'st_plan_set_style_target': (i32, [vp, i32, vp, vp, vp]),
         'st_plan_set_loss_weights': (i32, [vp, f32, ctypes.POINTER(f32), f32]),
@@ -470,6 +472,33 @@ class Plan:
         with torch.cuda.device(self.device):
             _check(self.lib.st_plan_moments(self.handle, int(layer), _ptr(mean), _ptr(srm), _stream()))
         return mean, srm
+
+    def set_style_mask(self, mask):
+        """A spatial mask for the style statistics (st_plan_set_style_mask): a [height, width] tensor with values in [0, 1]
+        at the plan's image size, or None to clear it.  While it is set every style head of every closure and step, and
+        ``moments``, take the mask-weighted moments of their tap (the mask averaged down 2 x 2 to the tap's resolution).
+        Raises HipLibraryError on a strip plan, for a NaN or a value outside [0, 1], and when a level of the pyramid sums
+        to 0; a refused mask leaves the plan without one."""
+        with torch.cuda.device(self.device):
+            if mask is None:
+                _check(self.lib.st_plan_set_style_mask(self.handle, None, _stream()))
+                return
+            mask = torch.as_tensor(mask)
+            if tuple(mask.shape) != (self.height, self.width):
+                raise ValueError(f'style mask of shape {tuple(mask.shape)}: the plan is {self.height} x {self.width}')
+            mask = mask.to(self.device, torch.float32).contiguous()
+            _check(self.lib.st_plan_set_style_mask(self.handle, _ptr(mask), _stream()))
+
+    def style_mask_level(self, level):
+        """(sqrt of level ``level`` of the style mask as an [h, w] tensor - a copy -, the level's sum) as the plan keeps them
+        (st_plan_style_mask): level k serves the taps behind k pools.  Raises HipLibraryError when no mask is set."""
+        data, h, w, total = ctypes.c_void_p(), ctypes.c_int(), ctypes.c_int(), ctypes.c_double()
+        _check(self.lib.st_plan_style_mask(self.handle, int(level), ctypes.byref(data), ctypes.byref(h), ctypes.byref(w),
+                                           ctypes.byref(total)))
+        out = torch.empty((h.value, w.value), device=self.device, dtype=torch.float32)
+        with torch.cuda.device(self.device):
+            _copy_d2d(out, data.value)
+        return out, total.value
 
     def set_content_target(self, feat, index=0):
         """The target of content layer ``index`` of the configured list (st_plan_set_content_target_at)."""

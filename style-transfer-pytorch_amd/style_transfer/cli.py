@@ -304,6 +304,12 @@ def build_parser():
     p.add_argument('--style-eps', type=_loss_eps, default=None, metavar='EPS[,...]',
                    help="the eps of the style term's module (default: 1e-4 for 'w2', 1e-8 for 'gram'); a comma-separated "
                         "list gives one per style layer, an empty item the default, e.g. '1e-2,,,,1e-3'")
+    p.add_argument('--style-mask', type=str, default=None, metavar='PATH',
+                   help='an image (read as greyscale, white = 1) saying which pixels of the output take the style; it is '
+                        'resized to every scale')
+    p.add_argument('--style-image-masks', type=str, default=None, nargs='+', metavar='PATH',
+                   help="one per style image: an image saying which pixels of that style image the style is taken from, or "
+                        "the literal 'none' for no mask on that image")
     p.add_argument('--trace', type=str, default='trace.json', help='where to write the iteration trace')
     return p
 
@@ -326,6 +332,24 @@ def _loss_eps(text):
     except ValueError:
         raise argparse.ArgumentTypeError(f'invalid eps: {text!r} (a number, or a comma-separated list of numbers)') from None
     return values[0] if len(values) == 1 else values
+
+
+def apply_style_masks(st, args):
+    """--style-mask / --style-image-masks onto the StyleTransfer attributes that stylize() reads: the files are opened here;
+    one path per style image is demanded here, since the literal 'none' is only meaningful by position."""
+    def load(path):
+        try:
+            return Image.open(path).convert('L')
+        except OSError as err:
+            _fail(err)
+    st.style_mask = None if args.style_mask is None else load(args.style_mask)
+    st.style_image_masks = None
+    if args.style_image_masks is not None:
+        if len(args.style_image_masks) != len(args.styles):
+            _fail(ValueError(f"--style-image-masks: {len(args.style_image_masks)} entries for {len(args.styles)} style images "
+                             "(use 'none' for an image without a mask)"))
+        st.style_image_masks = [None if path.lower() == 'none' else load(path) for path in args.style_image_masks]
+    return st
 
 
 def apply_loss_kinds(st, args):
@@ -383,6 +407,7 @@ def main(argv=None):
     print('Loading model...')
     st = StyleTransfer(devices=devices, pooling=args.pooling, weights=args.weights, precision=args.precision)
     apply_loss_kinds(st, args)
+    apply_style_masks(st, args)
     callback = Callback(st, args, image_type=image_type, web_interface=web_interface)
     atexit.register(callback.close)
 

@@ -290,6 +290,61 @@ def _resolve_layer_losses(content_loss, style_loss, content_eps, style_eps, n_co
     return kinds[0], kinds[1], epses[0], epses[1]
 
 
+def _mask_image(mask, attr):
+    """One mask as (PIL image, divisor): a PIL image becomes mode 'L' (divisor 255), a 2-D numpy / torch array with values
+    in [0, 1] a mode 'F' image (divisor 1).  Raises ``ValueError`` naming ``attr``."""
+    if isinstance(mask, Image.Image):
+        image = mask.convert('L')
+        if image.getextrema()[1] == 0:
+            raise ValueError(f'{attr}: the mask is zero everywhere; no pixel would carry the style statistics')
+        return image, 255.0
+    if isinstance(mask, torch.Tensor):
+        mask = mask.detach().cpu().numpy()
+    try:
+        values = np.asarray(mask, dtype=np.float32)
+    except (TypeError, ValueError):
+        raise ValueError(f'{attr}: a mask is a PIL image or a 2-D numpy / torch array, not {type(mask).__name__}') from None
+    if values.ndim != 2 or values.size == 0:
+        raise ValueError(f'{attr}: a mask array has 2 dimensions (height, width), not shape {tuple(values.shape)}')
+    if not np.isfinite(values).all() or values.min() < 0 or values.max() > 1:
+        raise ValueError(f'{attr}: the mask holds non-finite values or values outside [0, 1]')
+    if values.max() == 0:
+        raise ValueError(f'{attr}: the mask is zero everywhere; no pixel would carry the style statistics')
+    return Image.fromarray(np.ascontiguousarray(values), mode='F'), 1.0
+
+
+def _resolve_style_masks(style_mask, style_image_masks, n_style_images, world=1):
+    """``StyleTransfer.style_mask`` / ``style_image_masks`` as stylize() takes them: returns (the output mask or None, one
+    entry - a mask or None - per style image), every mask as ``_mask_image`` gives it, for ``_sized_mask`` to bring to a
+    scale's size.  Raises ``ValueError`` naming the attribute for a list of the wrong length, an array of the wrong number
+    of dimensions, values outside [0, 1] or non-finite, an all-zero mask, and for any mask on several ranks, before any
+    device work."""
+    output = None if style_mask is None else _mask_image(style_mask, 'style_mask')
+    if style_image_masks is None:
+        per_image = [None] * n_style_images
+    else:
+        if isinstance(style_image_masks, (Image.Image, np.ndarray, torch.Tensor)) or not hasattr(style_image_masks, '__len__'):
+            raise ValueError('style_image_masks: give None, or a list with exactly one entry (None or a mask) per style image')
+        if len(style_image_masks) != n_style_images:
+            raise ValueError(f'style_image_masks: {len(style_image_masks)} entries for {n_style_images} style images; give '
+                             'None, or exactly one entry (None or a mask) per style image')
+        per_image = [None if mask is None else _mask_image(mask, f'style_image_masks[{i}]')
+                     for i, mask in enumerate(style_image_masks)]
+    if world > 1 and (output is not None or any(entry is not None for entry in per_image)):
+        raise ValueError(f'style_mask / style_image_masks on {world} ranks: row strips take no style mask (a level\'s sum would '
+                         'span the ranks); masks are out of scope for strips - run them on one device')
+    return output, per_image
+
+
+def _sized_mask(entry, width, height):
+    """A resolved mask at ``width`` x ``height``: bilinear, as fp32 in [0, 1] ([height, width] tensor)."""
+    image, divisor = entry
+    values = np.asarray(image.resize((width, height), Image.BILINEAR), dtype=np.float32)
+    # (an 'F' image's bilinear weights are floats: a value can leave [0, 1] by a rounding, which the plan would refuse)
+    values = values / np.float32(divisor) if divisor != 1.0 else values.clip(0, 1)
+    return torch.from_numpy(np.ascontiguousarray(values))
+
+
 def _resolve_weights(weights):
     if isinstance(weights, (list, tuple)):
         return list(weights)
@@ -650,6 +705,13 @@ class StyleTransfer:
     # number for every layer of the list, or a sequence with a number or None per layer
     content_eps = None
     style_eps = None
+    # Spatial masks for the style statistics (read by stylize() too; the reference has none).  style_mask: which pixels of the
+    # OUTPUT take the style - a PIL image (read as 'L' / 255) or a 2-D numpy / torch array in [0, 1], resized bilinearly to
+    # every scale; the style heads then take mask-weighted moments of the iterate's taps (_hip.Plan.set_style_mask).
+    # style_image_masks: a list with one entry per style image, None or a mask of the same forms, resized to that style image
+    # at every scale: which of ITS pixels the style is taken from.  One device only.
+    style_mask = None
+    style_image_masks = None
 
     def __init__(self, devices=['cuda:0'], pooling='max', weights=None, precision='fp16x3'):
         # reference :310 defaults to ['cpu']; this build has no CPU path, so the default is the first HIP device
@@ -710,8 +772,14 @@ class StyleTransfer:
                 raise ValueError("image_type must be 'pil' or 'np_uint16'")
 
     # ---- per-scale targets (reference :425-453) ----
-    def _build_targets(self, plan, content, style_images, style_weights, scale, style_scale_fac, style_size):
+    def _build_targets(self, plan, content, style_images, style_weights, scale, style_scale_fac, style_size,
+                       style_mask=None, image_masks=None):
         device = self.devices[0]
+        # masks (_resolve_style_masks' forms): a style image's is in force on ITS plan only while its moments are taken - that
+        # plan can be the iterate's own, and this method runs again after the range guard - and the output's goes on last
+        masked = style_mask is not None or any(entry is not None for entry in image_masks or [])
+        if masked:
+            plan.set_style_mask(None)
         content_layers, style_layers = list(plan.content_layers), list(plan.style_layers)
         # fp16x3's activation-aware range guard (cold path, st_plan_range_guard): the forward arithmetic is checked on every
         # image BEFORE its features become targets; the closure's gradients are checked in stylize() once the targets exist
@@ -737,6 +805,9 @@ class StyleTransfer:
             if not style_layers:
                 continue
             splan.forward(style, max(style_layers))
+            image_mask = image_masks[i] if image_masks else None
+            if image_mask is not None:
+                splan.set_style_mask(_sized_mask(image_mask, sw, sh))
             for layer in style_layers:
                 mean, srm = splan.moments(layer)
                 mean *= style_weights[i]
@@ -746,8 +817,12 @@ class StyleTransfer:
                 else:
                     blended[layer][0].add_(mean)
                     blended[layer][1].add_(srm)
+            if image_mask is not None:
+                splan.set_style_mask(None)
         for idx, layer in enumerate(style_layers):
             plan.set_style_target(idx, *blended[layer])
+        if style_mask is not None:
+            plan.set_style_mask(_sized_mask(style_mask, plan.width, plan.height))
 
     def _guard_rows(self, rows_image, blended=None, content_weight=None, tv_weight=None):
         """st_plan_range_guard on a block of image rows taken as an image of its own (a whole-image plan of that size).
@@ -881,6 +956,8 @@ class StyleTransfer:
         content_loss, style_loss, content_eps, style_eps = _resolve_layer_losses(
             self.content_loss, self.style_loss, self.content_eps, self.style_eps, len(content_layers), len(style_layers),
             world=max(len(self.devices), _dist_info()[1]))
+        style_mask, image_masks = _resolve_style_masks(self.style_mask, self.style_image_masks, len(style_images),
+                                                       world=max(len(self.devices), _dist_info()[1]))
         if len(self.devices) > 1 and self._job is None:
             return _device_list_stylize(self, content_image, style_images, dict(
                 style_weights=style_weights, content_weight=content_weight, tv_weight=tv_weight, optimizer=optimizer,
@@ -1012,7 +1089,7 @@ class StyleTransfer:
                 if any(value is not None for value in content_eps + style_eps):
                     plan.set_loss_eps(content_eps, style_eps)
                 self._build_targets(plan, content.to(device), style_images, style_weights, scale, style_scale_fac,
-                                    style_size)
+                                    style_size, style_mask, image_masks)
             plan.set_loss_weights(content_weights, layer_weights, tv_weight)
             if sharded and self.model.net.precision == 'fp16x3':
                 # ... sharded: on this rank's rows of the iterate, against the scale's style targets; the union of the ranks'
@@ -1033,7 +1110,7 @@ class StyleTransfer:
                 fwd, bwd = plan.range_guard(self.image)
                 if any(fwd):
                     self._build_targets(plan, content.to(device), style_images, style_weights, scale, style_scale_fac,
-                                        style_size)
+                                        style_size, style_mask, image_masks)
                 if any(fwd) or any(bwd):
                     print(f'fp16x3 range guard: bf16x6 for the forward of convs {[i for i, v in enumerate(fwd) if v]} and '
                           f'the data gradient of convs {[i for i, v in enumerate(bwd) if v]} from now on')
