@@ -351,26 +351,7 @@ int run_forward(st_plan* p, const float* image, int last_layer, hipStream_t s, b
 
 // the moments of a tap and the step back onto it: what a head of either kind needs, and all that st_plan_moments does
 int ensure_moment_alloc(st_plan* p, StyleHead& h) {
-    if (h.allocated) return 0;
-    const size_t nn = (size_t)h.n * h.n;
-    if (plan_alloc(p, &h.srm, nn) || plan_alloc(p, &h.ssym, nn) || plan_alloc(p, &h.mean, h.n) || plan_alloc(p, &h.bvec, h.n))
-        return 1;
-    long long splits = (16ll << 20) / (long long)nn;
-    if (splits > 1024) splits = 1024;
-    if (splits < 8) splits = 8;
-    h.gram.max_splits = (int)splits;
-    if (plan_alloc(p, &h.gram.partial, (size_t)splits * nn) ||
-        plan_alloc(p, &h.gram.partial_sum, (size_t)splits * h.n))
-        return 1;
-    // the head's 1x1 gradient convolution runs on the head's own stream: its own split-K workspace, needed
-    // only while the tap is too small to fill the chip.  launch_conv keeps >= 4 chunks of 8 channels per slice,
-    // i.e. splits at most n / 32 ways, and never beyond kConvScratchFloats.
-    const long long wg = ((h.npix_local + 255) / 256) * (h.n / 64);
-    if (wg < 512) {
-        size_t need = (size_t)(h.n / 32) * h.n * (size_t)h.npix_local;
-        if (need > kConvScratchFloats) need = kConvScratchFloats;
-        if (plan_alloc(p, &h.conv_scratch, need)) return 1;
-    }
+    if (!h.allocated && alloc_head_moments(h, head_gram_split_cap(h.n), /*with_step=*/true, PlanAlloc{p})) return 1;
     h.allocated = true;
     return 0;
 }
@@ -382,14 +363,8 @@ int ensure_style_alloc(st_plan* p, StyleHead& h, int kind) {
     const size_t nn = (size_t)h.n * h.n;
     if (kind == 1) return h.gram_t ? 0 : plan_alloc(p, &h.gram_t, nn);
     if (h.w2_allocated) return 0;
-    float** mats[] = {&h.cov_t, &h.root_t, &h.cov, &h.tmat, &h.mmat, &h.root, &h.gm, &h.dt, &h.dcov};
-    for (float** m : mats)
-        if (!*m && plan_alloc(p, m, nn)) return 1;
-    if ((!h.mean_t && plan_alloc(p, &h.mean_t, h.n)) || (!h.gdiag && plan_alloc(p, &h.gdiag, 64))) return 1;
-    float* nsbase = nullptr;
-    if (plan_alloc(p, &nsbase, ns_workspace_floats(h.n))) return 1;
-    ns_workspace_carve(h.ns, nsbase, h.n);
-    if (ns_workspace_reset(h.ns, nullptr)) return 1;
+    const PlanAlloc alloc{p};
+    if (alloc(&h.cov_t, nn) || alloc(&h.root_t, nn) || alloc(&h.mean_t, h.n) || alloc_head_w2(h, alloc)) return 1;
     ST_HIP(hipStreamSynchronize(nullptr));        // (the heads' streams are non-blocking: nothing orders them behind the null stream)
     h.w2_allocated = true;
     return 0;
@@ -442,41 +417,29 @@ void mask_head_site(const st_plan* p, HeadSite& at, int op) {
 int moments_of_tap(st_plan* p, const HeadSite& at, float* mean_out, float* srm_out, hipStream_t s, float* cov_out) {
     StyleHead& h = *at.h;
     const Node& tap = *at.tap;
-    const int idx = at.slot;
     // (relu1_1 in the closure: conv1_1's launch has left the partials of its workgroups - run_forward)
     // (a mask set since that forward: the partials are plain sums, take the masked ones)
-    const bool fused = idx == 0 && p->gram1_fused && !at.sqrt_mask;
-    const int splits = fused ? p->gram1_splits : gram_choose_splits(h.n, h.npix_local, h.gram.max_splits);
+    const bool fused = at.slot == 0 && p->gram1_fused && !at.sqrt_mask;
+    const int given = fused ? p->gram1_splits : (ablate_side() & 1) ? gram_choose_splits(h.n, h.npix_local, h.gram.max_splits) : 0;
     // ST_GRAM_F32=1 (attribution runs, tools/grad_attribution.py): the moments on the exact fp32 matrix pipe in every mode
     static Option gram_f32("ST_GRAM_F32", 0);
-    auto gram = [&] {
-        if (!fused && !(ablate_side() & 1) &&
-            launch_gram_partial(tap.y, h.n, h.npix_local, splits, h.gram, s,
-                                (p->net->conv_elem == 1 && !gram_f32.get()) ? tap.y_amax : nullptr, at.sqrt_mask))
-            return 1;
-        return launch_gram_finalize(h.gram, h.n, h.npix, splits, mean_out, srm_out, s, cov_out, at.eps, at.mask_sum);
-    };
+    HeadMoments m;
+    m.feat = tap.y; m.mean = mean_out; m.srm = srm_out; m.cov = cov_out; m.eps = at.eps;
+    if (!given && p->net->conv_elem == 1 && !gram_f32.get()) m.bound = tap.y_amax;
+    m.sqrt_mask = at.sqrt_mask; m.mask_sum = at.mask_sum; m.given_splits = given;
     // relu1_1's Gram (C = 64) reads its tap once and has 64 MACs per element on the 16-bit pipe: HBM-bound
-    if (idx == 0 && !fused) return hbm_profiled(p, HBM_GRAM1, 4.0 * h.n * (double)h.npix_local, s, gram);
-    return gram();
+    if (at.slot == 0 && !fused) return hbm_profiled(p, HBM_GRAM1, 4.0 * h.n * (double)h.npix_local, s, [&] { return head_moments(h, m, s); });
+    return head_moments(h, m, s);
 }
 
-// raw sums over the local pixels: sums = [F F^T (C*C) | F 1 (C)]  (strip mode, before the all-reduce)
+// raw sums over the local pixels: sums = [F F^T (C*C) | F 1 (C)]  (strip mode, before the all-reduce): normaliser 1, outputs swapped
 int moment_sums_of_tap(st_plan* p, int j, float* sums, hipStream_t s) {
     StyleHead& h = p->head[p->style_op[j]];
     const Node& tap = node_at(p, p->style_op[j]);
-    const int splits = gram_choose_splits(h.n, h.npix_local, h.gram.max_splits);
-    if (launch_gram_partial(tap.y, h.n, h.npix_local, splits, h.gram, s, p->net->conv_elem == 1 ? tap.y_amax : nullptr))
-        return 1;
-    return launch_gram_finalize(h.gram, h.n, /*N=*/1, splits, sums + (size_t)h.n * h.n, sums, s);
-}
-
-GemmBatch one_gemm(int n, const float* a, const float* b, float* d, int ta, int tb) {
-    GemmBatch g{};
-    g.n = n; g.count = 1;
-    g.p[0].a1 = a; g.p[0].b1 = b; g.p[0].d = d; g.p[0].ta1 = ta; g.p[0].tb1 = tb;
-    g.p[0].epilogue = EPI_SCALE; g.p[0].c = 1.f;
-    return g;
+    HeadMoments m;
+    m.feat = tap.y; m.mean = sums + (size_t)h.n * h.n; m.srm = sums; m.norm = 1;
+    if (p->net->conv_elem == 1) m.bound = tap.y_amax;
+    return head_moments(h, m, s);
 }
 
 // everything after the moments (h.mean, h.srm) are known, in two parts: the C x C work - covariance, A cov A, the NS
@@ -516,17 +479,10 @@ int style_head_chain(st_plan* p, const HeadSite& at, hipStream_t s, bool cov_rea
     if (tl) ST_HIP(hipEventRecord(tlh[0], s));
     // (cov_ready: the Gram kernel's finalize pass wrote the covariance along with the moments)
     if (!cov_ready && launch_cov_from_moments(h.mean, h.srm, h.cov, n, at.eps, s)) return 1;
-    // sqrt_term = sqrtm(cov_sqrt @ cov @ cov_sqrt)                       (style_transfer.py:179)
-    if (launch_gemm_batch(one_gemm(n, h.root_t, h.cov, h.tmat, 0, 0), s)) return 1;
-    // (n = 512: the Frobenius norms the two chains open with - of M and of the root, sqrtm.py:16,38 - come out of the
-    // products that make those matrices instead of two launches of their own on relu5_1's critical path)
-    GemmBatch mm = one_gemm(n, h.tmat, h.root_t, h.mmat, 0, 0);
-    const int m_partials = gemm_sumsq_fusable(n) ? (n / 32) * (n / 32) : 0;
-    if (m_partials) mm.p[0].sumsq_partials = h.ns.scalars + 8;
-    if (launch_gemm_batch(mm, s)) return 1;
-    // the loss term (style_transfer.py:178-181) and the seed dL/d root = gdiag * I ride in the backward chain's opening
-    // kernel (one launch less on the iteration's critical path); then the Lyapunov recurrence -> dL/dM
-    const W2LossJob job{h.mean, h.mean_t, h.cov, h.cov_t, h.root, n, w, at.loss, h.gdiag};
+    int m_partials = 0;
+    if (w2_open(h, h.root_t, s, &m_partials)) return 1;
+    // (w2_loss_job rides in the backward chain's opening kernel: one launch less on the critical path); then the Lyapunov recurrence -> dL/dM
+    const W2LossJob job = w2_loss_job(h, h.mean_t, h.cov_t, w, at.loss);
     if (idx >= 0 && ns_chain_combined() && (ns_chain_mask() & (idx == 4 ? 4 : idx == 3 ? 2 : 1))) {
         // round 5: both recurrences and the loss scalars in ONE persistent launch (st_nschain.hip)
         const float* mm1[1] = {h.mmat};
@@ -543,11 +499,7 @@ int style_head_chain(st_plan* p, const HeadSite& at, hipStream_t s, bool cov_rea
         if (ns_sqrt_backward(h.root, nullptr, h.gdiag, h.gm, n, h.ns, s, &job, root_partials)) return 1;
     }
     if (tl) ST_HIP(hipEventRecord(tlh[2], s));
-    // M = (A cov) A  with A = cov_sqrt (constant):  d cov = A^T (G A^T)
-    if (launch_gemm_batch(one_gemm(n, h.gm, h.root_t, h.dt, 0, 1), s)) return 1;
-    if (launch_gemm_batch(one_gemm(n, h.root_t, h.dt, h.dcov, 1, 0), s)) return 1;
-    const bool f16 = p->net->conv_elem == 1;
-    return launch_style_grad_finish(h.dcov, h.mean, h.mean_t, n, w, h.npix, h.ssym, h.bvec, s, f16 ? h.s_amax : nullptr, at.mask_sum);
+    return w2_close(h, h.mean_t, h.root_t, w, h.ssym, h.bvec, p->net->conv_elem == 1 ? h.s_amax : nullptr, at.mask_sum, s);
 }
 
 // The three shallow heads (relu1_1, relu2_1, relu3_1: C = 64, 128, 256) with their Newton-Schulz chains in LOCKSTEP on one
@@ -594,7 +546,7 @@ int style_heads_shallow_lockstep(st_plan* p, hipStream_t s, const int* idx, int 
     for (int l = 0; l < lanes; ++l) { mm[l] = h[l]->mmat; roots[l] = h[l]->root; ws[l] = &h[l]->ns; }
     W2LossJob jobs[3];
     for (int l = 0; l < lanes; ++l)
-        jobs[l] = W2LossJob{h[l]->mean, h[l]->mean_t, h[l]->cov, h[l]->cov_t, h[l]->root, n[l], at[l].weight, at[l].loss, h[l]->gdiag};
+        jobs[l] = w2_loss_job(*h[l], h[l]->mean_t, h[l]->cov_t, at[l].weight, at[l].loss);
     const float* croots[3] = {};
     const float* gd[3] = {};
     float* gm[3] = {};
@@ -631,33 +583,20 @@ static bool head5_masks_its_gradient() {
 
 int style_head_gradient(st_plan* p, const HeadSite& at, hipStream_t s) {
     StyleHead& h = *at.h;
-    const int idx = at.slot;
-    const int n = h.n;
     const Node& tap = *at.tap;
     const bool f16 = p->net->conv_elem == 1;
-    // dF = Ssym F + b 1^T : a 1x1 convolution over the tap; WRITES the tap's gradient buffer (general closure: its seed buffer)
-    ConvProblem c{};
-    c.in = tap.y; c.mask = nullptr; c.wgt = h.ssym; c.bias = h.bvec; c.out = at.grad;
-    c.cin = n; c.cout = n; c.height = tap.h; c.width = tap.w; c.taps = 1; c.relu = 0; c.accumulate = 0;
-    c.out_amax = f16 ? at.grad_amax : nullptr;
     static Option head_f32("ST_HEAD_1X1_F32", 0);          // attribution runs: the heads' 1x1 gradient step in exact fp32
-    if (f16 && !head_f32.get()) {       // large taps: fp16x3 1x1 kernel (st_conv1x1.hip); launch_conv keeps split-K problems on fp32
-        c.planes = 2; c.elem = 1; c.amax_word = tap.y_amax; c.wgt_amax = h.s_amax;
-    }
-    c.scratch = h.conv_scratch;
     // relu5_1's gradient is final as this launch leaves it (nothing accumulates into the top of the trunk), so its
     // threshold_backward is applied HERE, by the producer, like everywhere else in the backward pass - and conv5_1's data
     // gradient stages one operand stream and runs on the producer / consumer kernel (head5_masks_its_gradient)
-    if (idx == 4 && head5_masks_its_gradient()) c.out_mask = tap.y;
+    const float* out_mask = (at.slot == 4 && head5_masks_its_gradient()) ? tap.y : nullptr;
     if (ablate_side() & 2) return 0;
-    const long long npix = (long long)tap.h * tap.w;
-    if (head_dgrad_small_applies(n, npix))       // a tap of <= 1024 pixels: one small-GEMM launch instead of split-K + reduce
-        return hbm_profiled(p, HBM_HEAD_1X1, 2.0 * n * (double)npix * sizeof(float), s, [&] {
-            return launch_head_dgrad_small(h.ssym, tap.y, h.bvec, c.out_mask, at.grad, n, npix, c.out_amax, s);
-        });
+    // dF = Ssym F + b 1^T : WRITES the tap's gradient buffer (general closure: its seed buffer)
     // (not part of the `roofline` bracket, which is the 3x3 trunk kernel's: on the large taps this step is HBM-bound -
     // read F, write dF - and reported under roofline_hbm)
-    return hbm_profiled(p, HBM_HEAD_1X1, 2.0 * n * (double)tap.h * tap.w * sizeof(float), s, [&] { return launch_conv(c, s); });
+    return hbm_profiled(p, HBM_HEAD_1X1, 2.0 * h.n * (double)tap.h * tap.w * sizeof(float), s, [&] {
+        return head_step(h, tap.y, tap.h, tap.w, at.grad, s, f16 && !head_f32.get(), tap.y_amax, f16 ? at.grad_amax : nullptr, out_mask);
+    });
 }
 
 // kProgram[op] is one of the listed content or style layers

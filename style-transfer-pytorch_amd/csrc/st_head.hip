@@ -2,35 +2,24 @@
 // welded to an st_plan, and the pointwise terms - MSE, scaled MSE, TV - as value / gradient pairs whose upstream gradient is a
 // DEVICE scalar (autograd's grad_output, the product of Scale / SumLoss: never read on the host).
 //
-// A head runs the plan's own sequence with weight 1 on the plan-free launchers of st_common.h:
-//   moments    max |F| (fp16x3 only), Gram partials, finalize -> mean, srm (W2: + cov = srm - mean mean^T + eps I)
-//   W2         A cov A, the Newton-Schulz forward chain, the loss term in the Lyapunov chain's opening kernel, d cov -> (Ssym, b)
-//   Gram       the scaled-MSE sums of srm against the target, D + D^T -> (Ssym, 0)
-//   backward   (u Ssym, u b) and the bound of u Ssym by head_scale_kernel, then the 1x1 step dF = (u Ssym) F + (u b) 1^T
-// What the plan knows and a head must find out: the operand bound of the fp16x3 kernels.  A trunk kernel leaves max |y| of the
+// A head runs st_head_core.h's sequence - a plan's heads' own, launch for launch - on its own StyleHead with weight 1 and no mask;
+// its backward is (u Ssym, u b) and the bound of u Ssym by head_scale_kernel, the one head kernel of this file, then head_step.
+// What a plan knows and a head must find out: the operand bound of the fp16x3 kernels.  A trunk kernel leaves max |y| of the
 // tap it writes; here the tensor is whatever autograd hands over - signed, possibly all zeros (bound 0: scale_exp gives 2^0,
-// the planes are exact zeros and the bias term alone makes the result) - so launch_amax measures it, once per forward, into
+// the planes are exact zeros and the bias term alone makes the result) - so head_moments measures it, once per forward, into
 // the per-call state that the backward reads.  eps is the module's, where the plan passes its entry's (kCovEps / kScaledMseEps by default).
 #include <cstdint>
 #include <vector>
 
 #include "../../include/st_amd.h"
-#include "st_common.h"
+#include "st_head_core.h"
 
 struct st_head {
-    int kind = 0, n = 0, height = 0, width = 0, precision = 0;
-    long long npix = 0;
+    int kind = 0, height = 0, width = 0, precision = 0;
     long long bytes = 0;
     std::vector<void*> allocations;
-    st::GramWorkspace gram{};
-    float *mean = nullptr, *srm = nullptr;                 // this forward's moments
-    float *ssym_u = nullptr, *b_u = nullptr;               // backward: (Ssym, b) scaled by the upstream gradient
-    float* conv_scratch = nullptr;                         // split-K workspace of the 1x1 step (small taps only)
-    unsigned int *feat_bound = nullptr, *ssym_bound = nullptr;     // fp16x3: max |F| of a forward without state, max |u Ssym|
-    // W2 only
-    float *cov = nullptr, *tmat = nullptr, *mmat = nullptr, *root = nullptr, *gm = nullptr, *dt = nullptr, *dcov = nullptr,
-          *gdiag = nullptr;
-    st::NSWorkspace ns{};
+    st::StyleHead w;                 // this forward's moments and W2 matrices; (ssym, bvec, s_amax): the backward's (u Ssym, u b), max |u Ssym|
+    unsigned int* feat_bound = nullptr;                    // fp16x3: max |F| of a forward without state
     // Gram only
     float *kind_partials = nullptr, *totals = nullptr;
     unsigned int* ticket = nullptr;
@@ -50,7 +39,7 @@ int head_alloc(st_head* h, float** out, size_t floats) {
     return 0;
 }
 
-size_t state_floats(const st_head* h) { return (size_t)h->n * h->n + h->n + kAmaxWordUints; }
+size_t state_floats(const st_head* h) { return (size_t)h->w.n * h->w.n + h->w.n + kAmaxWordUints; }
 
 // (u Ssym, u b) and the bound on max |u Ssym| for the fp16x3 1x1 step; one workgroup per row.  u Ssym stays exactly symmetric.
 __global__ __launch_bounds__(256) void head_scale_kernel(const float* __restrict__ ssym, const float* __restrict__ bvec,
@@ -303,26 +292,12 @@ int diff_grad(const float* x, const float* target, long long count, const float*
     return 0;
 }
 
-// max |F| into `bound` (fp16x3), the Gram partials, and the finalize pass: mean, srm and (cov != nullptr) the covariance
-int head_moments(st_head* h, const float* feat, unsigned int* bound, float* mean, float* srm, float* cov, float eps,
-                 hipStream_t s) {
-    const bool f16 = h->precision == 4;
-    const long long count = (long long)h->n * h->npix;
-    if (f16) {
-        ST_HIP(hipMemsetAsync(bound, 0, kAmaxWordUints * sizeof(unsigned int), s));
-        if (launch_amax(feat, count, bound, 0, s)) return 1;
-    }
-    const int splits = gram_choose_splits(h->n, h->npix, h->gram.max_splits);
-    if (launch_gram_partial(feat, h->n, h->npix, splits, h->gram, s, f16 ? bound : nullptr)) return 1;
-    return launch_gram_finalize(h->gram, h->n, h->npix, splits, mean, srm, s, cov, eps);
-}
-
-GemmBatch one_product(int n, const float* a, const float* b, float* d, int ta, int tb) {
-    GemmBatch g{};
-    g.n = n; g.count = 1;
-    g.p[0].a1 = a; g.p[0].b1 = b; g.p[0].d = d; g.p[0].ta1 = ta; g.p[0].tb1 = tb;
-    g.p[0].epilogue = EPI_SCALE; g.p[0].c = 1.f;
-    return g;
+// this forward's moments, with max |F| measured into `bound` first (fp16x3); cov != nullptr: the covariance too
+int moments_of(st_head* h, const float* feat, unsigned int* bound, float* mean, float* srm, float* cov, float eps, hipStream_t s) {
+    HeadMoments m;
+    m.feat = feat; m.mean = mean; m.srm = srm; m.cov = cov; m.eps = eps;
+    if (h->precision == 4) { m.bound = bound; m.measure_bound = true; }
+    return head_moments(h->w, m, s);
 }
 
 }  // namespace
@@ -342,44 +317,27 @@ int st_head_create(st_head** out, int kind, int channels, int height, int width,
                "st_head_create: a %d x %d tap: height and width >= 1, fewer than 2^24 pixels", height, width);
     ST_REQUIRE(precision == 0 || precision == 4, "st_head_create: precision must be 0 (fp32) or 4 (fp16x3)");
     st_head* h = new st_head;
-    h->kind = kind; h->n = channels; h->height = height; h->width = width; h->precision = precision;
-    h->npix = (long long)height * width;
-    const int n = channels;
-    const size_t nn = (size_t)n * n;
+    h->kind = kind; h->height = height; h->width = width; h->precision = precision;
+    StyleHead& w = h->w;
+    w.n = channels;
+    w.npix = w.npix_local = (long long)height * width;
     auto fail = [&] { st_head_destroy(h); return 1; };
-    // the moments' workspace and the 1x1 step's split-K scratch, sized as a plan sizes its heads' (ensure_moment_alloc)
-    long long splits = (16ll << 20) / (long long)nn;
-    splits = std::min(1024ll, std::max(8ll, splits));
-    // ... of which this one shape ever uses gram_choose_splits' pick (a plan's head may be handed fewer local pixels later)
-    splits = gram_choose_splits(n, h->npix, (int)splits);
-    h->gram.max_splits = (int)splits;
-    if (head_alloc(h, &h->gram.partial, (size_t)splits * nn) || head_alloc(h, &h->gram.partial_sum, (size_t)splits * n) ||
-        head_alloc(h, &h->mean, n))
-        return fail();
-    const bool full = kind != 2;          // (a moments-only head: the Gram workspace, a mean and the bound word)
-    if (full && (head_alloc(h, &h->srm, nn) || head_alloc(h, &h->ssym_u, nn) || head_alloc(h, &h->b_u, n))) return fail();
-    if (full && ((h->npix + 255) / 256) * (n / 64) < 512) {
-        const size_t need = std::min((size_t)(n / 32) * n * (size_t)h->npix, kConvScratchFloats);
-        if (head_alloc(h, &h->conv_scratch, need)) return fail();
-    }
+    auto alloc = [h](float** out, size_t floats) { return head_alloc(h, out, floats); };
+    // sized by the routines that size a plan's heads - except that of the split cap this one shape ever uses gram_choose_splits'
+    // pick (a plan's head may be handed fewer local pixels later).  A moments-only head: the Gram workspace, a mean, the bound words.
+    if (alloc_head_moments(w, gram_choose_splits(w.n, w.npix, head_gram_split_cap(w.n)), /*with_step=*/kind != 2, alloc)) return fail();
     float* words = nullptr;
     if (head_alloc(h, &words, 2 * kAmaxWordUints)) return fail();
     h->feat_bound = reinterpret_cast<unsigned int*>(words);
-    h->ssym_bound = h->feat_bound + kAmaxWordUints;
+    w.s_amax = h->feat_bound + kAmaxWordUints;
     if (hipMemset(words, 0, 2 * kAmaxWordUints * sizeof(float)) != hipSuccess) { set_error("st_head_create: hipMemset failed"); return fail(); }
     if (kind == 1) {
         float* tick = nullptr;
         if (head_alloc(h, &h->kind_partials, 2 * kStreamBlocks) || head_alloc(h, &h->totals, 64) || head_alloc(h, &tick, 64)) return fail();
         h->ticket = reinterpret_cast<unsigned int*>(tick);
         if (hipMemset(tick, 0, 64 * sizeof(float)) != hipSuccess) { set_error("st_head_create: hipMemset failed"); return fail(); }
-    } else if (kind == 0) {
-        float** mats[] = {&h->cov, &h->tmat, &h->mmat, &h->root, &h->gm, &h->dt, &h->dcov};
-        for (float** m : mats)
-            if (head_alloc(h, m, nn)) return fail();
-        float* nsbase = nullptr;
-        if (head_alloc(h, &h->gdiag, 64) || head_alloc(h, &nsbase, ns_workspace_floats(n))) return fail();
-        ns_workspace_carve(h->ns, nsbase, n);
-        if (ns_workspace_reset(h->ns, nullptr)) return fail();
+    } else if (kind == 0 && alloc_head_w2(w, alloc)) {
+        return fail();
     }
     if (hipStreamSynchronize(nullptr) != hipSuccess) { set_error("st_head_create: synchronise failed"); return fail(); }
     *out = h;
@@ -400,7 +358,7 @@ long long st_head_state_floats(const st_head* h) { return h ? (long long)state_f
 int st_head_moments(st_head* h, const float* feat, float* mean_out, float* srm_out, void* stream) {
     ST_REQUIRE(h && feat && srm_out, "st_head_moments: null argument");
     ST_REQUIRE(aligned16(feat), "st_head_moments: feat must be 16-byte aligned");
-    return head_moments(h, feat, h->feat_bound, mean_out ? mean_out : h->mean, srm_out, nullptr, 0.f, static_cast<hipStream_t>(stream));
+    return moments_of(h, feat, h->feat_bound, mean_out ? mean_out : h->w.mean, srm_out, nullptr, 0.f, static_cast<hipStream_t>(stream));
 }
 
 int st_head_forward(st_head* h, const float* feat, const float* mean_t, const float* cov_t, const float* root_t,
@@ -409,7 +367,8 @@ int st_head_forward(st_head* h, const float* feat, const float* mean_t, const fl
     ST_REQUIRE(h->kind != 2, "st_head_forward: a moments-only head");
     ST_REQUIRE(aligned16(feat) && aligned16(state), "st_head_forward: feat and state must be 16-byte aligned");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int n = h->n;
+    StyleHead& w = h->w;
+    const int n = w.n;
     const size_t nn = (size_t)n * n;
     float* ssym = state;
     float* bvec = state ? state + nn : nullptr;
@@ -417,31 +376,21 @@ int st_head_forward(st_head* h, const float* feat, const float* mean_t, const fl
     if (h->kind == 1) {
         // StyleLoss.forward (style_transfer.py:141-142): ScaledMSELoss of the Gram matrix against its target
         ST_REQUIRE(gram_t, "st_head_forward: a Gram head needs gram_t");
-        if (head_moments(h, feat, bound, h->mean, h->srm, nullptr, 0.f, s)) return 1;
-        if (launch_scaled_mse_sums(h->srm, gram_t, (long long)nn, 1.f, h->kind_partials, h->totals, loss_out, s, h->ticket, eps)) return 1;
-        if (!state) return 0;
-        return launch_gram_grad_finish(h->srm, gram_t, h->totals, n, 1.f, h->npix, ssym, bvec, s, nullptr);
+        if (moments_of(h, feat, bound, w.mean, w.srm, nullptr, 0.f, s)) return 1;
+        return gram_body(w, gram_t, 1.f, eps, h->kind_partials, h->totals, h->ticket, loss_out, ssym, bvec, nullptr, 0.f, s);
     }
     // StyleLossW2.forward (style_transfer.py:174-181)
     ST_REQUIRE(mean_t && cov_t && root_t, "st_head_forward: a W2 head needs mean_t, cov_t and root_t");
-    if (head_moments(h, feat, bound, h->mean, h->srm, h->cov, eps, s)) return 1;
-    // sqrt_term = sqrtm(cov_sqrt @ cov @ cov_sqrt)                       (style_transfer.py:179)
-    if (launch_gemm_batch(one_product(n, root_t, h->cov, h->tmat, 0, 0), s)) return 1;
-    GemmBatch mm = one_product(n, h->tmat, root_t, h->mmat, 0, 0);
-    const int m_partials = gemm_sumsq_fusable(n) ? (n / 32) * (n / 32) : 0;
-    if (m_partials) mm.p[0].sumsq_partials = h->ns.scalars + 8;
-    if (launch_gemm_batch(mm, s)) return 1;
-    int root_partials = 0;
-    if (ns_sqrt_forward(h->mmat, h->root, n, h->ns, s, m_partials, &root_partials)) return 1;
+    if (moments_of(h, feat, bound, w.mean, w.srm, w.cov, eps, s)) return 1;
+    int m_partials = 0, root_partials = 0;
+    if (w2_open(w, root_t, s, &m_partials)) return 1;
+    if (ns_sqrt_forward(w.mmat, w.root, n, w.ns, s, m_partials, &root_partials)) return 1;
     if (!state)       // the value alone: no Lyapunov chain to ride in
-        return launch_style_loss_value(h->mean, mean_t, h->cov, cov_t, h->root, n, 1.f, loss_out, h->gdiag, s);
+        return launch_style_loss_value(w.mean, mean_t, w.cov, cov_t, w.root, n, 1.f, loss_out, w.gdiag, s);
     // the loss term and the seed dL/d root = gdiag I in the backward chain's opening kernel, then dL/dM
-    const W2LossJob job{h->mean, mean_t, h->cov, cov_t, h->root, n, 1.f, loss_out, h->gdiag};
-    if (ns_sqrt_backward(h->root, nullptr, h->gdiag, h->gm, n, h->ns, s, &job, root_partials)) return 1;
-    // M = (A cov) A  with A = cov_sqrt (constant):  d cov = A^T (G A^T)
-    if (launch_gemm_batch(one_product(n, h->gm, root_t, h->dt, 0, 1), s)) return 1;
-    if (launch_gemm_batch(one_product(n, root_t, h->dt, h->dcov, 1, 0), s)) return 1;
-    return launch_style_grad_finish(h->dcov, h->mean, mean_t, n, 1.f, h->npix, ssym, bvec, s, nullptr);
+    const W2LossJob job = w2_loss_job(w, mean_t, cov_t, 1.f, loss_out);
+    if (ns_sqrt_backward(w.root, nullptr, w.gdiag, w.gm, n, w.ns, s, &job, root_partials)) return 1;
+    return w2_close(w, mean_t, root_t, 1.f, ssym, bvec, nullptr, 0.f, s);
 }
 
 int st_head_backward(st_head* h, const float* feat, const float* state, const float* upstream, float* grad_feat, void* stream) {
@@ -449,26 +398,15 @@ int st_head_backward(st_head* h, const float* feat, const float* state, const fl
     ST_REQUIRE(h->kind != 2, "st_head_backward: a moments-only head");
     ST_REQUIRE(aligned16(feat) && aligned16(state) && aligned16(grad_feat), "st_head_backward: feat, state and grad_feat must be 16-byte aligned");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int n = h->n;
+    const StyleHead& w = h->w;
+    const int n = w.n;
     const size_t nn = (size_t)n * n;
     const bool f16 = h->precision == 4;
-    if (f16) ST_HIP(hipMemsetAsync(h->ssym_bound, 0, kAmaxWordUints * sizeof(unsigned int), s));
-    hipLaunchKernelGGL(head_scale_kernel, dim3(n), dim3(256), 0, s, state, state + nn, upstream, n, h->ssym_u, h->b_u,
-                       f16 ? h->ssym_bound : nullptr);
+    if (f16) ST_HIP(hipMemsetAsync(w.s_amax, 0, kAmaxWordUints * sizeof(unsigned int), s));
+    hipLaunchKernelGGL(head_scale_kernel, dim3(n), dim3(256), 0, s, state, state + nn, upstream, n, w.ssym, w.bvec, f16 ? w.s_amax : nullptr);
     ST_LAUNCH_CHECK();
-    // dF = (u Ssym) F + (u b) 1^T: the plan's 1x1 step (style_head_gradient) without a mask or a consumer's bound
-    if (head_dgrad_small_applies(n, h->npix))
-        return launch_head_dgrad_small(h->ssym_u, feat, h->b_u, nullptr, grad_feat, n, h->npix, nullptr, s);
-    ConvProblem c{};
-    c.in = feat; c.wgt = h->ssym_u; c.bias = h->b_u; c.out = grad_feat;
-    c.cin = n; c.cout = n; c.height = h->height; c.width = h->width; c.taps = 1;
-    if (f16) {       // large taps: the fp16x3 1x1 kernel; launch_conv keeps split-K problems on fp32
-        c.planes = 2; c.elem = 1;
-        c.amax_word = const_cast<unsigned int*>(reinterpret_cast<const unsigned int*>(state + nn + n));
-        c.wgt_amax = h->ssym_bound;
-    }
-    c.scratch = h->conv_scratch;
-    return launch_conv(c, s);
+    // dF = (u Ssym) F + (u b) 1^T: the plan's 1x1 step without a mask or a consumer's bound, on the bound the forward left in the state
+    return head_step(w, feat, h->height, h->width, grad_feat, s, f16, const_cast<unsigned int*>(reinterpret_cast<const unsigned int*>(state + nn + n)));
 }
 
 long long st_op_reduce_scratch_floats(void) { return kReduceScratchFloats; }

@@ -1,5 +1,6 @@
-// Internal to libst_amd.so: the VGG-19 program, the plan's nodes and style heads, st_net / st_plan, and the plan helpers
+// Internal to libst_amd.so: the VGG-19 program, the plan's nodes and head sites, st_net / st_plan, and the plan helpers
 // that more than one of st_api.hip, st_closure.hip, st_taps.hip, st_mask.hip, st_strip.hip and st_range_guard.hip call.
+// (StyleHead and a head's launch sequence: st_head_core.h, shared with st_head.hip; the wrappers below add the plan's part.)
 #pragma once
 
 #include <functional>
@@ -8,6 +9,7 @@
 
 #include "../../include/st_amd.h"
 #include "st_common.h"
+#include "st_head_core.h"
 
 namespace st {
 
@@ -44,26 +46,6 @@ struct Node {
     unsigned int* y_amax = nullptr;
     unsigned int* g_amax = nullptr;
     size_t count() const { return (size_t)c * h * w; }
-};
-
-struct StyleHead {
-    int n = 0;            // channels
-    long long npix = 0;        // GLOBAL pixel count of the tap (normalisation of the moments)
-    long long npix_local = 0;  // pixels held by this plan (== npix unless strip-sharded)
-    unsigned int* s_amax = nullptr;   // fp16x3: bound on max |ssym| of this pass (one of plan->amax_word's bounds)
-    bool target_set = false;
-    bool joined_in_build = false;    // phase construction: this head's broadcast + gradient step have been placed
-    // targets
-    float *mean_t = nullptr, *cov_t = nullptr, *root_t = nullptr;
-    // per-iteration
-    float *mean = nullptr, *srm = nullptr, *cov = nullptr, *tmat = nullptr, *mmat = nullptr, *root = nullptr,
-          *gm = nullptr, *dt = nullptr, *dcov = nullptr, *ssym = nullptr, *bvec = nullptr, *gdiag = nullptr;
-    float* conv_scratch = nullptr;     // split-K workspace of the head's 1x1 gradient conv (small taps only)
-    float* gram_t = nullptr;           // Gram kind (st_plan::style_kind[j] == 1): the target Gram matrix [n][n]
-    NSWorkspace ns{};
-    GramWorkspace gram{};
-    bool allocated = false;            // what every kind needs: the moments, their workspace, (Ssym, b), the 1x1 step's scratch
-    bool w2_allocated = false;         // ... and what only the W2 kind does: the target's root, the chains' matrices and workspace
 };
 
 // Where a W2 style head sits: head_site(p, j) for the j-th LISTED style layer in the default and strip closures, the same
@@ -299,6 +281,8 @@ constexpr int kHaloTrailer = 16;            // floats; word 0 = the sender's max
 
 // ---- st_closure.hip
 int plan_alloc(st_plan* p, float** out, size_t floats);
+// ... as the heads' allocator (st_head_core.h): a buffer that is there stays, so a call that failed half way can be made again
+struct PlanAlloc { st_plan* p; int operator()(float** out, size_t floats) const { return *out ? 0 : plan_alloc(p, out, floats); } };
 int conv_launch_profiled(st_plan* p, const ConvProblem& prob, hipStream_t s, double flops_fraction = 1.0);
 template <class F>
 int hbm_profiled(st_plan* p, int cat, double bytes, hipStream_t s, F&& launch) {

@@ -31,6 +31,7 @@
 //                           buffer (gram_head: four launches, no Newton-Schulz chain)
 //   a scaled-MSE content term   the sums and the term, then the seed written or added  (launch_scaled_mse_sums / _grad)
 // Everything around the terms - TV, the forward, the terms' total, the tap backward, the step's fold - is unchanged.
+// (Either kind's launches are st_head_core.h's, shared with the standalone modules; gram_head and style_head add the plan's part.)
 //
 // A style mask (st_plan_set_style_mask, st_mask.hip) also runs this closure, the reference's configuration under the default
 // kinds and eps included: every head's site carries sqrt(m) at its tap's level and the level's sum (mask_head_site), the Gram
@@ -140,12 +141,8 @@ float* kind_totals(st_plan* p, int k) { return p->kind_scratch + 2 * kStreamBloc
 int gram_head(st_plan* p, const HeadSite& at, int term, hipStream_t s) {
     StyleHead& h = *at.h;
     if (moments_of_tap(p, at, h.mean, h.srm, s)) return 1;
-    float* totals = kind_totals(p, term);
-    if (launch_scaled_mse_sums(h.srm, h.gram_t, (long long)h.n * h.n, at.weight, p->kind_scratch, totals, at.loss, s, p->tickets + 128,
-                               at.eps))
-        return 1;
-    if (launch_gram_grad_finish(h.srm, h.gram_t, totals, h.n, at.weight, h.npix, h.ssym, h.bvec, s,
-                                p->net->conv_elem == 1 ? h.s_amax : nullptr, at.mask_sum))
+    if (gram_body(h, h.gram_t, at.weight, at.eps, p->kind_scratch, kind_totals(p, term), p->tickets + 128, at.loss, h.ssym, h.bvec,
+                  p->net->conv_elem == 1 ? h.s_amax : nullptr, at.mask_sum, s))
         return 1;
     return style_head_gradient(p, at, s);
 }
