@@ -167,6 +167,47 @@ int st_plan_set_style_mask(st_plan* plan, const float* mask_or_null, void* strea
 int st_plan_style_mask(const st_plan* plan, int level, const float** sqrt_mask, int* h, int* w, double* sum);
 
 /*
+ * Several style regions, each with its own style (Gatys et al.'s guided transfer: sky from one painting, ground from
+ * another).  The reference has no such control; the semantics are fixed here.  R regions, 1 <= R <= 4.  Region r has a mask
+ * m_r - masks[r], [H][W] fp32 on the device with values in [0, 1], at the plan's image size, with the style mask's pyramid
+ * (above) of its own -, one target per listed style layer (st_plan_set_region_style_target) and a weight rho_r
+ * (st_plan_set_region_weights; 1 / R each after every successful call here).  With M_r the sum of m_r at the tap's level,
+ * the term of (region r, style entry j) is the module of entry j's own kind and eps - StyleLossW2 or StyleLoss - on the
+ * weighted moments
+ *     mean = sum_p m_r,p f_p / M_r,   srm = sum_p m_r,p f_p f_p^T / M_r
+ * against region r's target of that layer, times style_weight[j] * rho_r: the style mask's formulas, once per region.  The
+ * style term of entry j (st_plan_term_losses, which keeps its shape) is the fp32 sum of its regions' terms in region order;
+ * the feature gradient of the layer is sum_r (Ssym_r F + b_r 1^T) diag(m_r), accumulated in region order, and a content
+ * term of the same layer is added after it.  Masks may overlap and need not sum to 1; a pixel in no region takes no style.
+ * The content and TV terms, and st_plan_moments, see no region.
+ * While regions are in force the plan runs the general closure (csrc/st_taps.hip), on the default configuration too, for
+ * st_plan_loss_and_grad, st_plan_step, st_plan_lbfgs_step and st_plan_range_guard, on the caller's stream, launching
+ * eagerly; two closures give equal bits (one owner per gradient element, no atomics).  n_regions == 0 clears them
+ * (masks may be NULL then): the plan is then, bit for bit, one that never had any; and a plan with one region of weight 1
+ * and mask m is, bit for bit, the plan with st_plan_set_style_mask(m).  Regions and a style mask exclude each other: either
+ * setter fails, naming the other, while the other is in force - clear first.  The lists, kinds, eps, weights and the
+ * targets already set stay (a region's targets are kept in heads of its own, which this call allocates for the listed
+ * style layers; st_plan_set_taps and the kinds setters do so again - the masks and weights survive them, the targets do
+ * not).  The call is synchronous - every region's level sums are read back here, in one read-back - and invalidates a
+ * captured graph.  It fails, naming the cause, on a strip plan, for more than 4 regions, and for a region (named) whose
+ * mask holds a NaN or a value outside [0, 1] or has a level (named) that sums to 0; a refused call leaves the plan without
+ * regions.
+ */
+int st_plan_set_style_regions(st_plan* plan, int n_regions, const float* const* masks, void* stream);
+/* Borrow level `level` (0 .. 4) of region `region`'s mask as the plan keeps it: the SQUARE ROOT of the level, dense [h][w]
+ * fp32 on the device, with the level's sum M.  Any output pointer may be null.  Fails when no regions are set. */
+int st_plan_style_region(const st_plan* plan, int region, int level, const float** sqrt_mask, int* h, int* w, double* sum);
+/* st_plan_set_style_target for region `region` (0 .. R - 1) of the regions in force; region 0's target is the plan's own
+ * (st_plan_set_style_target is this call with region 0, and the only region a plan without regions has). */
+int st_plan_set_region_style_target(st_plan* plan, int region, int index, const float* mean, const float* srm, void* stream);
+/* rho_r of the regions in force: R finite host floats, used as given (not normalised); NULL restores 1 / R each.  Fails when
+ * no regions are set.  Invalidates a captured graph. */
+int st_plan_set_region_weights(st_plan* plan, const float* weights_or_null);
+/* The weighted terms of every (region, style entry) as the plan's last closure left them: *terms = device array
+ * [*regions][*styles] of floats, owned by the plan.  regions and styles may be null.  Fails when no regions are set. */
+int st_plan_region_terms(st_plan* plan, float** terms, int* regions, int* styles);
+
+/*
  * StyleTransfer.content_layers / style_layers (style_transfer.py:315-317, read by every scale at :425-453): the layers the
  * plan's closure puts its ContentLossMSE and StyleLossW2 terms on.  Each entry is a features index that st_plan_feature
  * accepts - the 13 ReLU outputs 1 3 6 8 11 13 15 17 20 22 24 26 29 and the 4 pool outputs 4 9 18 27; the reference also

@@ -447,8 +447,18 @@ int st_plan_set_style_target(st_plan* p, int index, const float* mean, const flo
     ST_REQUIRE(p && mean && srm, "st_plan_set_style_target: null argument");
     ST_REQUIRE(index >= 0 && index < p->n_style, "st_plan_set_style_target: index %d out of range (%d style layers)", index,
                p->n_style);
+    return st_plan_set_region_style_target(p, 0, index, mean, srm, stream);
+}
+
+int st_plan_set_region_style_target(st_plan* p, int region, int index, const float* mean, const float* srm, void* stream) {
+    ST_REQUIRE(p && mean && srm, "st_plan_set_region_style_target: null argument");
+    ST_REQUIRE(region >= 0 && region < std::max(p->n_regions, 1),
+               "st_plan_set_region_style_target: region %d out of range (%d style regions are set: st_plan_set_style_regions)", region,
+               p->n_regions);
+    ST_REQUIRE(index >= 0 && index < p->n_style, "st_plan_set_region_style_target: index %d out of range (%d style layers)", index,
+               p->n_style);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    StyleHead& h = p->head[p->style_op[index]];
+    StyleHead& h = region_head_at(p, region, p->style_op[index]);
     if (ensure_style_alloc(p, h, p->style_kind[index])) return 1;
     if (p->style_kind[index] == 1) {    // StyleLoss.get_target (:136-139): the second raw moment IS the Gram target; no root
         ST_HIP(hipMemcpyAsync(h.gram_t, srm, (size_t)h.n * h.n * sizeof(float), hipMemcpyDeviceToDevice, s));

@@ -762,6 +762,11 @@ int require_targets(const st_plan* p) {
     for (int j = 0; j < p->n_style; ++j)
         ST_REQUIRE(p->head[p->style_op[j]].target_set, "style target %d (features[%d]) not set (st_plan_set_style_target)", j,
                    kProgram[p->style_op[j]].feat_index);
+    for (int r = 1; r < p->n_regions; ++r)
+        for (int j = 0; j < p->n_style; ++j)
+            ST_REQUIRE(p->region_head[r - 1][p->style_op[j]].target_set,
+                       "style target %d (features[%d]) of region %d not set (st_plan_set_region_style_target)", j,
+                       kProgram[p->style_op[j]].feat_index, r);
     return 0;
 }
 

@@ -641,6 +641,14 @@ int launch_mask_pyramid(const float* mask, const int* h, const int* w, float* co
                         hipStream_t s);
 // buf [c][npix] *= sqrt_mask[npix]^2 per pixel column: the masked heads' gradient step dF = (Ssym F + b 1^T) diag(m)
 int launch_mask_columns(float* buf, const float* sqrt_mask, int channels, long long npix, hipStream_t s);
+// ---- style regions (st_plan_set_style_regions): several masks with a style each --------------------
+constexpr int kMaxRegions = 4;
+// dst [c][npix] += sqrt_mask[npix]^2 * src [c][npix] per pixel column: region r >= 1's gradient step onto the seed that region 0
+// wrote.  Two reads and one write of the tap; one thread owns an element, so the sum's order is the order of the launches.
+int launch_mask_columns_add(float* dst, const float* src, const float* sqrt_mask, int channels, long long npix, hipStream_t s);
+// out[j] = region_terms[0][j] + region_terms[1][j] + ... in region order (fp32), j < n_style; region_terms is [regions][n_style].
+// One region: out[j] takes region_terms[0][j] as it is.
+int launch_sum_region_terms(const float* region_terms, int regions, int n_style, float* out, hipStream_t s);
 // TV loss partial sums + gradient (optionally scaled by `weight`): see st_pointwise.hip
 int launch_tv(const float* image, int height, int width, float weight, float* grad, float* partials,
               float* loss_out, hipStream_t s, unsigned int* ticket = nullptr);

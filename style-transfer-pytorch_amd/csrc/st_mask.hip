@@ -13,6 +13,15 @@
 // validates the mask with the same read); the closures get it as a kernel argument.
 //
 // Here: the pyramid kernel, the pointwise kernel of the gradient step, and the two entry points.
+//
+// Style regions (st_plan_set_style_regions): R <= kMaxRegions masks with a style each - Gatys et al.'s guided transfer, the
+// formulas above once per region.  Region r has a pyramid of its own (this file's kernel, one call per region: a given mask
+// yields the bits it yields as a style mask), one target per listed style layer and a weight rho_r; the term of (region r,
+// entry j) is entry j's module on region r's weighted moments against region r's target, times style_weight[j] rho_r.  An
+// entry's term is the fp32 sum of its regions' terms in region order (sum_region_terms_kernel), and the tap's gradient
+// sum_r (Ssym_r F + b_r 1^T) diag(m_r) is accumulated in region order: region 0 writes the seed and is multiplied by m_0 as a
+// style mask is, region r >= 1 writes its 1x1 step into one scratch buffer and mask_columns_add_kernel adds m_r times it onto
+// the seed - one owner per element, no atomics, so two closures give equal bits.  The closure's part is st_taps.hip's.
 #include <cmath>
 
 #include "st_plan.h"
@@ -130,6 +139,44 @@ __global__ __launch_bounds__(256) void mask_columns_kernel(float* __restrict__ b
     }
 }
 
+// dst [c][npix] += sqrt_mask^2 * src per pixel column, with mask_columns_kernel's structure.  HBM-bound: two reads and one write
+// of the tap (the level of the mask stays in L2), so the grid is capped at kStreamBlocks workgroups striding over the buffer.
+__global__ __launch_bounds__(256) void mask_columns_add_kernel(float* __restrict__ dst, const float* __restrict__ src,
+                                                               const float* __restrict__ sqrt_mask, long long count, long long npix) {
+#pragma clang fp contract(off)
+    const long long n4 = count / 4;
+    const long long first = blockIdx.x * 256ll + threadIdx.x, stride = (long long)gridDim.x * 256;
+    f32x4* dst4 = reinterpret_cast<f32x4*>(dst);
+    const f32x4* src4 = reinterpret_cast<const f32x4*>(src);
+    for (long long i = first; i < n4; i += stride) {
+        f32x4 v = dst4[i];
+        const f32x4 a = src4[i];
+        long long px = (4 * i) % npix;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float sm = sqrt_mask[px];
+            v[e] = v[e] + (sm * sm) * a[e];
+            px = px + 1 == npix ? 0 : px + 1;
+        }
+        dst4[i] = v;
+    }
+    for (long long i = 4 * n4 + first; i < count; i += stride) {
+        const float sm = sqrt_mask[i % npix];
+        dst[i] = dst[i] + (sm * sm) * src[i];
+    }
+}
+
+// the entries' terms from their regions' terms, in region order; one region: the bits as the head wrote them
+__global__ __launch_bounds__(64) void sum_region_terms_kernel(const float* __restrict__ region_terms, int regions, int n_style,
+                                                              float* __restrict__ out) {
+#pragma clang fp contract(off)
+    const int j = threadIdx.x;
+    if (j >= n_style) return;
+    float t = region_terms[j];
+    for (int r = 1; r < regions; ++r) t = t + region_terms[(size_t)r * n_style + j];
+    out[j] = t;
+}
+
 }  // namespace
 
 int launch_mask_pyramid(const float* mask, const int* h, const int* w, float* const* sqrt_level, double* partials, double* stats,
@@ -159,6 +206,75 @@ int launch_mask_columns(float* buf, const float* sqrt_mask, int channels, long l
     return 0;
 }
 
+int launch_mask_columns_add(float* dst, const float* src, const float* sqrt_mask, int channels, long long npix, hipStream_t s) {
+    ST_REQUIRE(dst && src && sqrt_mask && channels > 0 && npix > 0, "mask columns add: bad argument");
+    const long long count = (long long)channels * npix;
+    long long blocks = (std::max(count / 4, count % 4) + 255) / 256;
+    blocks = std::min(std::max(blocks, 1ll), (long long)kStreamBlocks);
+    hipLaunchKernelGGL(mask_columns_add_kernel, dim3((unsigned)blocks), dim3(256), 0, s, dst, src, sqrt_mask, count, npix);
+    ST_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_sum_region_terms(const float* region_terms, int regions, int n_style, float* out, hipStream_t s) {
+    ST_REQUIRE(region_terms && out && regions >= 1 && regions <= kMaxRegions && n_style >= 0 && n_style <= 16,
+               "sum region terms: bad argument");
+    if (n_style == 0) return 0;
+    hipLaunchKernelGGL(sum_region_terms_kernel, dim3(1), dim3(64), 0, s, region_terms, regions, n_style, out);
+    ST_LAUNCH_CHECK();
+    return 0;
+}
+
+namespace {
+
+constexpr size_t kPyramidPartials = (size_t)kMaskLevels * kMaskPyramidBlocks * 4;
+
+// the levels' sizes and the pyramid kernel's scratch: its partials and, behind them, 8 results per region (a style mask: the first 8)
+int ensure_pyramid_scratch(st_plan* p) {
+    if (p->mask_stats) return 0;
+    p->mask_h[0] = p->H;
+    p->mask_w[0] = p->W;
+    for (int k = 1; k < kMaskLevels; ++k) {
+        p->mask_h[k] = p->pool[k - 1].h;
+        p->mask_w[k] = p->pool[k - 1].w;
+    }
+    float* mem = nullptr;
+    if (plan_alloc(p, &mem, 2 * (kPyramidPartials + 8 * kMaxRegions))) return 1;
+    p->mask_stats = reinterpret_cast<double*>(mem);
+    return 0;
+}
+
+
+// rho: the weights given, or 1 / R each
+void deal_region_weights(st_plan* p, int regions, const float* given) {
+    for (int r = 0; r < kMaxRegions; ++r) p->region_weight[r] = r >= regions ? 0.f : given ? given[r] : 1.f / (float)regions;
+}
+
+}  // namespace
+
+int ensure_region_heads(st_plan* p, int regions, const int* style_ops, int n_style, const int* kinds) {
+    if (regions <= 0) return 0;
+    if (!p->region_amax) {
+        float* mem = nullptr;
+        if (plan_alloc(p, &mem, (size_t)(kMaxRegions - 1) * 16 * kAmaxWordUints)) return 1;
+        p->region_amax = reinterpret_cast<unsigned int*>(mem);
+    }
+    if (!p->region_terms) {
+        if (plan_alloc(p, &p->region_terms, (size_t)kMaxRegions * 16)) return 1;
+        ST_HIP(hipMemset(p->region_terms, 0, (size_t)kMaxRegions * 16 * sizeof(float)));
+    }
+    for (int r = 1; r < regions; ++r)
+        for (int j = 0; j < n_style; ++j) {
+            const StyleHead& base = p->head[style_ops[j]];
+            StyleHead& h = p->region_head[r - 1][style_ops[j]];
+            h.n = base.n;
+            h.npix = base.npix;
+            h.npix_local = base.npix_local;
+            if (ensure_style_alloc(p, h, kinds[j])) return 1;
+        }
+    return 0;
+}
+
 }  // namespace st
 
 using namespace st;
@@ -176,20 +292,12 @@ int st_plan_set_style_mask(st_plan* p, const float* mask, void* stream) {
         }
         return 0;
     }
-    constexpr size_t kPartials = (size_t)kMaskLevels * kMaskPyramidBlocks * 4;
-    if (!p->mask_stats) {
-        p->mask_h[0] = p->H;
-        p->mask_w[0] = p->W;
-        for (int k = 1; k < kMaskLevels; ++k) {
-            p->mask_h[k] = p->pool[k - 1].h;
-            p->mask_w[k] = p->pool[k - 1].w;
-        }
-        for (int k = 0; k < kMaskLevels; ++k)
-            if (plan_alloc(p, &p->mask_sqrt[k], (size_t)p->mask_h[k] * p->mask_w[k])) return 1;
-        float* mem = nullptr;
-        if (plan_alloc(p, &mem, 2 * (kPartials + 8))) return 1;
-        p->mask_stats = reinterpret_cast<double*>(mem);
-    }
+    ST_REQUIRE(!p->n_regions, "st_plan_set_style_mask: %d style regions are in force on this plan (st_plan_set_style_regions): "
+               "clear them first", p->n_regions);
+    constexpr size_t kPartials = kPyramidPartials;
+    if (ensure_pyramid_scratch(p)) return 1;
+    for (int k = 0; k < kMaskLevels; ++k)
+        if (!p->mask_sqrt[k] && plan_alloc(p, &p->mask_sqrt[k], (size_t)p->mask_h[k] * p->mask_w[k])) return 1;
     // the levels are overwritten whether or not the mask is then accepted: no mask is in force until it is
     p->style_mask = false;
     invalidate_graph(p);
@@ -218,6 +326,81 @@ int st_plan_style_mask(const st_plan* p, int level, const float** sqrt_mask, int
     if (h) *h = p->mask_h[level];
     if (w) *w = p->mask_w[level];
     if (sum) *sum = p->mask_sum[level];
+    return 0;
+}
+
+int st_plan_set_style_regions(st_plan* p, int n_regions, const float* const* masks, void* stream) {
+    ST_REQUIRE(p, "st_plan_set_style_regions: null plan");
+    ST_REQUIRE(!p->strip, "st_plan_set_style_regions: strip plans take no style regions (a level's sum would span the ranks)");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // no regions are in force until every one of them is accepted
+    p->n_regions = 0;
+    invalidate_graph(p);
+    if (n_regions == 0) return 0;
+    ST_REQUIRE(n_regions >= 1 && n_regions <= kMaxRegions, "st_plan_set_style_regions: %d regions: a plan takes 1 to %d", n_regions,
+               kMaxRegions);
+    ST_REQUIRE(masks, "st_plan_set_style_regions: null list of masks");
+    for (int r = 0; r < n_regions; ++r) ST_REQUIRE(masks[r], "st_plan_set_style_regions: the mask of region %d is null", r);
+    ST_REQUIRE(!p->style_mask, "st_plan_set_style_regions: a style mask is in force on this plan (st_plan_set_style_mask): clear it first");
+    if (ensure_pyramid_scratch(p)) return 1;
+    for (int r = 0; r < n_regions; ++r)
+        for (int k = 0; k < kMaskLevels; ++k)
+            if (!p->region_sqrt[r][k] && plan_alloc(p, &p->region_sqrt[r][k], (size_t)p->mask_h[k] * p->mask_w[k])) return 1;
+    if (ensure_region_heads(p, n_regions, p->style_op, p->n_style, p->style_kind)) return 1;
+    assign_head_bounds(p);
+    // one pyramid call per region (the partials are reused in stream order), 8 results each, ONE read-back
+    double* results = p->mask_stats + kPyramidPartials;
+    for (int r = 0; r < n_regions; ++r)
+        if (launch_mask_pyramid(masks[r], p->mask_h, p->mask_w, p->region_sqrt[r], p->mask_stats, results + 8 * r, s)) return 1;
+    double stats[8 * kMaxRegions];
+    ST_HIP(hipMemcpyAsync(stats, results, (size_t)8 * n_regions * sizeof(double), hipMemcpyDeviceToHost, s));
+    ST_HIP(hipStreamSynchronize(s));
+    for (int r = 0; r < n_regions; ++r) {
+        const double* st = stats + 8 * r;
+        ST_REQUIRE(st[7] == 0.0, "st_plan_set_style_regions: the mask of region %d holds %.0f NaN value(s): a mask's values lie in [0, 1]",
+                   r, st[7]);
+        ST_REQUIRE(st[5] >= 0.0 && st[6] <= 1.0,
+                   "st_plan_set_style_regions: the values of region %d's mask span [%g, %g]: a mask's values lie in [0, 1]", r, st[5], st[6]);
+        for (int k = 0; k < kMaskLevels; ++k) {
+            ST_REQUIRE(st[k] > 0.0,
+                       "st_plan_set_style_regions: region %d's mask, level %d (%d x %d, behind %d poolings) sums to 0: the style layers "
+                       "at that level would have no pixel to take the region's statistics from", r, k, p->mask_h[k], p->mask_w[k], k);
+            p->region_sum[r][k] = st[k];
+        }
+    }
+    deal_region_weights(p, n_regions, nullptr);
+    p->n_regions = n_regions;
+    return 0;
+}
+
+int st_plan_style_region(const st_plan* p, int region, int level, const float** sqrt_mask, int* h, int* w, double* sum) {
+    ST_REQUIRE(p, "st_plan_style_region: null plan");
+    ST_REQUIRE(p->n_regions > 0, "st_plan_style_region: no style regions are set on this plan (st_plan_set_style_regions)");
+    ST_REQUIRE(region >= 0 && region < p->n_regions, "st_plan_style_region: region %d out of range (%d regions)", region, p->n_regions);
+    ST_REQUIRE(level >= 0 && level < kMaskLevels, "st_plan_style_region: level %d out of range (0 .. %d)", level, kMaskLevels - 1);
+    if (sqrt_mask) *sqrt_mask = p->region_sqrt[region][level];
+    if (h) *h = p->mask_h[level];
+    if (w) *w = p->mask_w[level];
+    if (sum) *sum = p->region_sum[region][level];
+    return 0;
+}
+
+int st_plan_set_region_weights(st_plan* p, const float* weights) {
+    ST_REQUIRE(p, "st_plan_set_region_weights: null plan");
+    ST_REQUIRE(p->n_regions > 0, "st_plan_set_region_weights: no style regions are set on this plan (st_plan_set_style_regions)");
+    for (int r = 0; weights && r < p->n_regions; ++r)
+        ST_REQUIRE(std::isfinite(weights[r]), "st_plan_set_region_weights: the weight of region %d is not finite", r);
+    deal_region_weights(p, p->n_regions, weights);
+    invalidate_graph(p);       // the weights are baked into kernel arguments
+    return 0;
+}
+
+int st_plan_region_terms(st_plan* p, float** terms, int* regions, int* styles) {
+    ST_REQUIRE(p && terms, "st_plan_region_terms: null argument");
+    ST_REQUIRE(p->n_regions > 0, "st_plan_region_terms: no style regions are set on this plan (st_plan_set_style_regions)");
+    *terms = p->region_terms;
+    if (regions) *regions = p->n_regions;
+    if (styles) *styles = p->n_style;
     return 0;
 }
 

@@ -153,7 +153,20 @@ struct st_plan {
     float* mask_sqrt[st::kMaskLevels] = {};          // [h][w] of mask_h / mask_w, allocated by the first setter call
     int mask_h[st::kMaskLevels] = {}, mask_w[st::kMaskLevels] = {};
     double mask_sum[st::kMaskLevels] = {};
-    double* mask_stats = nullptr;                    // the pyramid kernel's partials and, behind them, its 8 results
+    double* mask_stats = nullptr;                    // the pyramid kernel's partials and, behind them, its 8 results per region
+    // Style regions (st_plan_set_style_regions, st_mask.hip): n_regions masks with a style each, the style mask's formulas once
+    // per region.  Region 0's head of a position is head[op]; regions 1 .. R - 1 have heads of their own (targets, workspaces,
+    // bound word), allocated for the listed style positions whenever the regions, the lists or the kinds change.  The general
+    // closure runs while n_regions > 0 (general_taps); a region's term is weighted style_weight[j] * region_weight[r].
+    int n_regions = 0;                               // 0: none in force (then a style mask may be)
+    float region_weight[st::kMaxRegions] = {};       // rho_r: 1 / R each from st_plan_set_style_regions, or st_plan_set_region_weights'
+    float* region_sqrt[st::kMaxRegions][st::kMaskLevels] = {};   // a pyramid per region (sizes: mask_h / mask_w), on first use
+    double region_sum[st::kMaxRegions][st::kMaskLevels] = {};
+    st::StyleHead region_head[st::kMaxRegions - 1][st::kNumOps];     // [r - 1][op]
+    unsigned int* region_amax = nullptr;             // [(kMaxRegions - 1) * 16] bound words: head (r, j) owns word (r - 1) 16 + j
+    float* region_terms = nullptr;                   // [kMaxRegions][16], used [R][n_style]: the weighted terms (st_plan_region_terms)
+    float* region_scratch = nullptr;                 // the 1x1 step of a region r >= 1, before it is added onto the seed ...
+    size_t region_scratch_floats = 0;                // ... sized by the largest listed style tap
     float* grad_img = nullptr;       // [3][H][W] internal gradient for st_plan_step
     float* losses = nullptr;         // [8] device
     float* red_partials = nullptr;   // scratch for two-level reductions: TV [0, 4 kStreamBlocks), content MSE after it
@@ -275,7 +288,16 @@ inline void assign_head_bounds(st_plan* p) {
     unsigned int* words = reinterpret_cast<unsigned int*>(p->amax_word);
     for (StyleHead& h : p->head) h.s_amax = words + (size_t)63 * kAmaxWordUints;
     for (int j = 0; j < p->n_style; ++j) p->head[p->style_op[j]].s_amax = words + (size_t)(48 + j) * kAmaxWordUints;
+    // the heads of regions 1 .. R - 1 (style regions): words of a block of their own, which the closure clears; an unlisted one has none
+    for (int r = 1; r < kMaxRegions; ++r) {
+        for (StyleHead& h : p->region_head[r - 1]) h.s_amax = nullptr;
+        for (int j = 0; p->region_amax && j < p->n_style; ++j)
+            p->region_head[r - 1][p->style_op[j]].s_amax = p->region_amax + (size_t)((r - 1) * 16 + j) * kAmaxWordUints;
+    }
 }
+// region r's head of kProgram[op] (style regions; region 0's is the position's own)
+inline StyleHead& region_head_at(st_plan* p, int region, int op) { return region == 0 ? p->head[op] : p->region_head[region - 1][op]; }
+inline const StyleHead& region_head_at(const st_plan* p, int region, int op) { return region_head_at(const_cast<st_plan*>(p), region, op); }
 
 constexpr int kHaloTrailer = 16;            // floats; word 0 = the sender's max |row| (raw bits), the rest unused (64-byte alignment)
 
@@ -338,6 +360,11 @@ bool targets_ready(const st_plan* p);
 float* loss_terms(st_plan* p);        // the array the closure's weighted terms go to, in SumLoss order
 float style_eps_of(const st_plan* p, int j);   // effective eps of style entry j / content entry i (mse: -1)
 float content_eps_of(const st_plan* p, int i);
+
+// ---- st_mask.hip
+// style regions in force: the heads of regions 1 .. R - 1 for these style positions under these kinds (st_plan_set_style_regions,
+// and st_plan_set_taps / the kinds setters BEFORE they change the plan: a failed allocation leaves it as it was)
+int ensure_region_heads(st_plan* p, int regions, const int* style_ops, int n_style, const int* kinds);
 
 // ---- st_strip.hip
 int halo_alloc(st_plan* p, float** out, size_t floats);

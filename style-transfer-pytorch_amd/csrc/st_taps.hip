@@ -37,6 +37,13 @@
 // kinds and eps included: every head's site carries sqrt(m) at its tap's level and the level's sum (mask_head_site), the Gram
 // launch and the normalisers read them, and the head's seed buffer is multiplied by m per pixel column (launch_mask_columns)
 // right behind the head's 1x1 step, before a content term of the same layer adds onto it.
+//
+// Style regions (st_plan_set_style_regions, st_mask.hip) run it too.  Per style entry, deepest first, and per region in order: a
+// site with that region's level and sum, head, weight style_weight[j] rho_r and term slot (region_head_site) through the same
+// style_head / gram_head.  Region 0 writes the seed and is multiplied by m_0 as above; region r >= 1 writes its 1x1 step into
+// the plan's one scratch buffer, which launch_mask_columns_add adds onto the seed times m_r.  The entries' terms are then summed
+// from the regions' in region order (launch_sum_region_terms) before the terms' total.  The bound words of the heads of regions
+// r >= 1 lie in a block of their own, cleared here before the first head.
 #include <algorithm>
 #include <cmath>
 
@@ -61,6 +68,7 @@ int list_kind(const int* kinds, int n) {
 void drop_targets(st_plan* p) {
     for (int op = 0; op < kNumOps; ++op) {
         p->head[op].target_set = false;
+        for (int r = 1; r < kMaxRegions; ++r) p->region_head[r - 1][op].target_set = false;
         p->content_set[op] = false;
     }
     assign_head_bounds(p);
@@ -91,7 +99,7 @@ static bool default_eps(const st_plan* p) {
 
 bool general_taps(const st_plan* p) {
     static Option force("ST_GENERAL_TAPS", 0);
-    return !p->strip && (!p->reference_taps || !default_kinds(p) || !default_eps(p) || p->style_mask || force.get() != 0);
+    return !p->strip && (!p->reference_taps || !default_kinds(p) || !default_eps(p) || p->style_mask || p->n_regions > 0 || force.get() != 0);
 }
 
 float style_eps_of(const st_plan* p, int j) {
@@ -113,7 +121,8 @@ int closure_top_op(const st_plan* p) {
 bool targets_ready(const st_plan* p) {
     bool ok = true;
     for (int i = 0; i < p->n_content; ++i) ok = ok && p->content_set[p->content_op[i]];
-    for (int j = 0; j < p->n_style; ++j) ok = ok && p->head[p->style_op[j]].target_set;
+    for (int r = 0; r < std::max(p->n_regions, 1); ++r)
+        for (int j = 0; j < p->n_style; ++j) ok = ok && region_head_at(p, r, p->style_op[j]).target_set;
     return ok;
 }
 
@@ -133,6 +142,22 @@ HeadSite general_head_site(st_plan* p, int j) {
     return at;
 }
 
+// ... and of region r while style regions are in force: that region's level of its own pyramid, its head of the position, the
+// entry's weight times rho_r, and the (region, entry) term.  Region r >= 1 writes its 1x1 step into the scratch buffer.
+HeadSite region_head_site(st_plan* p, int j, int r) {
+    HeadSite at = general_head_site(p, j);
+    const int op = p->style_op[j];
+    int level = 0;
+    for (int i = 0; i <= op; ++i) level += kProgram[i].kind == 1;
+    at.h = &region_head_at(p, r, op);
+    at.weight = p->style_weight[j] * p->region_weight[r];
+    at.loss = p->region_terms + (size_t)r * p->n_style + j;
+    if (r > 0) at.grad = p->region_scratch;
+    at.sqrt_mask = p->region_sqrt[r][level];
+    at.mask_sum = (float)p->region_sum[r][level];
+    return at;
+}
+
 // the totals (sum d^2, sum |d| + eps) of scaled-MSE term k in SumLoss order, behind the per-block partials
 float* kind_totals(st_plan* p, int k) { return p->kind_scratch + 2 * kStreamBlocks + 2 * k; }
 
@@ -145,6 +170,28 @@ int gram_head(st_plan* p, const HeadSite& at, int term, hipStream_t s) {
                   p->net->conv_elem == 1 ? h.s_amax : nullptr, at.mask_sum, s))
         return 1;
     return style_head_gradient(p, at, s);
+}
+
+// Style regions in force: the heads of every listed entry, in `order`, one per region in region order.  dF_r's pixel columns
+// times m_r: region 0 in place on the seed it wrote (the masked plan's launches), region r >= 1 from the scratch buffer ONTO the
+// seed.  Then each entry's term from its regions' terms.
+int region_heads(st_plan* p, const int* order, bool* styled, hipStream_t s) {
+    const int nc = p->n_content, ns = p->n_style, regions = p->n_regions;
+    if (regions > 1)
+        ST_HIP(hipMemsetAsync(p->region_amax, 0, (size_t)(kMaxRegions - 1) * 16 * kAmaxWordUints * sizeof(unsigned int), s));
+    for (int k = 0; k < ns; ++k) {
+        const int j = order[k];
+        float* seed = p->tap_seed[p->style_op[j]];
+        for (int r = 0; r < regions; ++r) {
+            const HeadSite at = region_head_site(p, j, r);
+            if (p->style_kind[j] == 1 ? gram_head(p, at, nc + j, s) : style_head(p, at, s)) return 1;
+            if (r == 0 ? launch_mask_columns(seed, at.sqrt_mask, at.h->n, at.h->npix, s)
+                       : launch_mask_columns_add(seed, at.grad, at.sqrt_mask, at.h->n, at.h->npix, s))
+                return 1;
+        }
+        styled[p->style_op[j]] = true;
+    }
+    return launch_sum_region_terms(p->region_terms, regions, ns, loss_terms(p) + nc, s);
 }
 
 // seed buffers of the tapped positions and the terms' array
@@ -161,6 +208,14 @@ int ensure_tap_buffers(st_plan* p) {
         if (seed(p->content_op[i])) return 1;
     for (int i = 0; i < p->n_style; ++i)
         if (seed(p->style_op[i])) return 1;
+    // style regions: one buffer of the largest listed style tap for the 1x1 steps of regions r >= 1
+    size_t largest = 0;
+    for (int i = 0; p->n_regions > 1 && i < p->n_style; ++i) largest = std::max(largest, node_at(p, p->style_op[i]).count());
+    if (largest > p->region_scratch_floats) {
+        p->region_scratch = nullptr;         // (the smaller one stays the plan's until it is destroyed)
+        if (plan_alloc(p, &p->region_scratch, largest)) { p->region_scratch_floats = 0; return 1; }
+        p->region_scratch_floats = largest;
+    }
     return 0;
 }
 
@@ -182,13 +237,17 @@ int general_loss_and_grad(st_plan* p, const float* image, float* grad_out, float
     for (int j = 0; j < ns; ++j) order[j] = j;
     std::sort(order, order + ns, [&](int a, int b) { return p->style_op[a] > p->style_op[b]; });
     bool styled[kNumOps] = {};
-    for (int k = 0; k < ns; ++k) {
-        const HeadSite at = general_head_site(p, order[k]);
-        if (p->style_kind[order[k]] == 1 ? gram_head(p, at, nc + order[k], s) : style_head(p, at, s)) return 1;
-        // a style mask: dF's pixel columns times m, on the seed as the head's 1x1 step left it and BEFORE a content term of the
-        // same layer adds onto it
-        if (at.sqrt_mask && launch_mask_columns(at.grad, at.sqrt_mask, at.h->n, at.h->npix, s)) return 1;
-        styled[p->style_op[order[k]]] = true;
+    if (p->n_regions) {
+        if (region_heads(p, order, styled, s)) return 1;
+    } else {
+        for (int k = 0; k < ns; ++k) {
+            const HeadSite at = general_head_site(p, order[k]);
+            if (p->style_kind[order[k]] == 1 ? gram_head(p, at, nc + order[k], s) : style_head(p, at, s)) return 1;
+            // a style mask: dF's pixel columns times m, on the seed as the head's 1x1 step left it and BEFORE a content term of
+            // the same layer adds onto it
+            if (at.sqrt_mask && launch_mask_columns(at.grad, at.sqrt_mask, at.h->n, at.h->npix, s)) return 1;
+            styled[p->style_op[order[k]]] = true;
+        }
     }
     // ContentLossMSE per content layer (style_transfer.py:425-429), behind the style head of the same layer where there is one;
     // an entry of kind 1: ContentLoss, its sums and then its seed
@@ -265,6 +324,9 @@ int st_plan_set_taps(st_plan* p, int n_content, const int* content_layers, int n
     const int ckind = std::max(list_kind(p->content_kind, p->n_content), 0), skind = std::max(list_kind(p->style_kind, p->n_style), 0);
     for (int j = 0; j < n_style; ++j)
         if (ensure_style_alloc(p, p->head[sop[j]], skind)) return 1;
+    int skinds[16];
+    std::fill(skinds, skinds + 16, skind);
+    if (ensure_region_heads(p, p->n_regions, sop, n_style, skinds)) return 1;       // (style regions in force: they stay)
     // the weights: the reference's lists named again keep theirs; every other change of lists starts from the new lists'
     // defaults - the reference's content_weight split over the layers (:366) and equal style weights, or, for the reference's
     // own lists, its own style weights
@@ -295,6 +357,7 @@ int apply_loss_kinds(st_plan* p, const int* ck, const int* sk) {
     // what the listed heads need under their new kinds, now: a failed allocation leaves the plan as it was
     for (int j = 0; j < p->n_style; ++j)
         if (ensure_style_alloc(p, p->head[p->style_op[j]], sk[j])) return 1;
+    if (ensure_region_heads(p, p->n_regions, p->style_op, p->n_style, sk)) return 1;
     for (int i = 0; i < 16; ++i) {
         p->content_kind[i] = ck[i];
         p->style_kind[i] = sk[i];

@@ -64,6 +64,11 @@ def _declare(lib):
         'st_plan_moments': (i32, [vp, i32, vp, vp, vp]),
         'st_plan_set_style_mask': (i32, [vp, vp, vp]),
         'st_plan_style_mask': (i32, [vp, i32, pp, ip, ip, ctypes.POINTER(f64)]),
+        'st_plan_set_style_regions': (i32, [vp, i32, pp, vp]),
+        'st_plan_style_region': (i32, [vp, i32, i32, pp, ip, ip, ctypes.POINTER(f64)]),
+        'st_plan_set_region_style_target': (i32, [vp, i32, i32, vp, vp, vp]),
+        'st_plan_set_region_weights': (i32, [vp, ctypes.POINTER(f32)]),
+        'st_plan_region_terms': (i32, [vp, pp, ip, ip]),
         'st_plan_set_content_target': (i32, [vp, vp, vp]),
         'st_plan_set_style_target': (i32, [vp, i32, vp, vp, vp]),
         'st_plan_set_loss_weights': (i32, [vp, f32, ctypes.POINTER(f32), f32]),
@@ -499,6 +504,67 @@ class Plan:
         with torch.cuda.device(self.device):
             _copy_d2d(out, data.value)
         return out, total.value
+
+    def set_style_regions(self, masks):
+        """Several style regions with a style each (st_plan_set_style_regions): a list of 1 to 4 [height, width] tensors with
+        values in [0, 1] at the plan's image size, or None (or an empty list) to clear them.  Region r's targets are set with
+        ``set_region_style_target``, its weight with ``set_region_weights`` (1 / R each after every call here); each style
+        term is then the sum over the regions of the layer's module on the region's mask-weighted moments against the
+        region's target.  Raises ValueError for a mask of another size, HipLibraryError on a strip plan, for more than 4
+        regions, while a style mask is set, for a NaN or a value outside [0, 1] and when a level of a region's pyramid sums
+        to 0; a refused call leaves the plan without regions."""
+        with torch.cuda.device(self.device):
+            if masks is None or len(masks) == 0:
+                _check(self.lib.st_plan_set_style_regions(self.handle, 0, None, _stream()))
+                return
+            held = []
+            for r, mask in enumerate(masks):
+                mask = torch.as_tensor(mask)
+                if tuple(mask.shape) != (self.height, self.width):
+                    raise ValueError(f'style region {r}: mask of shape {tuple(mask.shape)}: the plan is {self.height} x {self.width}')
+                held.append(mask.to(self.device, torch.float32).contiguous())
+            ptrs = (ctypes.c_void_p * len(held))(*[_ptr(m).value for m in held])
+            _check(self.lib.st_plan_set_style_regions(self.handle, len(held), ptrs, _stream()))
+
+    def style_region_level(self, region, level):
+        """(sqrt of level ``level`` of region ``region``'s mask as an [h, w] tensor - a copy -, the level's sum) as the plan
+        keeps them (st_plan_style_region).  Raises HipLibraryError when no regions are set."""
+        data, h, w, total = ctypes.c_void_p(), ctypes.c_int(), ctypes.c_int(), ctypes.c_double()
+        _check(self.lib.st_plan_style_region(self.handle, int(region), int(level), ctypes.byref(data), ctypes.byref(h),
+                                             ctypes.byref(w), ctypes.byref(total)))
+        out = torch.empty((h.value, w.value), device=self.device, dtype=torch.float32)
+        with torch.cuda.device(self.device):
+            _copy_d2d(out, data.value)
+        return out, total.value
+
+    def set_region_style_target(self, region, index, mean, srm):
+        """``set_style_target`` for region ``region`` of the regions in force (st_plan_set_region_style_target)."""
+        with torch.cuda.device(self.device):
+            _check(self.lib.st_plan_set_region_style_target(self.handle, int(region), int(index), _ptr(mean.contiguous()),
+                                                            _ptr(srm.contiguous()), _stream()))
+
+    def set_region_weights(self, weights):
+        """The regions' weights, one per region in force, used as given; None restores 1 / R each (st_plan_set_region_weights)."""
+        if weights is None:
+            _check(self.lib.st_plan_set_region_weights(self.handle, None))
+            return
+        ws = [float(w) for w in weights]
+        count = ctypes.c_int()
+        _check(self.lib.st_plan_region_terms(self.handle, ctypes.byref(ctypes.c_void_p()), ctypes.byref(count), None))
+        if len(ws) != count.value:
+            raise ValueError(f'{len(ws)} region weights for {count.value} style regions')
+        _check(self.lib.st_plan_set_region_weights(self.handle, (ctypes.c_float * len(ws))(*ws)))
+
+    def region_term_losses(self):
+        """The weighted term of every (region, style layer) of the last closure as an [R, n_style] device tensor
+        (st_plan_region_terms; a copy): column j sums, over the regions in order, to style term j of ``term_losses``."""
+        data, regions, styles = ctypes.c_void_p(), ctypes.c_int(), ctypes.c_int()
+        with torch.cuda.device(self.device):
+            _check(self.lib.st_plan_region_terms(self.handle, ctypes.byref(data), ctypes.byref(regions), ctypes.byref(styles)))
+            out = torch.empty((regions.value, styles.value), device=self.device, dtype=torch.float32)
+            if out.numel():
+                _copy_d2d(out, data.value)
+        return out
 
     def set_content_target(self, feat, index=0):
         """The target of content layer ``index`` of the configured list (st_plan_set_content_target_at)."""

@@ -310,6 +310,13 @@ def build_parser():
     p.add_argument('--style-image-masks', type=str, default=None, nargs='+', metavar='PATH',
                    help="one per style image: an image saying which pixels of that style image the style is taken from, or "
                         "the literal 'none' for no mask on that image")
+    p.add_argument('--style-regions', type=str, default=None, nargs='+', metavar='PATH',
+                   help='1 to 4 images (read as greyscale, white = 1), one per style region: which pixels of the output take '
+                        "that region's style; they are resized to every scale and may overlap (not with --style-mask)")
+    p.add_argument('--style-image-regions', type=int, default=None, nargs='+', metavar='INT',
+                   help='with --style-regions, one region index per style image: the region whose style that image gives')
+    p.add_argument('--style-region-weights', type=float, default=None, nargs='+', metavar='FLOAT',
+                   help="one weight per style region, used as given (default: 1 / the number of regions each)")
     p.add_argument('--trace', type=str, default='trace.json', help='where to write the iteration trace')
     return p
 
@@ -349,6 +356,10 @@ def apply_style_masks(st, args):
             _fail(ValueError(f"--style-image-masks: {len(args.style_image_masks)} entries for {len(args.styles)} style images "
                              "(use 'none' for an image without a mask)"))
         st.style_image_masks = [None if path.lower() == 'none' else load(path) for path in args.style_image_masks]
+    # --style-regions / --style-image-regions / --style-region-weights: stylize() checks them against each other
+    st.style_regions = None if args.style_regions is None else [load(path) for path in args.style_regions]
+    st.style_image_regions = args.style_image_regions
+    st.style_region_weights = args.style_region_weights
     return st
 
 

@@ -16,6 +16,7 @@ scale-to-scale resampling of the optimiser state.
 """
 
 import math
+import operator
 import os
 import time
 import warnings
@@ -334,6 +335,65 @@ def _resolve_style_masks(style_mask, style_image_masks, n_style_images, world=1)
         raise ValueError(f'style_mask / style_image_masks on {world} ranks: row strips take no style mask (a level\'s sum would '
                          'span the ranks); masks are out of scope for strips - run them on one device')
     return output, per_image
+
+
+MAX_STYLE_REGIONS = 4
+
+
+def _resolve_style_regions(style_regions, style_image_regions, style_region_weights, n_style_images, style_weights=None,
+                           style_mask=None, world=1):
+    """``StyleTransfer.style_regions`` / ``style_image_regions`` / ``style_region_weights`` as stylize() takes them: None, or
+    (one mask per region as ``_mask_image`` gives it, the region index of every style image, the regions' weights or None).
+    ``style_weights``: stylize()'s argument as given (None: equal weights) - a region's target blends its own images' moments
+    with ``style_weights[i]`` over the region's sum, which must not be 0.  Raises ``ValueError`` naming the attribute -
+    a wrong length, an index out of range, a region without an image or whose images' weights sum to 0, more than 4 regions,
+    ``style_mask`` together with ``style_regions``, weights that are not finite and non-negative with one positive, and any
+    region on several ranks - before any device work."""
+    if style_regions is None:
+        if style_image_regions is not None or style_region_weights is not None:
+            raise ValueError('style_image_regions / style_region_weights: given without style_regions')
+        return None
+    if isinstance(style_regions, (Image.Image, np.ndarray, torch.Tensor)) or not hasattr(style_regions, '__len__'):
+        raise ValueError('style_regions: give None, or a list of 1 to 4 masks, one per region')
+    count = len(style_regions)
+    if not 1 <= count <= MAX_STYLE_REGIONS:
+        raise ValueError(f'style_regions: {count} regions; a plan takes 1 to {MAX_STYLE_REGIONS}')
+    if style_mask is not None:
+        raise ValueError('style_mask together with style_regions: a plan takes one or the other (a single region IS a style mask)')
+    if world > 1:
+        raise ValueError(f'style_regions on {world} ranks: row strips take no style regions (a level\'s sum would span the '
+                         'ranks); regions are out of scope for strips - run them on one device')
+    regions = [_mask_image(mask, f'style_regions[{r}]') for r, mask in enumerate(style_regions)]
+    if style_image_regions is None:
+        raise ValueError('style_image_regions: required with style_regions - one region index per style image')
+    try:
+        image_regions = [operator.index(r) for r in style_image_regions]
+    except TypeError:
+        raise ValueError('style_image_regions: one integer region index per style image') from None
+    if len(image_regions) != n_style_images:
+        raise ValueError(f'style_image_regions: {len(image_regions)} entries for {n_style_images} style images; give exactly one '
+                         'region index per style image')
+    for i, r in enumerate(image_regions):
+        if not 0 <= r < count:
+            raise ValueError(f'style_image_regions[{i}]: region {r} out of range (0 .. {count - 1})')
+    image_weights = [1.0] * n_style_images if style_weights is None else [float(w) for w in style_weights]
+    for r in range(count):
+        own = [i for i, region in enumerate(image_regions) if region == r]
+        if not own:
+            raise ValueError(f'style_image_regions: region {r} has no style image')
+        if len(image_weights) == n_style_images and sum(image_weights[i] for i in own) == 0:
+            raise ValueError(f'style_image_regions: the style_weights of region {r}\'s images sum to 0')
+    weights = None
+    if style_region_weights is not None:
+        try:
+            weights = [float(w) for w in style_region_weights]
+        except TypeError:
+            raise ValueError('style_region_weights: give None, or one number per region') from None
+        if len(weights) != count:
+            raise ValueError(f'style_region_weights: {len(weights)} weights for {count} regions')
+        if not all(math.isfinite(w) and w >= 0 for w in weights) or not any(w > 0 for w in weights):
+            raise ValueError('style_region_weights: finite non-negative numbers with at least one positive')
+    return regions, image_regions, weights
 
 
 def _sized_mask(entry, width, height):
@@ -712,6 +772,15 @@ class StyleTransfer:
     # at every scale: which of ITS pixels the style is taken from.  One device only.
     style_mask = None
     style_image_masks = None
+    # Several style regions, each with its own style (read by stylize() next to the masks; _hip.Plan.set_style_regions).
+    # style_regions: None, or a list of 1 to 4 masks in style_mask's forms, resized bilinearly at every scale: where each
+    # region's style goes.  style_image_regions: one region index per style image, required then; a region's target for a
+    # layer blends its own images' moments with style_weights[i] over the region's sum (style_image_masks still applies per
+    # image).  style_region_weights: None (1 / R each) or one finite non-negative number per region, used as given.  Masks
+    # may overlap; a pixel in no region takes no style.  Not together with style_mask; one device only.
+    style_regions = None
+    style_image_regions = None
+    style_region_weights = None
 
     def __init__(self, devices=['cuda:0'], pooling='max', weights=None, precision='fp16x3'):
         # reference :310 defaults to ['cpu']; this build has no CPU path, so the default is the first HIP device
@@ -773,13 +842,20 @@ class StyleTransfer:
 
     # ---- per-scale targets (reference :425-453) ----
     def _build_targets(self, plan, content, style_images, style_weights, scale, style_scale_fac, style_size,
-                       style_mask=None, image_masks=None):
+                       style_mask=None, image_masks=None, regions=None):
         device = self.devices[0]
         # masks (_resolve_style_masks' forms): a style image's is in force on ITS plan only while its moments are taken - that
         # plan can be the iterate's own, and this method runs again after the range guard - and the output's goes on last
         masked = style_mask is not None or any(entry is not None for entry in image_masks or [])
         if masked:
             plan.set_style_mask(None)
+        # regions (_resolve_style_regions' triple): cleared while the targets are taken, as the mask is, and set last; image i's
+        # moments then go to its region's blend alone, with its weight over the region's sum
+        region_of = regions[1] if regions else [0] * len(style_images)
+        if regions:
+            plan.set_style_regions(None)
+            sums = [sum(w for w, r in zip(style_weights, region_of) if r == k) for k in range(len(regions[0]))]
+            style_weights = [w / sums[r] for w, r in zip(style_weights, region_of)]
         content_layers, style_layers = list(plan.content_layers), list(plan.style_layers)
         # fp16x3's activation-aware range guard (cold path, st_plan_range_guard): the forward arithmetic is checked on every
         # image BEFORE its features become targets; the closure's gradients are checked in stylize() once the targets exist
@@ -789,8 +865,9 @@ class StyleTransfer:
         if content_layers:
             plan.forward(content, max(content_layers))
             plan.set_content_target_from_forward()
-        blended = {}
+        blends = [{} for _ in range(len(regions[0]) if regions else 1)]
         for i, image in enumerate(style_images):
+            blended = blends[region_of[i]]
             if style_size is None:
                 sw, sh = size_to_fit(image.size, round(scale * style_scale_fac))
             else:
@@ -819,8 +896,15 @@ class StyleTransfer:
                     blended[layer][1].add_(srm)
             if image_mask is not None:
                 splan.set_style_mask(None)
-        for idx, layer in enumerate(style_layers):
-            plan.set_style_target(idx, *blended[layer])
+        if regions:
+            plan.set_style_regions([_sized_mask(entry, plan.width, plan.height) for entry in regions[0]])
+            plan.set_region_weights(regions[2])
+        for r, blended in enumerate(blends):
+            for idx, layer in enumerate(style_layers):
+                if regions:
+                    plan.set_region_style_target(r, idx, *blended[layer])
+                else:
+                    plan.set_style_target(idx, *blended[layer])
         if style_mask is not None:
             plan.set_style_mask(_sized_mask(style_mask, plan.width, plan.height))
 
@@ -958,6 +1042,9 @@ class StyleTransfer:
             world=max(len(self.devices), _dist_info()[1]))
         style_mask, image_masks = _resolve_style_masks(self.style_mask, self.style_image_masks, len(style_images),
                                                        world=max(len(self.devices), _dist_info()[1]))
+        regions = _resolve_style_regions(self.style_regions, self.style_image_regions, self.style_region_weights,
+                                         len(style_images), style_weights, self.style_mask,
+                                         world=max(len(self.devices), _dist_info()[1]))
         if len(self.devices) > 1 and self._job is None:
             return _device_list_stylize(self, content_image, style_images, dict(
                 style_weights=style_weights, content_weight=content_weight, tv_weight=tv_weight, optimizer=optimizer,
@@ -1089,7 +1176,7 @@ class StyleTransfer:
                 if any(value is not None for value in content_eps + style_eps):
                     plan.set_loss_eps(content_eps, style_eps)
                 self._build_targets(plan, content.to(device), style_images, style_weights, scale, style_scale_fac,
-                                    style_size, style_mask, image_masks)
+                                    style_size, style_mask, image_masks, regions)
             plan.set_loss_weights(content_weights, layer_weights, tv_weight)
             if sharded and self.model.net.precision == 'fp16x3':
                 # ... sharded: on this rank's rows of the iterate, against the scale's style targets; the union of the ranks'
@@ -1110,7 +1197,7 @@ class StyleTransfer:
                 fwd, bwd = plan.range_guard(self.image)
                 if any(fwd):
                     self._build_targets(plan, content.to(device), style_images, style_weights, scale, style_scale_fac,
-                                        style_size, style_mask, image_masks)
+                                        style_size, style_mask, image_masks, regions)
                 if any(fwd) or any(bwd):
                     print(f'fp16x3 range guard: bf16x6 for the forward of convs {[i for i, v in enumerate(fwd) if v]} and '
                           f'the data gradient of convs {[i for i, v in enumerate(bwd) if v]} from now on')
