@@ -677,7 +677,25 @@ int st_op_winograd_consumer_rate(int steps, int launches, double* tflops, void* 
 
 /* Diagnostic (tests/test_tv_hazard_gpu.py), no reference counterpart: after a device synchronise, copy `count` floats of an
  * internal buffer of the plan to the host.  what = 0: the TV kernels' per-workgroup partial sums (4 floats per workgroup:
- * the sums of squares of D1 .. D4 of style_transfer.py:189-192, tv_interior_kernel's workgroups first). */
+ * the sums of squares of D1 .. D4 of style_transfer.py:189-192, tv_interior_kernel's workgroups first).
+ *
+ * what = 2 (tests/test_operand_bounds_gpu.py), count = 64: the plan's 64 fp16x3 operand bounds, one float per bound word - the
+ * maximum over the word's slots, reinterpreted as a float, which is what a consumer scales its fp16 planes by (only the
+ * exponent counts: the consumer assumes max |operand| < 2^(floor(log2 b) + 1)).  A word no launch has raised reads 0.
+ *     words  0 .. 12   max |y| of the 13 convolutions' ReLU outputs (relu1_1 ... relu5_1)
+ *     words 16 .. 28   max |g| of the gradients of those outputs, as staged: already multiplied by the ReLU mask
+ *     words 32 .. 35   max |g| of the gradients of the 4 pooled maps
+ *     words 48 .. 63   the style heads' bounds on their C x C matrix Ssym: the j-th listed style layer owns word 48 + j
+ *     every other word is unused and reads 0
+ * Two sharing rules: a pooled map has no y word of its own, its consumer reads the word of the convolution that feeds the pool
+ * (average and L2 pooling may exceed that bound by less than one binade, which the fp16 scale leaves spare); and a convolution
+ * that feeds a pool has no g word of its own, its gradient is bounded by that pool's word (32 .. 35), which therefore covers
+ * both tensors - words 17, 19, 23 and 27 are never written.  The bounds are those of the LAST pass: a forward clears
+ * all 64 at its start, a backward the g words at its start; st_plan_step and st_plan_lbfgs_step clear all 64 in their tail
+ * for the next pass, so read them after st_plan_forward, st_plan_backward or st_plan_loss_and_grad, not after a step.
+ *
+ * what = 16 + i, i = 0 .. 16, count = C h w of that map: the gradient map of the i-th of the 17 taps in network order (relu1_1,
+ * relu1_2, pool1, relu2_1, ...) as the last backward or closure left it - the tensor its g word bounds. */
 int st_plan_debug_read(st_plan* plan, int what, float* out, int count);
 
 /* Measurement aid (csrc/st_diag.hip), no reference counterpart: microseconds per round of `rounds` device-wide barriers

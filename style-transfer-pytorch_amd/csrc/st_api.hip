@@ -549,9 +549,28 @@ int st_plan_debug_read(st_plan* p, int what, float* out, int count) {
     ST_REQUIRE(p && out && count > 0, "st_plan_debug_read: bad argument");
     // what = 0: the partial sums of the TV kernels' workgroups, 4 floats each (tv_interior_kernel's first, then tv_border_kernel's)
     // what = 1: every thread's (s1, s2, s3, s4, groups visited) of tv_interior_kernel under ST_TV_VARIANT=3
-    ST_REQUIRE((what == 0 && count <= 4 * kStreamBlocks) || (what == 1 && count <= kStreamBlocks * 256 * 5 && tv_debug_buffer()),
+    // what = 2: the 64 operand bounds of amax_word, each as the maximum over its kAmaxSlots slots (raw bits, as the consumers read it)
+    // what = 16 + i: Node::g of kProgram[i], the gradient map as its consumer stages it (count = its element count)
+    const bool grad_map = what >= 16 && what < 16 + kNumOps;
+    ST_REQUIRE((what == 0 && count <= 4 * kStreamBlocks) || (what == 1 && count <= kStreamBlocks * 256 * 5 && tv_debug_buffer()) ||
+                   (what == 2 && count == 64) ||
+                   (grad_map && p->grads_allocated && (size_t)count == node_at(p, what - 16).count()),
                "st_plan_debug_read: unknown buffer or count out of range");
     ST_HIP(hipDeviceSynchronize());
+    if (what == 2) {
+        std::vector<unsigned int> words((size_t)64 * kAmaxWordUints);
+        ST_HIP(hipMemcpy(words.data(), p->amax_word, words.size() * sizeof(unsigned int), hipMemcpyDeviceToHost));
+        for (int w = 0; w < 64; ++w) {
+            unsigned int m = 0;
+            for (int slot = 0; slot < kAmaxSlots; ++slot) m = std::max(m, words[(size_t)w * kAmaxWordUints + (size_t)slot * kAmaxSlotStride]);
+            memcpy(&out[w], &m, sizeof(float));
+        }
+        return 0;
+    }
+    if (grad_map) {
+        ST_HIP(hipMemcpy(out, node_at(p, what - 16).g, (size_t)count * sizeof(float), hipMemcpyDeviceToHost));
+        return 0;
+    }
     ST_HIP(hipMemcpy(out, what == 0 ? p->red_partials : tv_debug_buffer(), (size_t)count * sizeof(float), hipMemcpyDeviceToHost));
     return 0;
 }

@@ -418,8 +418,16 @@ class Plan:
         return int(self.lib.st_plan_device_bytes(self.handle))
 
     def debug_read(self, what, count):
-        """Diagnostic: `count` floats of an internal buffer (0: the TV kernels' per-workgroup partial sums)."""
+        """Diagnostic: `count` floats of an internal buffer, as a CPU tensor (st_plan_debug_read in include/st_amd.h).
+        0: the TV kernels' per-workgroup partial sums.  2 (`count` must be 64): the fp16x3 operand bounds of the last
+        pass, one float per bound word - words 0 .. 12 max |y| of the 13 ReLU outputs, 16 .. 28 max |g| of their
+        (ReLU-masked) gradients, 32 .. 35 max |g| of the 4 pooled maps' gradients, 48 .. 63 the style heads'; a pooled map
+        shares the word of the convolution that feeds its pool, that convolution's gradient shares the pool's g word.  Read
+        them after ``forward``, ``backward`` or ``loss_and_grad``: a ``step`` clears them in its tail.  16 + i: the
+        gradient map of the i-th of the 17 taps in network order (`count`: its C * h * w)."""
         import numpy as np
+        if int(what) == 2 and int(count) != 64:
+            raise ValueError(f'debug_read(2, {count}): the plan has 64 operand bounds')
         buf = np.empty(int(count), dtype=np.float32)
         _check(self.lib.st_plan_debug_read(self.handle, int(what), buf.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), int(count)))
         return torch.from_numpy(buf)

@@ -49,6 +49,22 @@ def test_environment_switches_of_the_default_build_are_the_documented_ones():
             assert f == 'st_api.hip' and 'return getenv(name);' in src.splitlines()[line - 1], f'{f}:{line} reads the environment directly'
 
 
+def test_operand_bound_readout_is_documented():
+    """st_plan_debug_read's what = 2 (tests/test_operand_bounds_gpu.py reads the 64 fp16x3 operand bounds through it): the
+    header states the word map, the two sharing rules and when the words may be read; the binding refuses another count."""
+    from style_transfer import _hip
+    text = open(os.path.join(REPO, 'include', 'st_amd.h')).read()
+    comment = text[:text.index('int st_plan_debug_read(')].rsplit('/*', 1)[1]
+    comment = ' '.join(comment.replace('*', ' ').split())
+    for phrase in ('what = 2', 'count = 64', 'words 0 .. 12', 'words 16 .. 28', 'words 32 .. 35', 'words 48 .. 63', 'reads 0',
+                   'a pooled map has no y word of its own', 'a convolution that feeds a pool has no g word of its own',
+                   'st_plan_step and st_plan_lbfgs_step clear all 64 in their tail', 'what = 16 + i'):
+        assert phrase in comment, f'include/st_amd.h, st_plan_debug_read: {phrase!r} is not documented'
+    with pytest.raises(ValueError, match='64 operand bounds'):
+        _hip.Plan.debug_read(None, 2, 63)
+    assert 'bound word' in _hip.Plan.debug_read.__doc__
+
+
 def test_default_build_has_no_experiment_kernels():
     """... and holds neither the persistent chain kernel nor the Winograd convolution (nm on the host library: kernel stubs)."""
     import subprocess
