@@ -208,6 +208,47 @@ int st_plan_set_region_weights(st_plan* plan, const float* weights_or_null);
 int st_plan_region_terms(st_plan* plan, float** terms, int* regions, int* styles);
 
 /*
+ * Spatial weight maps for the content and the TV term: where the picture stays close to the content image, and where it is
+ * smoothed.  The reference has neither; the semantics are fixed here.  `mask` is [H][W] fp32 on the device with values in
+ * [0, 1], at the plan's image size; NULL clears the map.
+ *
+ * The content map w is averaged down to the trunk's five resolutions as the style mask is (level k + 1 = avg_pool2d(level k,
+ * 2) at floor sizes, whatever the pooling mode), and the plan keeps the levels themselves.  A content layer takes the level
+ * of the number of pools at or before it.  With d = F - T on a [C][h][w] tap, w_p the level's value at pixel p and cw the
+ * entry's weight:
+ *     kind mse (ContentLossMSE):     term = cw sum_{c,p} w_p d^2 / (C h w),        seed = cw (2 / (C h w)) w_p d
+ *     kind scaled_mse (ContentLoss): S2 = sum w_p d^2, S1 = sum w_p |d| + eps, L = S2 / S1,
+ *                                    term = cw L,                                 seed = cw w_p (2 d - L sgn d) / S1
+ * The normaliser stays the element count, not the map's sum: a map of ones gives the unweighted term, and a smaller map
+ * lowers the term where less was asked for.  One map serves every content layer, each at its own level, and every eps.
+ *
+ * The TV map w is used at the image's size only, as given.  Each squared difference of the nine-point TVLoss
+ * (style_transfer.py:184-195) is weighed by the mean of the map at the difference's two end points, the map
+ * replicate-padded as the image is; the counts in the denominators are unchanged.  With P and Wp the padded image and map
+ * and s1 .. s4 the reference's slices,
+ *     q(a, b) = mean(((Wp[a] + Wp[b]) / 2) (P[a] - P[b])^2)
+ *     tv = 2 (q((s1,s2),(s1,s1)) / 3 + q((s2,s1),(s1,s1)) / 3 + q((s4,s4),(s3,s3)) / 12 + q((s4,s3),(s3,s4)) / 12)
+ * the term is tv_weight times that, and the gradient is the gradient of exactly that.  A map of ones is TVLoss.
+ *
+ * The two maps are independent of each other and of the style mask and the style regions: all may be in force together.  A
+ * plan with either map runs the general closure (csrc/st_taps.hip), on the default configuration too, for
+ * st_plan_loss_and_grad, st_plan_step, st_plan_lbfgs_step and st_plan_range_guard, launching eagerly; there are no
+ * floating-point atomics, so two closures give equal bits.  A plan whose maps are cleared is, bit for bit, one that never had
+ * any.  Setting or clearing a map keeps the lists, kinds, eps, weights and every target (a content target does not depend on
+ * the map) and invalidates a captured graph.  The setters are synchronous: the map is validated on the device in the pass
+ * that builds the levels, and the result is read back once.  They fail, naming the cause, on a strip plan, for a NaN or a
+ * value outside [0, 1], and for a map that is zero everywhere; a refused map leaves the plan without that map.
+ */
+int st_plan_set_content_mask(st_plan* plan, const float* mask_or_null, void* stream);
+/* Borrow level `level` (0 .. 4) of the content map in force as the plan keeps it: the level itself, dense [h][w] fp32 on the
+ * device.  Any output pointer may be null.  Fails when no content map is set. */
+int st_plan_content_mask(const st_plan* plan, int level, const float** map, int* h, int* w);
+int st_plan_set_tv_mask(st_plan* plan, const float* mask_or_null, void* stream);
+/* Borrow the TV map in force: a bit-exact copy of what was given, dense [H][W] fp32 on the device.  Any output pointer may be
+ * null.  Fails when no TV map is set. */
+int st_plan_tv_mask(const st_plan* plan, const float** map, int* h, int* w);
+
+/*
  * StyleTransfer.content_layers / style_layers (style_transfer.py:315-317, read by every scale at :425-453): the layers the
  * plan's closure puts its ContentLossMSE and StyleLossW2 terms on.  Each entry is a features index that st_plan_feature
  * accepts - the 13 ReLU outputs 1 3 6 8 11 13 15 17 20 22 24 26 29 and the 4 pool outputs 4 9 18 27; the reference also

@@ -612,6 +612,17 @@ int launch_scaled_mse_sums(const float* x, const float* target, long long count,
                            float* loss_out, hipStream_t s, unsigned int* ticket, float eps = kScaledMseEps);
 int launch_scaled_mse_grad(const float* feat, const float* target, long long count, float weight, const float* totals,
                            float* grad, hipStream_t s, int accumulate = 0);
+// The three launches above under a spatial weight map (st_plan_set_content_mask): the tap is [count / npix][npix] and element i
+// is weighed by wmap[i % npix] - mse: term = weight sum w d^2 / count, seed = weight (2 / count) w d; scaled_mse: S2 = sum w d^2,
+// S1 = sum w |d| + eps, seed = weight w (2 d - L sgn d) / S1.  A ticket word is required; a map of ones gives the bits above.
+int launch_content_mse_weighted(const float* feat, const float* target, const float* wmap, long long count, long long npix,
+                                float weight, float* grad, float* partials, float* loss_out, hipStream_t s, unsigned int* ticket,
+                                int accumulate = 0);
+int launch_scaled_mse_sums_weighted(const float* x, const float* target, const float* wmap, long long count, long long npix,
+                                    float weight, float* partials, float* totals, float* loss_out, hipStream_t s,
+                                    unsigned int* ticket, float eps = kScaledMseEps);
+int launch_scaled_mse_grad_weighted(const float* feat, const float* target, const float* wmap, long long count, long long npix,
+                                    float weight, const float* totals, float* grad, hipStream_t s, int accumulate = 0);
 // ... or, for a Gram head, (Ssym, b) of its 1x1 step: ssym = (weight / npix) (D + D^T), D = dL/dG from the totals; bvec = 0
 // (mask_sum > 0, here and in launch_style_grad_finish: a masked head's normaliser in the place of npix)
 int launch_gram_grad_finish(const float* gram, const float* gram_t, const float* totals, int n, float weight, long long npix,
@@ -636,9 +647,10 @@ constexpr int kMaskPyramidBlocks = 64;            // workgroups per level: their
 // From mask [h[0]][w[0]] (values in [0, 1]): level k + 1 is the plain mean of the 2 x 2 cells of level k at floor sizes
 // (h[k + 1] = h[k] / 2: avg_pool2d(m, 2)); sqrt_level[k] receives sqrt of level k.  stats (device, 8 doubles): [0..4] the sum
 // of each level, [5] min and [6] max of the mask, [7] the number of NaNs in it; partials: kMaskLevels x kMaskPyramidBlocks x 4
-// doubles.  Fixed-order sums, no atomics: two calls give the same bits.
+// doubles.  Fixed-order sums, no atomics: two calls give the same bits.  store_root = false (the content and TV weight maps):
+// the levels themselves are stored - level 0 is then a bit-exact copy of the mask; levels < kMaskLevels: only the first ones.
 int launch_mask_pyramid(const float* mask, const int* h, const int* w, float* const* sqrt_level, double* partials, double* stats,
-                        hipStream_t s);
+                        hipStream_t s, bool store_root = true, int levels = kMaskLevels);
 // buf [c][npix] *= sqrt_mask[npix]^2 per pixel column: the masked heads' gradient step dF = (Ssym F + b 1^T) diag(m)
 int launch_mask_columns(float* buf, const float* sqrt_mask, int channels, long long npix, hipStream_t s);
 // ---- style regions (st_plan_set_style_regions): several masks with a style each --------------------
@@ -649,9 +661,10 @@ int launch_mask_columns_add(float* dst, const float* src, const float* sqrt_mask
 // out[j] = region_terms[0][j] + region_terms[1][j] + ... in region order (fp32), j < n_style; region_terms is [regions][n_style].
 // One region: out[j] takes region_terms[0][j] as it is.
 int launch_sum_region_terms(const float* region_terms, int regions, int n_style, float* out, hipStream_t s);
-// TV loss partial sums + gradient (optionally scaled by `weight`): see st_pointwise.hip
+// TV loss partial sums + gradient (optionally scaled by `weight`): see st_pointwise.hip.  wmap (st_plan_set_tv_mask): [height][width],
+// every squared difference weighed by the mean of the map at its two end points; null: the unweighted kernels
 int launch_tv(const float* image, int height, int width, float weight, float* grad, float* partials,
-              float* loss_out, hipStream_t s, unsigned int* ticket = nullptr);
+              float* loss_out, hipStream_t s, unsigned int* ticket = nullptr, const float* wmap = nullptr);
 // Strip of a larger image: local rows [row0, row0 + height) of `global_height`; halo = [2][3][W] rows of the
 // neighbours (nullptr / has_* == 0 at the global border).  Writes the gradient and sums[4] = the four
 // sums of squared differences owned by this strip (to be all-reduced), no final value.

@@ -22,6 +22,10 @@
 // sum_r (Ssym_r F + b_r 1^T) diag(m_r) is accumulated in region order: region 0 writes the seed and is multiplied by m_0 as a
 // style mask is, region r >= 1 writes its 1x1 step into one scratch buffer and mask_columns_add_kernel adds m_r times it onto
 // the seed - one owner per element, no atomics, so two closures give equal bits.  The closure's part is st_taps.hip's.
+//
+// Weight maps for the content and TV terms (st_plan_set_content_mask / st_plan_set_tv_mask): the same pyramid kernel with the
+// levels stored as they are - all five for the content map, level 0 alone for the TV map (a bit-exact copy) - and validated by
+// the same read-back.  The weighted terms themselves are st_pointwise.hip's kernels, launched by st_taps.hip.
 #include <cmath>
 
 #include "st_plan.h"
@@ -49,8 +53,9 @@ __device__ __forceinline__ float pyramid_cell(const float* __restrict__ mask, in
     }
 }
 
+// root == 0 (the content and TV weight maps, below): the level itself is stored in the place of its square root.
 __global__ __launch_bounds__(256) void mask_pyramid_kernel(const float* __restrict__ mask, PyramidShape sh,
-                                                           double* __restrict__ partials) {
+                                                           double* __restrict__ partials, int root) {
 #pragma clang fp contract(off)
     __shared__ double red[4][256];
     const int lev = blockIdx.y;
@@ -68,7 +73,7 @@ __global__ __launch_bounds__(256) void mask_pyramid_kernel(const float* __restri
             case 3: v = pyramid_cell<3>(mask, W, y, x); break;
             default: v = pyramid_cell<4>(mask, W, y, x); break;
         }
-        out[i] = sqrtf(v);
+        out[i] = root ? sqrtf(v) : v;
         if (v != v) {
             nans += 1.0;
         } else {
@@ -96,12 +101,13 @@ __global__ __launch_bounds__(256) void mask_pyramid_kernel(const float* __restri
 }
 
 // stats[0..4] = the levels' sums, [5] min, [6] max, [7] NaN count of level 0 (the mask itself)
+// (levels: how many the pyramid kernel ran; the sums of the others are 0)
 __global__ __launch_bounds__(64) void pyramid_finish_kernel(const double* __restrict__ partials, int blocks,
-                                                            double* __restrict__ stats) {
+                                                            double* __restrict__ stats, int levels) {
     const int t = threadIdx.x;
     if (t < kMaskLevels) {
         double s = 0.0;
-        for (int b = 0; b < blocks; ++b) s += partials[((size_t)t * blocks + b) * 4];
+        for (int b = 0; t < levels && b < blocks; ++b) s += partials[((size_t)t * blocks + b) * 4];
         stats[t] = s;
     } else if (t < kMaskLevels + 3) {
         const int what = t - kMaskLevels + 1;              // 1 min, 2 max, 3 NaNs - of level 0
@@ -180,18 +186,19 @@ __global__ __launch_bounds__(64) void sum_region_terms_kernel(const float* __res
 }  // namespace
 
 int launch_mask_pyramid(const float* mask, const int* h, const int* w, float* const* sqrt_level, double* partials, double* stats,
-                        hipStream_t s) {
+                        hipStream_t s, bool store_root, int levels) {
+    ST_REQUIRE(levels >= 1 && levels <= kMaskLevels, "mask pyramid: %d levels", levels);
     PyramidShape sh{};
-    for (int k = 0; k < kMaskLevels; ++k) {
+    for (int k = 0; k < levels; ++k) {
         ST_REQUIRE(h[k] >= 1 && w[k] >= 1 && sqrt_level[k], "mask pyramid: level %d is empty", k);
         ST_REQUIRE(k == 0 || (h[k] == h[k - 1] / 2 && w[k] == w[k - 1] / 2), "mask pyramid: level %d is not the floor half of level %d", k, k - 1);
         sh.h[k] = h[k];
         sh.w[k] = w[k];
         sh.out[k] = sqrt_level[k];
     }
-    hipLaunchKernelGGL(mask_pyramid_kernel, dim3(kMaskPyramidBlocks, kMaskLevels), dim3(256), 0, s, mask, sh, partials);
+    hipLaunchKernelGGL(mask_pyramid_kernel, dim3(kMaskPyramidBlocks, levels), dim3(256), 0, s, mask, sh, partials, store_root ? 1 : 0);
     ST_LAUNCH_CHECK();
-    hipLaunchKernelGGL(pyramid_finish_kernel, dim3(1), dim3(64), 0, s, partials, kMaskPyramidBlocks, stats);
+    hipLaunchKernelGGL(pyramid_finish_kernel, dim3(1), dim3(64), 0, s, partials, kMaskPyramidBlocks, stats, levels);
     ST_LAUNCH_CHECK();
     return 0;
 }
@@ -326,6 +333,70 @@ int st_plan_style_mask(const st_plan* p, int level, const float** sqrt_mask, int
     if (h) *h = p->mask_h[level];
     if (w) *w = p->mask_w[level];
     if (sum) *sum = p->mask_sum[level];
+    return 0;
+}
+
+namespace {
+
+// What both weight-map setters do: the first `levels` levels of `map`'s pyramid, stored as they are (level 0: a bit-exact
+// copy), validated by the same pass - one read-back of the level sums, the range and the NaN count.  `who` names the setter.
+int take_weight_map(st_plan* p, const float* map, float** level, int levels, const char* who, hipStream_t s) {
+    if (ensure_pyramid_scratch(p)) return 1;
+    for (int k = 0; k < levels; ++k)
+        if (!level[k] && plan_alloc(p, &level[k], (size_t)p->mask_h[k] * p->mask_w[k])) return 1;
+    double* results = p->mask_stats + kPyramidPartials;
+    if (launch_mask_pyramid(map, p->mask_h, p->mask_w, level, p->mask_stats, results, s, /*store_root=*/false, levels)) return 1;
+    double stats[8];
+    ST_HIP(hipMemcpyAsync(stats, results, sizeof(stats), hipMemcpyDeviceToHost, s));
+    ST_HIP(hipStreamSynchronize(s));
+    ST_REQUIRE(stats[7] == 0.0, "%s: the map holds %.0f NaN value(s): a map's values lie in [0, 1]", who, stats[7]);
+    ST_REQUIRE(stats[5] >= 0.0 && stats[6] <= 1.0, "%s: the map's values span [%g, %g]: a map's values lie in [0, 1]", who, stats[5],
+               stats[6]);
+    ST_REQUIRE(stats[0] > 0.0, "%s: the map is zero everywhere: the term would vanish (set its weight to 0 for that)", who);
+    return 0;
+}
+
+}  // namespace
+
+int st_plan_set_content_mask(st_plan* p, const float* mask, void* stream) {
+    ST_REQUIRE(p, "st_plan_set_content_mask: null plan");
+    ST_REQUIRE(!p->strip, "st_plan_set_content_mask: strip plans take no content map (the general closure serves it, on one device)");
+    // no map is in force until it is accepted: the levels are overwritten whether or not it then is
+    if (p->content_mask || mask) invalidate_graph(p);
+    p->content_mask = false;
+    if (!mask) return 0;
+    if (take_weight_map(p, mask, p->content_map, kMaskLevels, "st_plan_set_content_mask", static_cast<hipStream_t>(stream))) return 1;
+    p->content_mask = true;
+    return 0;
+}
+
+int st_plan_content_mask(const st_plan* p, int level, const float** map, int* h, int* w) {
+    ST_REQUIRE(p, "st_plan_content_mask: null plan");
+    ST_REQUIRE(p->content_mask, "st_plan_content_mask: no content map is set on this plan (st_plan_set_content_mask)");
+    ST_REQUIRE(level >= 0 && level < kMaskLevels, "st_plan_content_mask: level %d out of range (0 .. %d)", level, kMaskLevels - 1);
+    if (map) *map = p->content_map[level];
+    if (h) *h = p->mask_h[level];
+    if (w) *w = p->mask_w[level];
+    return 0;
+}
+
+int st_plan_set_tv_mask(st_plan* p, const float* mask, void* stream) {
+    ST_REQUIRE(p, "st_plan_set_tv_mask: null plan");
+    ST_REQUIRE(!p->strip, "st_plan_set_tv_mask: strip plans take no TV map (the general closure serves it, on one device)");
+    if (p->tv_mask || mask) invalidate_graph(p);
+    p->tv_mask = false;
+    if (!mask) return 0;
+    if (take_weight_map(p, mask, &p->tv_map, 1, "st_plan_set_tv_mask", static_cast<hipStream_t>(stream))) return 1;
+    p->tv_mask = true;
+    return 0;
+}
+
+int st_plan_tv_mask(const st_plan* p, const float** map, int* h, int* w) {
+    ST_REQUIRE(p, "st_plan_tv_mask: null plan");
+    ST_REQUIRE(p->tv_mask, "st_plan_tv_mask: no TV map is set on this plan (st_plan_set_tv_mask)");
+    if (map) *map = p->tv_map;
+    if (h) *h = p->H;
+    if (w) *w = p->W;
     return 0;
 }
 

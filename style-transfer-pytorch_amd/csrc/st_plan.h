@@ -167,6 +167,13 @@ struct st_plan {
     float* region_terms = nullptr;                   // [kMaxRegions][16], used [R][n_style]: the weighted terms (st_plan_region_terms)
     float* region_scratch = nullptr;                 // the 1x1 step of a region r >= 1, before it is added onto the seed ...
     size_t region_scratch_floats = 0;                // ... sized by the largest listed style tap
+    // Spatial weight maps for the content and TV terms (st_plan_set_content_mask / st_plan_set_tv_mask, st_mask.hip): the
+    // content map as the style mask's pyramid of the levels THEMSELVES - a content layer weighs (F - T) per pixel with the
+    // level of the pools at or before it -, the TV map at the image's size only, a bit-exact copy.  Either one runs the
+    // general closure (general_taps); independent of each other and of style_mask / n_regions.  Sizes: mask_h / mask_w.
+    bool content_mask = false, tv_mask = false;
+    float* content_map[st::kMaskLevels] = {};        // allocated by the first setter call
+    float* tv_map = nullptr;
     float* grad_img = nullptr;       // [3][H][W] internal gradient for st_plan_step
     float* losses = nullptr;         // [8] device
     float* red_partials = nullptr;   // scratch for two-level reductions: TV [0, 4 kStreamBlocks), content MSE after it

@@ -292,6 +292,162 @@ __global__ __launch_bounds__(256) void scaled_mse_grad_kernel(const float* __res
         }
     }
 }
+// ------------------------------------------------------------------------------------------------
+// The content terms under a spatial weight map (st_plan_set_content_mask, include/st_amd.h): the tap is [C][npix] flat and
+// element i is weighed by wmap[i % npix], the map at the tap's level of the pyramid; the normalisers stay the element count
+// (mse) and the weighted sums (scaled_mse).
+//   mse:         term = weight sum_i w d^2 / count,                         seed = weight (2 / count) w d
+//   scaled_mse:  S2 = sum w d^2, S1 = sum w |d| + eps, term = weight S2 / S1, seed = weight w (2 d - L sgn d) / S1, L = S2 / S1
+// Siblings of the three kernels above with their structure - 16-byte groups where npix % 4 == 0 (a group then lies in one
+// channel row and the map's group is aligned), one element at a time otherwise; per-block partials, the ticket, the last block's
+// fixed-order sum.  A thread's pixel index is carried along its grid-stride loop (one 64-bit remainder before the loop, an add
+// and a compare per step), so there is no division per element.  The map is read C times and stays in L2: the launches remain
+// three-stream HBM-bound passes.  A map of ones gives the unweighted kernels' bits (1 * x = x, same operation order).
+struct MapWalk {
+    long long pos, step, period;
+    __device__ __forceinline__ MapWalk(long long first, long long stride, long long n) : pos(first % n), step(stride % n), period(n) {}
+    __device__ __forceinline__ void next() {
+        pos += step;
+        if (pos >= period) pos -= period;
+    }
+};
+template <bool ACC>
+__global__ __launch_bounds__(256) void content_mse_w_kernel(const float* __restrict__ feat, const float* __restrict__ target,
+                                                            const float* __restrict__ wmap, long long count, long long npix,
+                                                            float weight, float norm, float* __restrict__ grad,
+                                                            float* __restrict__ partials, LastBlock lb, float final_count,
+                                                            float* __restrict__ loss_out) {
+#pragma clang fp contract(off)
+    __shared__ float scratch[4];
+    __shared__ bool is_last;
+    float s = 0.f;
+    const long long first = blockIdx.x * 256ll + threadIdx.x, stride = (long long)gridDim.x * 256;
+    if ((npix & 3) == 0) {
+        const long long n4 = count >> 2;
+        const f32x4* f4 = reinterpret_cast<const f32x4*>(feat);
+        const f32x4* t4 = reinterpret_cast<const f32x4*>(target);
+        const f32x4* w4 = reinterpret_cast<const f32x4*>(wmap);
+        f32x4* g4 = reinterpret_cast<f32x4*>(grad);
+        MapWalk px(first, stride, npix >> 2);
+        for (long long i = first; i < n4; i += stride, px.next()) {
+            const f32x4 f = f4[i], t = t4[i], w = w4[px.pos];
+            f32x4 g;
+            if (ACC) g = g4[i];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float d = f[k] - t[k];
+                s += w[k] * (d * d);
+                const float v = (norm * (w[k] * d)) * weight;
+                g[k] = ACC ? g[k] + v : v;
+            }
+            g4[i] = g;
+        }
+    } else {
+        MapWalk px(first, stride, npix);
+        for (long long i = first; i < count; i += stride, px.next()) {
+            const float d = feat[i] - target[i], w = wmap[px.pos];
+            s += w * (d * d);
+            const float v = (norm * (w * d)) * weight;
+            grad[i] = ACC ? grad[i] + v : v;
+        }
+    }
+    s = block_sum_256(s, scratch);
+    if (threadIdx.x == 0) partials[blockIdx.x] = s;
+    if (!last_block_arrives(lb, &is_last)) return;
+    float t = 0.f;
+    for (int i = threadIdx.x; i < (int)gridDim.x; i += 256) t += partials[i];
+    t = block_sum_256(t, scratch);
+    if (threadIdx.x == 0) loss_out[0] = (t / final_count) * weight;
+}
+__global__ __launch_bounds__(256) void scaled_mse_sums_w_kernel(const float* __restrict__ x, const float* __restrict__ target,
+                                                                const float* __restrict__ wmap, long long count, long long npix,
+                                                                float weight, float eps, float* __restrict__ partials,
+                                                                LastBlock lb, float* __restrict__ totals,
+                                                                float* __restrict__ loss_out) {
+#pragma clang fp contract(off)
+    __shared__ float scratch[4];
+    __shared__ bool is_last;
+    float s2 = 0.f, s1 = 0.f;
+    const long long first = blockIdx.x * 256ll + threadIdx.x, stride = (long long)gridDim.x * 256;
+    if ((npix & 3) == 0) {
+        const long long n4 = count >> 2;
+        const f32x4* x4 = reinterpret_cast<const f32x4*>(x);
+        const f32x4* t4 = reinterpret_cast<const f32x4*>(target);
+        const f32x4* w4 = reinterpret_cast<const f32x4*>(wmap);
+        MapWalk px(first, stride, npix >> 2);
+        for (long long i = first; i < n4; i += stride, px.next()) {
+            const f32x4 f = x4[i], t = t4[i], w = w4[px.pos];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float d = f[k] - t[k];
+                s2 += w[k] * (d * d);
+                s1 += w[k] * fabsf(d);
+            }
+        }
+    } else {
+        MapWalk px(first, stride, npix);
+        for (long long i = first; i < count; i += stride, px.next()) {
+            const float d = x[i] - target[i], w = wmap[px.pos];
+            s2 += w * (d * d);
+            s1 += w * fabsf(d);
+        }
+    }
+    s2 = block_sum_256(s2, scratch);
+    s1 = block_sum_256(s1, scratch);
+    if (threadIdx.x == 0) {
+        partials[2 * blockIdx.x] = s2;
+        partials[2 * blockIdx.x + 1] = s1;
+    }
+    if (!last_block_arrives(lb, &is_last)) return;
+    float t2 = 0.f, t1 = 0.f;
+    for (int i = threadIdx.x; i < (int)gridDim.x; i += 256) {
+        t2 += partials[2 * i];
+        t1 += partials[2 * i + 1];
+    }
+    t2 = block_sum_256(t2, scratch);
+    t1 = block_sum_256(t1, scratch);
+    if (threadIdx.x == 0) {
+        const float sum_abs = t1 + eps;
+        totals[0] = t2;
+        totals[1] = sum_abs;
+        loss_out[0] = (t2 / sum_abs) * weight;
+    }
+}
+template <bool ACC>
+__global__ __launch_bounds__(256) void scaled_mse_grad_w_kernel(const float* __restrict__ feat, const float* __restrict__ target,
+                                                                const float* __restrict__ wmap, long long count, long long npix,
+                                                                float weight, const float* __restrict__ totals,
+                                                                float* __restrict__ grad) {
+#pragma clang fp contract(off)
+    const float s1 = totals[1];
+    const float level = totals[0] / s1;
+    const long long first = blockIdx.x * 256ll + threadIdx.x, stride = (long long)gridDim.x * 256;
+    if ((npix & 3) == 0) {
+        const long long n4 = count >> 2;
+        const f32x4* f4 = reinterpret_cast<const f32x4*>(feat);
+        const f32x4* t4 = reinterpret_cast<const f32x4*>(target);
+        const f32x4* w4 = reinterpret_cast<const f32x4*>(wmap);
+        f32x4* g4 = reinterpret_cast<f32x4*>(grad);
+        MapWalk px(first, stride, npix >> 2);
+        for (long long i = first; i < n4; i += stride, px.next()) {
+            const f32x4 f = f4[i], t = t4[i], w = w4[px.pos];
+            f32x4 g;
+            if (ACC) g = g4[i];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float v = (w[k] * scaled_mse_slope(f[k] - t[k], level, s1)) * weight;
+                g[k] = ACC ? g[k] + v : v;
+            }
+            g4[i] = g;
+        }
+    } else {
+        MapWalk px(first, stride, npix);
+        for (long long i = first; i < count; i += stride, px.next()) {
+            const float v = (wmap[px.pos] * scaled_mse_slope(feat[i] - target[i], level, s1)) * weight;
+            grad[i] = ACC ? grad[i] + v : v;
+        }
+    }
+}
 // The Gram head's (Ssym, b) for the 1x1 step, one workgroup per row c of the n x n matrix (n = 64 ... 512):
 //   ssym[c][d] = (weight / npix) (D[c][d] + D[d][c]),  D = (2 (G - G_t) - L sgn(G - G_t)) / S1;   bvec[c] = 0
 __global__ __launch_bounds__(256) void gram_grad_finish_kernel(const float* __restrict__ gram, const float* __restrict__ gram_t,
@@ -635,6 +791,209 @@ __global__ __launch_bounds__(256) void tv_border_kernel(const float* __restrict_
         loss_out[0] = (2.f * (((d1 + d2) + d3) + d4)) * fin_weight;
     }
 }
+// ------------------------------------------------------------------------------------------------
+// TVLoss under a spatial weight map (st_plan_set_tv_mask, include/st_amd.h): every squared difference is weighed by the mean
+// of the map at its two end points, the map replicate-padded as the image is; the counts in the denominators are unchanged.
+//   loss = 2 (sum e1 D1^2 / (3 n) + sum e2 D2^2 / (3 n) + sum e3 D3^2 / (12 n2) + sum e4 D4^2 / (12 n2)),  e = (w_a + w_b) / 2
+// so d loss / d P through a difference is the unweighted one times e.  The two kernels below are tv_interior_kernel<1> and
+// tv_border_kernel (whole images only) on the same split, reading the map's 3 x 3 neighbourhood beside the image's: every
+// k (c - x) of the gradient becomes k (e (c - x)) and every s += d d becomes s += e (d d).  A map of ones gives the unweighted
+// kernels' bits ((1 + 1) / 2 = 1, 1 * x = x).  The four sums are four weighted sums; partials, ticket and the finish are shared.
+struct TVMap {
+    const float* p;        // [H][W]
+    int H, W;
+    __device__ __forceinline__ float at(int a, int b) const {
+        a = min(max(a, 0), H - 1);
+        b = min(max(b, 0), W - 1);
+        return p[(size_t)a * W + b];
+    }
+};
+// (the sum is one VALU addition of its own: left to the optimiser, the SLP vectoriser pairs a pixel's edge sums wc + w_a,
+// wc + w_b into ONE packed-FP32 addition with a cross-half op_sel on wc - the instruction of profiles/r05_tv_hazard.md, which
+// build.py's hazard guard refuses)
+__device__ __forceinline__ float tv_edge(float wa, float wb) {
+#pragma clang fp contract(off)
+    float sum;
+    asm("v_add_f32 %0, %1, %2" : "=v"(sum) : "v"(wa), "v"(wb));
+    return 0.5f * sum;
+}
+
+// tv_dP with the edge weights (im: a whole image, row0 = 0, no halo)
+__device__ __forceinline__ float tv_dP_w(const TVImage& im, const TVMap& wm, int a, int b, float k1, float k3) {
+#pragma clang fp contract(off)
+    const int H = im.H, W = im.W;
+    const float c = im.at(a, b), wc = wm.at(a, b);
+    float g = 0.f;
+    const bool row_in = (a >= 0 && a < H), col_in = (b >= 0 && b < W);
+    if (row_in) {
+        if (b >= 1 && b <= W) g += k1 * (tv_edge(wc, wm.at(a, b - 1)) * (c - im.at(a, b - 1)));
+        if (col_in) g -= k1 * (tv_edge(wc, wm.at(a, b + 1)) * (im.at(a, b + 1) - c));
+    }
+    if (col_in) {
+        if (a >= 1 && a <= H) g += k1 * (tv_edge(wc, wm.at(a - 1, b)) * (c - im.at(a - 1, b)));
+        if (row_in) g -= k1 * (tv_edge(wc, wm.at(a + 1, b)) * (im.at(a + 1, b) - c));
+    }
+    if (a >= 0 && b >= 0) g += k3 * (tv_edge(wc, wm.at(a - 1, b - 1)) * (c - im.at(a - 1, b - 1)));            // D3(a, b)
+    if (a <= H - 1 && b <= W - 1) g -= k3 * (tv_edge(wc, wm.at(a + 1, b + 1)) * (im.at(a + 1, b + 1) - c));    // D3(a+1, b+1)
+    if (a >= 0 && b <= W - 1) g += k3 * (tv_edge(wc, wm.at(a - 1, b + 1)) * (c - im.at(a - 1, b + 1)));        // D4(a, b+1)
+    if (a <= H - 1 && b >= 0) g -= k3 * (tv_edge(wc, wm.at(a + 1, b - 1)) * (im.at(a + 1, b - 1) - c));        // D4(a+1, b)
+    return g;
+}
+
+// tv_pixel_generic with the edge weights
+__device__ __forceinline__ float tv_pixel_w(const TVImage& im, const TVMap& wm, int y, int x, float k1, float k3, float& s1,
+                                            float& s2, float& s3, float& s4) {
+#pragma clang fp contract(off)
+    const int H = im.H, W = im.W;
+    float g = 0.f;
+    for (int ry = -1; ry <= 1; ++ry) {
+        if (ry != 0 && !((ry < 0 && y == 0) || (ry > 0 && y == H - 1))) continue;
+        for (int rx = -1; rx <= 1; ++rx) {
+            if (rx != 0 && !((rx < 0 && x == 0) || (rx > 0 && x == W - 1))) continue;
+            g += tv_dP_w(im, wm, y + ry, x + rx, k1, k3);
+        }
+    }
+    const float c = im.at(y, x), wc = wm.at(y, x);
+    const float d1 = im.at(y, x + 1) - c, d2 = im.at(y + 1, x) - c;
+    s1 += tv_edge(wm.at(y, x + 1), wc) * (d1 * d1);
+    s2 += tv_edge(wm.at(y + 1, x), wc) * (d2 * d2);
+    for (int iy = y; iy <= ((y == H - 1) ? y + 1 : y); ++iy)
+        for (int jx = x; jx <= ((x == W - 1) ? W : x); ++jx) {
+            const float d3 = im.at(iy, jx) - im.at(iy - 1, jx - 1);
+            const float d4 = im.at(iy, jx - 1) - im.at(iy - 1, jx);
+            s3 += tv_edge(wm.at(iy, jx), wm.at(iy - 1, jx - 1)) * (d3 * d3);
+            s4 += tv_edge(wm.at(iy, jx - 1), wm.at(iy - 1, jx)) * (d4 * d4);
+        }
+    return g;
+}
+
+__global__ __launch_bounds__(256) void tv_interior_w_kernel(const float* __restrict__ image, const float* __restrict__ wmap,
+                                                            int H, int W, float k1, float k3, float* __restrict__ grad,
+                                                            float* __restrict__ partials) {
+#pragma clang fp contract(off)
+    __shared__ float scratch[4];
+    float s1 = 0.f, s2 = 0.f, s3 = 0.f, s4 = 0.f;
+    const int gpr = W >> 2;                                  // groups of 4 pixels per row
+    int tpr = 256;                                           // threads sharing a row: power of two covering it
+    while (tpr > 1 && (tpr >> 1) >= gpr) tpr >>= 1;
+    const int rpb = 256 / tpr;
+    const int lr = threadIdx.x / tpr, gx = threadIdx.x % tpr;
+    const int rows = 3 * H;
+    for (int row0 = blockIdx.x * rpb; row0 < rows; row0 += gridDim.x * rpb) {
+        const int row = row0 + lr;
+        const int ch = row / H;
+        const int y = row - ch * H;
+        if (row >= rows || y < 1 || y > H - 2) continue;
+        const float* rowp = image + (size_t)ch * H * W + (size_t)y * W;
+        const float* wrowp = wmap + (size_t)y * W;
+        float* growp = grad + (size_t)ch * H * W + (size_t)y * W;
+        for (int g4 = gx; g4 < gpr; g4 += tpr) {
+            if (g4 == 0 || g4 == gpr - 1) continue;
+            const float* c = rowp + 4 * g4;
+            const float* m = wrowp + 4 * g4;
+            const f32x4 up = *reinterpret_cast<const f32x4*>(c - W);
+            const f32x4 mid = *reinterpret_cast<const f32x4*>(c);
+            const f32x4 dn = *reinterpret_cast<const f32x4*>(c + W);
+            const f32x4 wup = *reinterpret_cast<const f32x4*>(m - W);
+            const f32x4 wmid = *reinterpret_cast<const f32x4*>(m);
+            const f32x4 wdn = *reinterpret_cast<const f32x4*>(m + W);
+            const float U[6] = {c[-W - 1], up[0], up[1], up[2], up[3], c[-W + 4]};
+            const float M[6] = {c[-1], mid[0], mid[1], mid[2], mid[3], c[4]};
+            const float D[6] = {c[W - 1], dn[0], dn[1], dn[2], dn[3], c[W + 4]};
+            const float WU[6] = {m[-W - 1], wup[0], wup[1], wup[2], wup[3], m[-W + 4]};
+            const float WM[6] = {m[-1], wmid[0], wmid[1], wmid[2], wmid[3], m[4]};
+            const float WD[6] = {m[W - 1], wdn[0], wdn[1], wdn[2], wdn[3], m[W + 4]};
+            f32x4 o;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float cc = M[j + 1], wc = WM[j + 1];
+                float g = 0.f;
+                g += k1 * (tv_edge(wc, WM[j]) * (cc - M[j]));
+                g -= k1 * (tv_edge(wc, WM[j + 2]) * (M[j + 2] - cc));
+                g += k1 * (tv_edge(wc, WU[j + 1]) * (cc - U[j + 1]));
+                g -= k1 * (tv_edge(wc, WD[j + 1]) * (D[j + 1] - cc));
+                g += k3 * (tv_edge(wc, WU[j]) * (cc - U[j]));               // D3(a, b)
+                g -= k3 * (tv_edge(wc, WD[j + 2]) * (D[j + 2] - cc));       // D3(a+1, b+1)
+                g += k3 * (tv_edge(wc, WU[j + 2]) * (cc - U[j + 2]));       // D4(a, b+1)
+                g -= k3 * (tv_edge(wc, WD[j]) * (D[j] - cc));               // D4(a+1, b)
+                o[j] = g;
+                const float d1 = M[j + 2] - cc, d2 = D[j + 1] - cc, d3 = cc - U[j], d4 = M[j] - U[j + 1];
+                s1 += tv_edge(WM[j + 2], wc) * (d1 * d1);
+                s2 += tv_edge(WD[j + 1], wc) * (d2 * d2);
+                s3 += tv_edge(wc, WU[j]) * (d3 * d3);
+                s4 += tv_edge(WM[j], WU[j + 1]) * (d4 * d4);
+                // (the accumulators pinned as in tv_interior_kernel<1>: no packed-FP32 pairing of the four updates)
+                asm volatile("" : "+v"(s1), "+v"(s2), "+v"(s3), "+v"(s4));
+            }
+            *reinterpret_cast<f32x4*>(growp + 4 * g4) = o;
+        }
+    }
+    s1 = block_sum_256(s1, scratch);
+    s2 = block_sum_256(s2, scratch);
+    s3 = block_sum_256(s3, scratch);
+    s4 = block_sum_256(s4, scratch);
+    if (threadIdx.x == 0) {
+        partials[blockIdx.x * 4 + 0] = s1;
+        partials[blockIdx.x * 4 + 1] = s2;
+        partials[blockIdx.x * 4 + 2] = s3;
+        partials[blockIdx.x * 4 + 3] = s4;
+    }
+}
+
+__global__ __launch_bounds__(256) void tv_border_w_kernel(const float* __restrict__ image, const float* __restrict__ wmap,
+                                                          int H, int W, float k1, float k3, float* __restrict__ grad,
+                                                          float* __restrict__ partials, int interior, int first, LastBlock lb,
+                                                          float fin_n, float fin_n2, float fin_weight,
+                                                          float* __restrict__ loss_out) {
+#pragma clang fp contract(off)
+    __shared__ float scratch[4];
+    __shared__ bool is_last;
+    float s1 = 0.f, s2 = 0.f, s3 = 0.f, s4 = 0.f;
+    const TVMap wm{wmap, H, W};
+    auto pixel = [&](int ch, int y, int x) __attribute__((always_inline)) {
+        TVImage im{image + (size_t)ch * H * W, H, W, 0, H, nullptr, nullptr};
+        grad[(size_t)ch * H * W + (size_t)y * W + x] = tv_pixel_w(im, wm, y, x, k1, k3, s1, s2, s3, s4);
+    };
+    if (interior) {
+        const int gpr = W >> 2;
+        const int per_ch = 2 * gpr + 2 * (H - 2);              // groups of the first / last row + both ends of the others
+        const int total = 3 * per_ch * 4;                      // ... as pixels
+        for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
+            const int gi = i >> 2, j = i & 3;
+            const int ch = gi / per_ch, k = gi - ch * per_ch;
+            int y, g4;
+            if (k < gpr) { y = 0; g4 = k; }
+            else if (k < 2 * gpr) { y = H - 1; g4 = k - gpr; }
+            else { y = 1 + ((k - 2 * gpr) >> 1); g4 = ((k - 2 * gpr) & 1) ? gpr - 1 : 0; }
+            pixel(ch, y, 4 * g4 + j);
+        }
+    } else {
+        const int total = 3 * H * W;
+        for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
+            const int x = i % W, r = i / W;
+            pixel(r / H, r % H, x);
+        }
+    }
+    s1 = block_sum_256(s1, scratch);
+    s2 = block_sum_256(s2, scratch);
+    s3 = block_sum_256(s3, scratch);
+    s4 = block_sum_256(s4, scratch);
+    if (threadIdx.x == 0) {
+        float* mine = partials + (size_t)(first + blockIdx.x) * 4;
+        mine[0] = s1; mine[1] = s2; mine[2] = s3; mine[3] = s4;
+    }
+    if (!last_block_arrives(lb, &is_last)) return;
+    const int nparts = first + (int)gridDim.x;
+    float t[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int i = threadIdx.x; i < nparts; i += 256)
+        for (int k = 0; k < 4; ++k) t[k] += partials[i * 4 + k];
+    for (int k = 0; k < 4; ++k) t[k] = block_sum_256(t[k], scratch);
+    if (threadIdx.x == 0) {
+        const float d1 = (t[0] / fin_n) / 3.f, d2 = (t[1] / fin_n) / 3.f;
+        const float d3 = (t[2] / fin_n2) / 12.f, d4 = (t[3] / fin_n2) / 12.f;
+        loss_out[0] = (2.f * (((d1 + d2) + d3) + d4)) * fin_weight;
+    }
+}
 // sums[k] = fixed-order sum over the per-block partials (k = 0..width-1)
 __global__ __launch_bounds__(64) void reduce_partials_kernel(const float* __restrict__ partials, int nparts,
                                                              int width, float* __restrict__ sums) {
@@ -847,6 +1206,48 @@ int launch_scaled_mse_grad(const float* feat, const float* target, long long cou
     return 0;
 }
 
+// the content terms under a weight map (the kernels' comment has the formulas): wmap [npix], count = channels * npix
+int launch_content_mse_weighted(const float* feat, const float* target, const float* wmap, long long count, long long npix,
+                                float weight, float* grad, float* partials, float* loss_out, hipStream_t s, unsigned int* ticket,
+                                int accumulate) {
+    ST_REQUIRE(wmap && ticket && npix > 0 && count % npix == 0, "weighted content MSE: bad argument");
+    const int blocks = stream_blocks((npix & 3) == 0 ? count / 4 : count);
+    const float norm = (float)(2.0 / (double)count);
+    if (accumulate)
+        hipLaunchKernelGGL(content_mse_w_kernel<true>, dim3(blocks), dim3(256), 0, s, feat, target, wmap, count, npix, weight, norm,
+                           grad, partials, LastBlock{ticket}, (float)count, loss_out);
+    else
+        hipLaunchKernelGGL(content_mse_w_kernel<false>, dim3(blocks), dim3(256), 0, s, feat, target, wmap, count, npix, weight, norm,
+                           grad, partials, LastBlock{ticket}, (float)count, loss_out);
+    ST_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_scaled_mse_sums_weighted(const float* x, const float* target, const float* wmap, long long count, long long npix,
+                                    float weight, float* partials, float* totals, float* loss_out, hipStream_t s,
+                                    unsigned int* ticket, float eps) {
+    ST_REQUIRE(wmap && ticket && npix > 0 && count % npix == 0, "weighted scaled MSE sums: bad argument");
+    const int blocks = stream_blocks((npix & 3) == 0 ? count / 4 : count);
+    hipLaunchKernelGGL(scaled_mse_sums_w_kernel, dim3(blocks), dim3(256), 0, s, x, target, wmap, count, npix, weight, eps, partials,
+                       LastBlock{ticket}, totals, loss_out);
+    ST_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_scaled_mse_grad_weighted(const float* feat, const float* target, const float* wmap, long long count, long long npix,
+                                    float weight, const float* totals, float* grad, hipStream_t s, int accumulate) {
+    ST_REQUIRE(wmap && npix > 0 && count % npix == 0, "weighted scaled MSE gradient: bad argument");
+    const int blocks = stream_blocks((npix & 3) == 0 ? count / 4 : count);
+    if (accumulate)
+        hipLaunchKernelGGL(scaled_mse_grad_w_kernel<true>, dim3(blocks), dim3(256), 0, s, feat, target, wmap, count, npix, weight,
+                           totals, grad);
+    else
+        hipLaunchKernelGGL(scaled_mse_grad_w_kernel<false>, dim3(blocks), dim3(256), 0, s, feat, target, wmap, count, npix, weight,
+                           totals, grad);
+    ST_LAUNCH_CHECK();
+    return 0;
+}
+
 int launch_gram_grad_finish(const float* gram, const float* gram_t, const float* totals, int n, float weight, long long npix,
                             float* ssym, float* bvec, hipStream_t s, unsigned int* ssym_amax, float mask_sum) {
     hipLaunchKernelGGL(gram_grad_finish_kernel, dim3(n), dim3(256), 0, s, gram, gram_t, totals, n, weight,
@@ -895,13 +1296,14 @@ float* tv_debug_buffer() {
 }
 
 // the two TV launches; returns the number of partial-sum blocks (4 floats each) in `partials`
+// (wmap: a whole image's weight map - the weighted kernels; null: the kernels of the unweighted term, as ever)
 static int launch_tv_kernels(const float* image, int height, int width, StripInfo strip, float k1, float k3, float* grad,
                              float* partials, LastBlock lb, float n, float n2, float weight, float* loss_out,
-                             hipStream_t s, int* nparts) {
+                             hipStream_t s, int* nparts, const float* wmap = nullptr) {
     // (width >= 8 and height >= 2: with a single 4-pixel group per row, or a single row, the border kernel's "first and
     // last group / row" coincide and it would visit - and sum - those pixels twice)
     const bool vec = (width & 3) == 0 && width >= 8 && height >= 2 && (((long long)height * width) & 3) == 0 &&
-                     ((reinterpret_cast<uintptr_t>(image) | reinterpret_cast<uintptr_t>(grad)) & 15) == 0;
+                     ((reinterpret_cast<uintptr_t>(image) | reinterpret_cast<uintptr_t>(grad) | reinterpret_cast<uintptr_t>(wmap)) & 15) == 0;
     int first = 0;
     long long border_threads;
     if (vec) {
@@ -912,7 +1314,8 @@ static int launch_tv_kernels(const float* image, int height, int width, StripInf
         first = std::min((3 * height + rpb - 1) / rpb, kStreamBlocks - 256);
         static Option variant("ST_TV_VARIANT", 1);              // 1: shipped; 0 / 3: the reproducer (see the kernel)
         float* none = nullptr;
-        switch (kExperiments ? variant.get() : 1) {
+        switch (wmap ? -1 : kExperiments ? variant.get() : 1) {
+            case -1: hipLaunchKernelGGL(tv_interior_w_kernel, dim3(first), dim3(256), 0, s, image, wmap, height, width, k1, k3, grad, partials); break;
 #if defined(ST_EXPERIMENTS)          // (the reproducer kernels exist only in builds with --experiments)
             case 0: hipLaunchKernelGGL(tv_interior_kernel<0>, dim3(first), dim3(256), 0, s, image, height, width, k1, k3, grad, partials, none); break;
             case 3: hipLaunchKernelGGL(tv_interior_kernel<3>, dim3(first), dim3(256), 0, s, image, height, width, k1, k3, grad, partials, tv_debug_buffer()); break;
@@ -925,15 +1328,19 @@ static int launch_tv_kernels(const float* image, int height, int width, StripInf
         border_threads = 3ll * height * width;
     }
     const int nb = (int)std::min<long long>((border_threads + 255) / 256, vec ? 256 : kStreamBlocks);
-    hipLaunchKernelGGL(tv_border_kernel, dim3(nb), dim3(256), 0, s, image, height, width, k1, k3, grad, partials, strip,
-                       vec ? 1 : 0, first, lb, n, n2, weight, loss_out);
+    if (wmap)
+        hipLaunchKernelGGL(tv_border_w_kernel, dim3(nb), dim3(256), 0, s, image, wmap, height, width, k1, k3, grad, partials,
+                           vec ? 1 : 0, first, lb, n, n2, weight, loss_out);
+    else
+        hipLaunchKernelGGL(tv_border_kernel, dim3(nb), dim3(256), 0, s, image, height, width, k1, k3, grad, partials, strip,
+                           vec ? 1 : 0, first, lb, n, n2, weight, loss_out);
     ST_LAUNCH_CHECK();
     *nparts = first + nb;
     return 0;
 }
 
 int launch_tv(const float* image, int height, int width, float weight, float* grad, float* partials,
-              float* loss_out, hipStream_t s, unsigned int* ticket) {
+              float* loss_out, hipStream_t s, unsigned int* ticket, const float* wmap) {
     const double n = 3.0 * height * width, n2 = 3.0 * (height + 1) * (width + 1);
     // d loss / d D = weight * 2 * (1/3 or 1/12) * (1/n) * 2 D
     const float k1 = (float)(weight * 4.0 / (3.0 * n));
@@ -941,7 +1348,7 @@ int launch_tv(const float* image, int height, int width, float weight, float* gr
     StripInfo whole{0, height, 0, 0, nullptr};
     int nparts = 0;
     if (launch_tv_kernels(image, height, width, whole, k1, k3, grad, partials, LastBlock{ticket}, (float)n, (float)n2,
-                          weight, loss_out, s, &nparts))
+                          weight, loss_out, s, &nparts, wmap))
         return 1;
     if (ticket) return 0;                 // the border kernel's last block wrote the loss
     hipLaunchKernelGGL(tv_final_kernel, dim3(1), dim3(64), 0, s, partials, nparts, (float)n, (float)n2, weight,

@@ -44,6 +44,11 @@
 // the plan's one scratch buffer, which launch_mask_columns_add adds onto the seed times m_r.  The entries' terms are then summed
 // from the regions' in region order (launch_sum_region_terms) before the terms' total.  The bound words of the heads of regions
 // r >= 1 lie in a block of their own, cleared here before the first head.
+//
+// Weight maps for the content and TV terms (st_plan_set_content_mask / st_plan_set_tv_mask, st_mask.hip) run it as well.  The TV
+// launch gets the map (launch_tv's weighted kernels); a content entry gets the content map's level of its tap and runs the
+// weighted siblings of its kind's launches (launch_content_mse_weighted, launch_scaled_mse_*_weighted), which write or add
+// the seed as the unweighted ones do.  Everything behind the seeds is unchanged.
 #include <algorithm>
 #include <cmath>
 
@@ -99,7 +104,8 @@ static bool default_eps(const st_plan* p) {
 
 bool general_taps(const st_plan* p) {
     static Option force("ST_GENERAL_TAPS", 0);
-    return !p->strip && (!p->reference_taps || !default_kinds(p) || !default_eps(p) || p->style_mask || p->n_regions > 0 || force.get() != 0);
+    return !p->strip && (!p->reference_taps || !default_kinds(p) || !default_eps(p) || p->style_mask || p->n_regions > 0 ||
+                         p->content_mask || p->tv_mask || force.get() != 0);
 }
 
 float style_eps_of(const st_plan* p, int j) {
@@ -226,8 +232,9 @@ int general_loss_and_grad(st_plan* p, const float* image, float* grad_out, float
     const int nc = p->n_content, ns = p->n_style;
     float* terms = loss_terms(p);
     // TVLoss on the un-normalised image (style_transfer.py:376): WRITES grad_out; conv1_1's data gradient adds to it
-    if (hbm_profiled(p, HBM_TV, 2.0 * 3 * 4.0 * p->H * p->W, s, [&] {
-            return launch_tv(image, p->H, p->W, p->tv_weight, grad_out, p->red_partials, terms + nc + ns, s, p->tickets + 0);
+    const float* tv_map = p->tv_mask ? p->tv_map : nullptr;
+    if (hbm_profiled(p, HBM_TV, (2.0 * 3 + (tv_map ? 1 : 0)) * 4.0 * p->H * p->W, s, [&] {
+            return launch_tv(image, p->H, p->W, p->tv_weight, grad_out, p->red_partials, terms + nc + ns, s, p->tickets + 0, tv_map);
         }))
         return 1;
     const int top = closure_top_op(p);
@@ -254,6 +261,34 @@ int general_loss_and_grad(st_plan* p, const float* image, float* grad_out, float
     for (int i = 0; i < nc; ++i) {
         const int op = p->content_op[i];
         const Node& ct = node_at(p, op);
+        if (p->content_mask) {
+            // a content map: the level of the pools at or before the tap, and the weighted siblings of the entry's launches
+            int level = 0;
+            for (int k = 0; k <= op; ++k) level += kProgram[k].kind == 1;
+            const float* wmap = p->content_map[level];
+            const long long npix = (long long)ct.h * ct.w, count = (long long)ct.count();
+            const double map_bytes = 4.0 * (double)npix;
+            if (p->content_kind[i] == 1) {
+                float* totals = kind_totals(p, i);
+                if (hbm_profiled(p, HBM_CONTENT, 2.0 * 4.0 * ct.count() + map_bytes, s, [&] {
+                        return launch_scaled_mse_sums_weighted(ct.y, p->content_target[op], wmap, count, npix, p->content_weight[i],
+                                                               p->kind_scratch, totals, terms + i, s, p->tickets + 128,
+                                                               content_eps_of(p, i));
+                    }) ||
+                    hbm_profiled(p, HBM_CONTENT, (styled[op] ? 4.0 : 3.0) * 4.0 * ct.count() + map_bytes, s, [&] {
+                        return launch_scaled_mse_grad_weighted(ct.y, p->content_target[op], wmap, count, npix, p->content_weight[i],
+                                                               totals, p->tap_seed[op], s, styled[op] ? 1 : 0);
+                    }))
+                    return 1;
+            } else if (hbm_profiled(p, HBM_CONTENT, 3.0 * 4.0 * ct.count() + map_bytes, s, [&] {
+                           return launch_content_mse_weighted(ct.y, p->content_target[op], wmap, count, npix, p->content_weight[i],
+                                                              p->tap_seed[op], p->red_partials + 4 * kStreamBlocks, terms + i, s,
+                                                              p->tickets + 64, styled[op] ? 1 : 0);
+                       })) {
+                return 1;
+            }
+            continue;
+        }
         if (p->content_kind[i] == 1) {
             float* totals = kind_totals(p, i);
             if (hbm_profiled(p, HBM_CONTENT, 2.0 * 4.0 * ct.count(), s, [&] {

@@ -69,6 +69,10 @@ def _declare(lib):
         'st_plan_set_region_style_target': (i32, [vp, i32, i32, vp, vp, vp]),
         'st_plan_set_region_weights': (i32, [vp, ctypes.POINTER(f32)]),
         'st_plan_region_terms': (i32, [vp, pp, ip, ip]),
+        'st_plan_set_content_mask': (i32, [vp, vp, vp]),
+        'st_plan_content_mask': (i32, [vp, i32, pp, ip, ip]),
+        'st_plan_set_tv_mask': (i32, [vp, vp, vp]),
+        'st_plan_tv_mask': (i32, [vp, pp, ip, ip]),
         'st_plan_set_content_target': (i32, [vp, vp, vp]),
         'st_plan_set_style_target': (i32, [vp, i32, vp, vp, vp]),
         'st_plan_set_loss_weights': (i32, [vp, f32, ctypes.POINTER(f32), f32]),
@@ -572,6 +576,51 @@ class Plan:
             out = torch.empty((regions.value, styles.value), device=self.device, dtype=torch.float32)
             if out.numel():
                 _copy_d2d(out, data.value)
+        return out
+
+    def _set_weight_map(self, entry, what, mask):
+        with torch.cuda.device(self.device):
+            if mask is None:
+                _check(entry(self.handle, None, _stream()))
+                return
+            mask = torch.as_tensor(mask)
+            if tuple(mask.shape) != (self.height, self.width):
+                raise ValueError(f'{what} of shape {tuple(mask.shape)}: the plan is {self.height} x {self.width}')
+            mask = mask.to(self.device, torch.float32).contiguous()
+            _check(entry(self.handle, _ptr(mask), _stream()))
+
+    def set_content_mask(self, mask):
+        """A spatial weight map for the content terms (st_plan_set_content_mask): a [height, width] tensor with values in
+        [0, 1] at the plan's image size, or None to clear it.  While it is set every content term of every closure and step
+        weighs (F - T) per pixel with the map averaged down 2 x 2 to its tap's resolution; the normaliser stays the element
+        count.  Every target stays.  Raises ValueError for another size, HipLibraryError on a strip plan, for a NaN or a
+        value outside [0, 1] and for an all-zero map; a refused map leaves the plan without one."""
+        self._set_weight_map(self.lib.st_plan_set_content_mask, 'content map', mask)
+
+    def content_mask_level(self, level):
+        """Level ``level`` of the content map as the plan keeps it, an [h, w] tensor (a copy; st_plan_content_mask): level k
+        serves the content layers behind k pools.  Raises HipLibraryError when no content map is set."""
+        data, h, w = ctypes.c_void_p(), ctypes.c_int(), ctypes.c_int()
+        _check(self.lib.st_plan_content_mask(self.handle, int(level), ctypes.byref(data), ctypes.byref(h), ctypes.byref(w)))
+        out = torch.empty((h.value, w.value), device=self.device, dtype=torch.float32)
+        with torch.cuda.device(self.device):
+            _copy_d2d(out, data.value)
+        return out
+
+    def set_tv_mask(self, mask):
+        """A spatial weight map for the TV term (st_plan_set_tv_mask): a [height, width] tensor with values in [0, 1] at the
+        plan's image size, or None to clear it.  While it is set each squared difference of the TV term is weighed by the
+        mean of the map at its two end points.  Raises as ``set_content_mask`` does."""
+        self._set_weight_map(self.lib.st_plan_set_tv_mask, 'TV map', mask)
+
+    def tv_mask(self):
+        """The TV map in force as an [height, width] tensor (a copy, equal to what was set bit for bit; st_plan_tv_mask).
+        Raises HipLibraryError when no TV map is set."""
+        data, h, w = ctypes.c_void_p(), ctypes.c_int(), ctypes.c_int()
+        _check(self.lib.st_plan_tv_mask(self.handle, ctypes.byref(data), ctypes.byref(h), ctypes.byref(w)))
+        out = torch.empty((h.value, w.value), device=self.device, dtype=torch.float32)
+        with torch.cuda.device(self.device):
+            _copy_d2d(out, data.value)
         return out
 
     def set_content_target(self, feat, index=0):

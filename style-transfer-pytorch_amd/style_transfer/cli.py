@@ -317,6 +317,12 @@ def build_parser():
                    help='with --style-regions, one region index per style image: the region whose style that image gives')
     p.add_argument('--style-region-weights', type=float, default=None, nargs='+', metavar='FLOAT',
                    help="one weight per style region, used as given (default: 1 / the number of regions each)")
+    p.add_argument('--content-mask', type=str, default=None, metavar='PATH',
+                   help='an image (read as greyscale, white = 1) saying where the output stays close to the content image: the '
+                        'content term is weighed by it per pixel; it is resized to every scale')
+    p.add_argument('--tv-mask', type=str, default=None, metavar='PATH',
+                   help='an image (read as greyscale, white = 1) saying where the output is smoothed: the TV term is weighed by '
+                        'it per pixel; it is resized to every scale')
     p.add_argument('--trace', type=str, default='trace.json', help='where to write the iteration trace')
     return p
 
@@ -330,6 +336,18 @@ def _loss_names(choices):
                 raise argparse.ArgumentTypeError(f"invalid choice: {name!r} (choose from {', '.join(map(repr, choices))})")
         return names[0] if len(names) == 1 else names
     return parse
+
+
+def apply_weight_maps(st, args):
+    """--content-mask / --tv-mask onto the StyleTransfer attributes that stylize() reads: the files are opened here."""
+    def load(path):
+        try:
+            return Image.open(path).convert('L')
+        except OSError as err:
+            _fail(err)
+    st.content_mask = None if args.content_mask is None else load(args.content_mask)
+    st.tv_mask = None if args.tv_mask is None else load(args.tv_mask)
+    return st
 
 
 def _loss_eps(text):
@@ -419,6 +437,7 @@ def main(argv=None):
     st = StyleTransfer(devices=devices, pooling=args.pooling, weights=args.weights, precision=args.precision)
     apply_loss_kinds(st, args)
     apply_style_masks(st, args)
+    apply_weight_maps(st, args)
     callback = Callback(st, args, image_type=image_type, web_interface=web_interface)
     atexit.register(callback.close)
 

@@ -337,6 +337,27 @@ def _resolve_style_masks(style_mask, style_image_masks, n_style_images, world=1)
     return output, per_image
 
 
+def _resolve_weight_maps(content_mask, tv_mask, world=1):
+    """``StyleTransfer.content_mask`` / ``tv_mask`` as stylize() takes them: (the content map or None, the TV map or None), each
+    as ``_mask_image`` gives it, for ``_sized_mask`` to bring to a scale's size.  Raises ``ValueError`` naming the attribute for
+    an array of the wrong number of dimensions, values outside [0, 1] or non-finite, an all-zero map, and for either map on
+    several ranks, before any device work."""
+    maps = []
+    for attr, mask in (('content_mask', content_mask), ('tv_mask', tv_mask)):
+        if mask is None:
+            maps.append(None)
+            continue
+        try:
+            maps.append(_mask_image(mask, attr))
+        except ValueError as exc:
+            # (_mask_image words an all-zero mask for the style statistics)
+            raise ValueError(str(exc).replace('; no pixel would carry the style statistics', '; the term would vanish everywhere')) from None
+        if world > 1:
+            raise ValueError(f'{attr} on {world} ranks: row strips take no content or TV map (the general closure serves them); '
+                             'maps are out of scope for strips - run them on one device')
+    return tuple(maps)
+
+
 MAX_STYLE_REGIONS = 4
 
 
@@ -781,6 +802,13 @@ class StyleTransfer:
     style_regions = None
     style_image_regions = None
     style_region_weights = None
+    # Spatial weight maps for the content and TV terms (read by stylize() next to style_mask, in its forms, resized bilinearly at
+    # every scale; _hip.Plan.set_content_mask / set_tv_mask).  content_mask: where the output stays close to the content image -
+    # every content term weighs (F - T) per pixel with the map at its layer's resolution.  tv_mask: where the output is
+    # smoothed - each squared difference of the TV term is weighed by the mean of the map at its two end points.  Independent
+    # of each other and of the style masks and regions; one device only.
+    content_mask = None
+    tv_mask = None
 
     def __init__(self, devices=['cuda:0'], pooling='max', weights=None, precision='fp16x3'):
         # reference :310 defaults to ['cpu']; this build has no CPU path, so the default is the first HIP device
@@ -1045,6 +1073,8 @@ class StyleTransfer:
         regions = _resolve_style_regions(self.style_regions, self.style_image_regions, self.style_region_weights,
                                          len(style_images), style_weights, self.style_mask,
                                          world=max(len(self.devices), _dist_info()[1]))
+        content_map, tv_map = _resolve_weight_maps(self.content_mask, self.tv_mask,
+                                                   world=max(len(self.devices), _dist_info()[1]))
         if len(self.devices) > 1 and self._job is None:
             return _device_list_stylize(self, content_image, style_images, dict(
                 style_weights=style_weights, content_weight=content_weight, tv_weight=tv_weight, optimizer=optimizer,
@@ -1177,6 +1207,12 @@ class StyleTransfer:
                     plan.set_loss_eps(content_eps, style_eps)
                 self._build_targets(plan, content.to(device), style_images, style_weights, scale, style_scale_fac,
                                     style_size, style_mask, image_masks, regions)
+                # the content and TV maps at this scale's size, on the iterate's plan only and after the targets (which they
+                # leave alone): the range guard below then checks the closure that the iterations run
+                if content_map is not None:
+                    plan.set_content_mask(_sized_mask(content_map, cw, ch))
+                if tv_map is not None:
+                    plan.set_tv_mask(_sized_mask(tv_map, cw, ch))
             plan.set_loss_weights(content_weights, layer_weights, tv_weight)
             if sharded and self.model.net.precision == 'fp16x3':
                 # ... sharded: on this rank's rows of the iterate, against the scale's style targets; the union of the ranks'
