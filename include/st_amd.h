@@ -249,6 +249,52 @@ int st_plan_set_tv_mask(st_plan* plan, const float* mask_or_null, void* stream);
 int st_plan_tv_mask(const st_plan* plan, const float** map, int* h, int* w);
 
 /*
+ * A Laplacian loss on average-pooled images (Li et al., "Laplacian-Steered Neural Style Transfer"): the content image's edges
+ * and fine structure survive the style.  The reference has none; the semantics are fixed here.  x is the un-normalised
+ * [3][H][W] image in [0, 1] that the TV term sees, c the content image at the same size, `pools` 1 to 4 distinct integers
+ * p >= 1.  Per pool size p:
+ *     Q_p(x) = avg_pool2d(x, p): kernel and stride p, floor sizes h_p = H / p, w_p = W / p, the trailing rows and columns
+ *              dropped; for p = 1 it is x itself.  A window is summed row-major in fp32 and divided by p^2.
+ *     L(Q)[i][j] = 4 Q[i][j] - Q[i-][j] - Q[i+][j] - Q[i][j-] - Q[i][j+] per channel, the neighbour indices clamped to the map
+ *              (the map replicate-padded, as TVLoss pads the image); the subtractions in that order.
+ *     T_p = L(Q_p(c)), computed once by the setter with the very kernels the closure runs: x == c gives a residual of exactly 0.
+ *     term_p = weight sum((L(Q_p(x)) - T_p)^2) / (3 h_p w_p)
+ * A mean where the paper has a sum: every other term here is a mean, and a weight then means the same at every scale of the
+ * multi-scale loop.  The Laplacian term is the fp32 sum of the term_p in list order, and the gradient is the gradient of
+ * exactly that: pixel (y, x) with y < h_p p and x < w_p p receives (2 weight / (3 h_p w_p p^2)) (L^T r_p)[y / p][x / p], a pixel
+ * in a dropped trailing row or column nothing from that pool size.  L^T folds the clamped neighbours back: a border
+ * position's own row of L names it once more per side at the border - which, for this replicate-padded stencil, makes L^T
+ * equal to L (the operator is symmetric).  Every p must leave a pooled map of at least 2 x 2 (H / p >= 2 and W / p >= 2): on a
+ * 1-wide map the clamped Laplacian is identically zero.
+ *
+ * Accounting.  The 8-float loss array has no free slot in the reference's configuration, and a step's tail forms the total
+ * as 0 + l[0] + ... + l[6].  So slot 6 - and the last entry of st_plan_term_losses, whose count stays n_content + n_style + 1 -
+ * becomes the image-space slot: the TV launch writes tv there as before, then each pool size's final reduction adds its
+ * term_p onto it, in list order, stream-ordered, from one thread: the slot holds fp32(((tv + term_p0) + term_p1) + ...).
+ * st_plan_laplacian_terms reads [tv alone, term_p0, term_p1, ...] of the last closure.  Without a Laplacian nothing changes,
+ * bit for bit.
+ *
+ * st_plan_set_laplacian is synchronous; it allocates Q, r and T per pool size and builds the targets from `content_image`
+ * ([3][H][W] fp32 on the device, at the plan's size; not kept).  NULL clears the Laplacian (the other arguments are then
+ * ignored).  It fails, naming the cause, on a strip plan, for n_pools outside 1 .. 4, a repeated or non-positive p, a p that
+ * leaves less than 2 x 2, and a weight that is not finite and > 0; a refused call leaves the plan without a Laplacian.
+ * Setting or clearing keeps the lists, kinds, eps, weights, masks, maps and every target and invalidates a captured graph.  A
+ * plan with a Laplacian runs the general closure (csrc/st_taps.hip), on the default configuration too, for
+ * st_plan_loss_and_grad, st_plan_step, st_plan_lbfgs_step and st_plan_range_guard: three launches per pool size (pool,
+ * residual and value, gradient add) right behind the TV launch, no floating-point atomics, so two closures give equal bits.
+ * A plan whose Laplacian is cleared is, bit for bit, one that never had one.  It is independent of the style mask, the
+ * regions and the content / TV maps: all may be in force together.  Out of scope: a spatial map on this term, strips.
+ */
+int st_plan_set_laplacian(st_plan* plan, const float* content_image_or_null, int n_pools, const int* pools, float weight,
+                          void* stream);
+/* Borrow T of the k-th pool size (list order): dense [3][h][w] fp32 on the device.  Any output pointer may be null.  Fails when
+ * no Laplacian is set. */
+int st_plan_laplacian(const st_plan* plan, int k, const float** target, int* h, int* w);
+/* The last closure's [tv alone, term_p0, term_p1, ...]: *count = 1 + n_pools device floats owned by the plan.  Fails when no
+ * Laplacian is set. */
+int st_plan_laplacian_terms(st_plan* plan, float** terms, int* count);
+
+/*
  * StyleTransfer.content_layers / style_layers (style_transfer.py:315-317, read by every scale at :425-453): the layers the
  * plan's closure puts its ContentLossMSE and StyleLossW2 terms on.  Each entry is a features index that st_plan_feature
  * accepts - the 13 ReLU outputs 1 3 6 8 11 13 15 17 20 22 24 26 29 and the 4 pool outputs 4 9 18 27; the reference also
@@ -679,6 +725,19 @@ int st_op_scaled_mse_loss_backward(const float* x, const float* target, long lon
 int st_op_tv_value(const float* image, int height, int width, float* scratch, float* loss_out, void* stream);
 /* ... and grad [3][H][W] = upstream[0] * d TVLoss / d image. */
 int st_op_tv_loss_backward(const float* image, int height, int width, const float* upstream, float* grad, void* stream);
+/* The Laplacian loss of st_plan_set_laplacian for ONE pool size on a [C][H][W] image, C >= 1, at weight 1, by the same
+ * kernels.  `scratch`: st_op_laplacian_scratch_floats(C, H, W, pool) floats of the caller's, per call.  The target
+ * [C][H / pool][W / pool] = L(Q(image)) ... */
+long long st_op_laplacian_scratch_floats(int channels, int height, int width, int pool);
+int st_op_laplacian_target(const float* image, int channels, int height, int width, int pool, float* scratch, float* target_out,
+                           void* stream);
+/* ... the value loss_out[0] = sum r^2 / (C h w) with the residual r = L(Q(image)) - target written to residual_out [C][h][w]
+ * (autograd: saved on the node) ... */
+int st_op_laplacian_value(const float* image, const float* target, int channels, int height, int width, int pool, float* scratch,
+                          float* residual_out, float* loss_out, void* stream);
+/* ... and grad [C][H][W] = upstream[0] * d value / d image from that residual: zero in the dropped trailing rows and columns. */
+int st_op_laplacian_backward(const float* residual, int channels, int height, int width, int pool, const float* upstream,
+                             float* grad, void* stream);
 
 /* ==================================================================================================================
  * MEASUREMENT AIDS - not part of the drop-in surface (no reference counterpart; a binding of the reference does not

@@ -105,6 +105,29 @@ __device__ __forceinline__ float block_sum_256(float v, float* scratch) {
     return r;
 }
 
+// In-kernel final reduction ("last block") of the streaming value kernels (st_pointwise.hip, st_laplacian.hip): every block writes
+// its partial sums, then takes a ticket; the block that draws the last one sums all partials in index order.
+struct LastBlock {
+    unsigned int* ticket;     // device word, zero between launches (the last block resets it); nullptr = two-launch form
+};
+__device__ __forceinline__ bool last_block_arrives(const LastBlock& lb, bool* shared_flag) {
+    if (lb.ticket == nullptr) return false;
+    if (threadIdx.x == 0) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const unsigned int prev = atomicAdd(lb.ticket, 1u);
+        const bool last = (prev == gridDim.x - 1);
+        if (last) *lb.ticket = 0u;
+        *shared_flag = last;
+    }
+    __syncthreads();
+    const bool last = *shared_flag;
+    // every thread of the last block reads other blocks' partials: each needs its own agent-scope acquire (a CU's
+    // vector L1 is never refreshed by another CU's stores; one lane's fence is not a guarantee for the other waves)
+    if (last) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    return last;
+}
+
 // StyleLossW2.forward's scalars for one head (style_transfer.py:178-181): the loss term and the seed of its backward,
 // d loss / d root = gdiag * I.  A job rides along in the kernel that opens the Lyapunov backward chain (ns_prepare_kernel /
 // ns_backward_entry_kernel) instead of being a launch of its own on the heads' critical path; loss_out == nullptr: no job.
@@ -661,6 +684,21 @@ int launch_mask_columns_add(float* dst, const float* src, const float* sqrt_mask
 // out[j] = region_terms[0][j] + region_terms[1][j] + ... in region order (fp32), j < n_style; region_terms is [regions][n_style].
 // One region: out[j] takes region_terms[0][j] as it is.
 int launch_sum_region_terms(const float* region_terms, int regions, int n_style, float* out, hipStream_t s);
+// ---- Laplacian loss on pooled images (st_plan_set_laplacian, st_op_laplacian_*; st_laplacian.hip) ----
+constexpr int kMaxLapPools = 4;
+constexpr int kLapBlocks = 1024;                  // workgroups of the residual pass at most: its partials
+// Q [C][H / p][W / p] = avg_pool2d(image [C][H][W], p) at floor sizes, each window summed row-major
+int launch_lap_pool(const float* image, int C, int H, int W, int p, float* Q, hipStream_t s);
+// target == nullptr: out = L(Q) on [C][h][w] (the target pass).  Otherwise out = r = L(Q) - target and term_out[0] =
+// weight sum r^2 / (C h w) from partials (kLapBlocks floats), finished by the kernel's last block (ticket: a zeroed device
+// word) or, without a ticket, by a second launch.  With a ticket: tv_out (optional) first receives slot[0], then slot[0] (optional)
+// += the term - one thread, stream-ordered.
+int launch_lap_residual(const float* Q, const float* target, int C, int h, int w, float weight, float* out, float* partials,
+                        unsigned int* ticket, float* term_out, float* tv_out, float* slot, hipStream_t s);
+// grad [C][H][W] (+)= (2 weight / (C h w p^2)) (L^T r)[y / p][x / p] inside the pooled region (accumulate != 0: added, the rest
+// untouched; else written, zeros outside); upstream (optional): a device scalar that multiplies the factor
+int launch_lap_grad(const float* r, int C, int H, int W, int p, float weight, const float* upstream, float* grad, int accumulate,
+                    hipStream_t s);
 // TV loss partial sums + gradient (optionally scaled by `weight`): see st_pointwise.hip.  wmap (st_plan_set_tv_mask): [height][width],
 // every squared difference weighed by the mean of the map at its two end points; null: the unweighted kernels
 int launch_tv(const float* image, int height, int width, float weight, float* grad, float* partials,

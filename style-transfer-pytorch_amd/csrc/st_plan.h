@@ -1,5 +1,6 @@
 // Internal to libst_amd.so: the VGG-19 program, the plan's nodes and head sites, st_net / st_plan, and the plan helpers
-// that more than one of st_api.hip, st_closure.hip, st_taps.hip, st_mask.hip, st_strip.hip and st_range_guard.hip call.
+// that more than one of st_api.hip, st_closure.hip, st_taps.hip, st_mask.hip, st_laplacian.hip, st_strip.hip and
+// st_range_guard.hip call.
 // (StyleHead and a head's launch sequence: st_head_core.h, shared with st_head.hip; the wrappers below add the plan's part.)
 #pragma once
 
@@ -174,6 +175,19 @@ struct st_plan {
     bool content_mask = false, tv_mask = false;
     float* content_map[st::kMaskLevels] = {};        // allocated by the first setter call
     float* tv_map = nullptr;
+    // Laplacian loss on pooled images (st_plan_set_laplacian, st_laplacian.hip): n_lap pool sizes, each with its pooled map Q
+    // (unused for p = 1), residual r and target T = L(Q(content)), all [3][lap_h][lap_w].  The general closure runs while
+    // n_lap > 0 (general_taps) and adds each term onto the image-space slot and its gradient onto the TV gradient, right
+    // behind the TV launch.  Independent of the masks, regions and maps.
+    int n_lap = 0;                                   // 0: none in force
+    int lap_pool[st::kMaxLapPools] = {}, lap_h[st::kMaxLapPools] = {}, lap_w[st::kMaxLapPools] = {};
+    float lap_weight = 0.f;
+    float* lap_q[st::kMaxLapPools] = {};
+    float* lap_r[st::kMaxLapPools] = {};
+    float* lap_t[st::kMaxLapPools] = {};
+    size_t lap_floats[st::kMaxLapPools] = {};        // what slot k's three buffers hold
+    float* lap_partials = nullptr;                   // [kLapBlocks] of the residual pass in flight
+    float* lap_terms = nullptr;                      // [0] the TV term alone, [1 + k] pool size k's term (st_plan_laplacian_terms)
     float* grad_img = nullptr;       // [3][H][W] internal gradient for st_plan_step
     float* losses = nullptr;         // [8] device
     float* red_partials = nullptr;   // scratch for two-level reductions: TV [0, 4 kStreamBlocks), content MSE after it
@@ -367,6 +381,11 @@ bool targets_ready(const st_plan* p);
 float* loss_terms(st_plan* p);        // the array the closure's weighted terms go to, in SumLoss order
 float style_eps_of(const st_plan* p, int j);   // effective eps of style entry j / content entry i (mse: -1)
 float content_eps_of(const st_plan* p, int i);
+
+// ---- st_laplacian.hip
+// the plan's Laplacian terms on `image`, behind the TV launch that wrote `grad` and `slot`: each pool size's term onto the
+// slot and its gradient onto grad, in list order
+int laplacian_terms(st_plan* p, const float* image, float* grad, float* slot, hipStream_t s);
 
 // ---- st_mask.hip
 // style regions in force: the heads of regions 1 .. R - 1 for these style positions under these kinds (st_plan_set_style_regions,

@@ -117,27 +117,7 @@ __global__ __launch_bounds__(256) void ns_prepare_kernel(const float* __restrict
 // Saves the second launch - a single wave that, next to the trunk's persistent convolution workgroups, used to
 // wait up to 0.7 ms for a free CU at 2048^2.  Release / acquire at agent scope as MI355X_MICROARCH.md prescribes
 // (the asm waitcnt keeps the ticket behind the write-back of the partials).
-struct LastBlock {
-    unsigned int* ticket;     // device word, zero between launches (the last block resets it); nullptr = two-launch form
-};
-__device__ __forceinline__ bool last_block_arrives(const LastBlock& lb, bool* shared_flag) {
-    if (lb.ticket == nullptr) return false;
-    if (threadIdx.x == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const unsigned int prev = atomicAdd(lb.ticket, 1u);
-        const bool last = (prev == gridDim.x - 1);
-        if (last) *lb.ticket = 0u;
-        *shared_flag = last;
-    }
-    __syncthreads();
-    const bool last = *shared_flag;
-    // every thread of the last block reads other blocks' partials: each needs its own agent-scope acquire (a CU's
-    // vector L1 is never refreshed by another CU's stores; one lane's fence is not a guarantee for the other waves)
-    if (last) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    return last;
-}
-
+// (LastBlock / last_block_arrives: st_common.h, shared with st_laplacian.hip)
 // ACC (general closure, st_taps.hip): the layer is a style layer as well, whose head has WRITTEN grad - this term's is added.
 template <bool ACC>
 __global__ __launch_bounds__(256) void content_mse_kernel(const float* __restrict__ feat,

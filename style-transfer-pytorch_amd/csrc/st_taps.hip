@@ -49,6 +49,10 @@
 // launch gets the map (launch_tv's weighted kernels); a content entry gets the content map's level of its tap and runs the
 // weighted siblings of its kind's launches (launch_content_mse_weighted, launch_scaled_mse_*_weighted), which write or add
 // the seed as the unweighted ones do.  Everything behind the seeds is unchanged.
+//
+// A Laplacian loss (st_plan_set_laplacian, st_laplacian.hip) runs it as well: a pure image-space term like TV, launched right
+// behind it - each pool size's term is added onto the TV term's slot (the image-space slot: the last entry of the terms) and
+// its gradient onto the TV gradient, which run_tap_backward then adds the trunk's onto.
 #include <algorithm>
 #include <cmath>
 
@@ -105,7 +109,7 @@ static bool default_eps(const st_plan* p) {
 bool general_taps(const st_plan* p) {
     static Option force("ST_GENERAL_TAPS", 0);
     return !p->strip && (!p->reference_taps || !default_kinds(p) || !default_eps(p) || p->style_mask || p->n_regions > 0 ||
-                         p->content_mask || p->tv_mask || force.get() != 0);
+                         p->content_mask || p->tv_mask || p->n_lap > 0 || force.get() != 0);
 }
 
 float style_eps_of(const st_plan* p, int j) {
@@ -237,6 +241,8 @@ int general_loss_and_grad(st_plan* p, const float* image, float* grad_out, float
             return launch_tv(image, p->H, p->W, p->tv_weight, grad_out, p->red_partials, terms + nc + ns, s, p->tickets + 0, tv_map);
         }))
         return 1;
+    // the Laplacian terms (st_plan_set_laplacian): onto the TV term's slot and onto the gradient it wrote, before the trunk's
+    if (p->n_lap && laplacian_terms(p, image, grad_out, terms + nc + ns, s)) return 1;
     const int top = closure_top_op(p);
     if (run_forward(p, image, kProgram[top].feat_index, s, /*fork_heads=*/false)) return 1;
     // style heads, deepest first (the deepest one's gradient is what the backward starts from)

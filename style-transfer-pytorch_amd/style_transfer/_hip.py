@@ -73,6 +73,9 @@ def _declare(lib):
         'st_plan_content_mask': (i32, [vp, i32, pp, ip, ip]),
         'st_plan_set_tv_mask': (i32, [vp, vp, vp]),
         'st_plan_tv_mask': (i32, [vp, pp, ip, ip]),
+        'st_plan_set_laplacian': (i32, [vp, vp, i32, ip, f32, vp]),
+        'st_plan_laplacian': (i32, [vp, i32, pp, ip, ip]),
+        'st_plan_laplacian_terms': (i32, [vp, pp, ip]),
         'st_plan_set_content_target': (i32, [vp, vp, vp]),
         'st_plan_set_style_target': (i32, [vp, i32, vp, vp, vp]),
         'st_plan_set_loss_weights': (i32, [vp, f32, ctypes.POINTER(f32), f32]),
@@ -148,6 +151,10 @@ def _declare(lib):
         'st_op_scaled_mse_loss_backward': (i32, [vp, vp, i64, vp, vp, vp, vp]),
         'st_op_tv_value': (i32, [vp, i32, i32, vp, vp, vp]),
         'st_op_tv_loss_backward': (i32, [vp, i32, i32, vp, vp, vp]),
+        'st_op_laplacian_scratch_floats': (i64, [i32, i32, i32, i32]),
+        'st_op_laplacian_target': (i32, [vp, i32, i32, i32, i32, vp, vp, vp]),
+        'st_op_laplacian_value': (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
+        'st_op_laplacian_backward': (i32, [vp, i32, i32, i32, i32, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)       # AttributeError here = header and library disagree
@@ -620,6 +627,46 @@ class Plan:
         _check(self.lib.st_plan_tv_mask(self.handle, ctypes.byref(data), ctypes.byref(h), ctypes.byref(w)))
         out = torch.empty((h.value, w.value), device=self.device, dtype=torch.float32)
         with torch.cuda.device(self.device):
+            _copy_d2d(out, data.value)
+        return out
+
+    def set_laplacian(self, content_image, pools=(4,), weight=1.0):
+        """A Laplacian loss on average-pooled images (st_plan_set_laplacian): ``content_image`` a [3, height, width] (or
+        [1, 3, height, width]) tensor at the plan's size, or None to clear the term; ``pools`` 1 to 4 distinct pool sizes, each
+        leaving a pooled map of at least 2 x 2; ``weight`` finite and > 0.  While it is set every closure and step adds
+        ``weight * mean((L(avg_pool(x, p)) - L(avg_pool(content, p))) ** 2)`` per pool size onto the image-space slot (the TV
+        term's) and its gradient onto the image gradient.  Every target stays.  Raises ValueError for another size,
+        HipLibraryError for what the library refuses (a strip plan, the pools, the weight); a refused call leaves the plan
+        without a Laplacian."""
+        with torch.cuda.device(self.device):
+            if content_image is None:
+                _check(self.lib.st_plan_set_laplacian(self.handle, None, 0, None, 0.0, _stream()))
+                return
+            content_image = torch.as_tensor(content_image)
+            if tuple(content_image.shape[-3:]) != (3, self.height, self.width) or content_image.numel() != 3 * self.height * self.width:
+                raise ValueError(f'content image of shape {tuple(content_image.shape)}: the plan is 3 x {self.height} x {self.width}')
+            content_image = content_image.to(self.device, torch.float32).contiguous()
+            pools = [int(p) for p in pools]
+            pa = (ctypes.c_int * max(len(pools), 1))(*pools)
+            _check(self.lib.st_plan_set_laplacian(self.handle, _ptr(content_image), len(pools), pa, float(weight), _stream()))
+
+    def laplacian_target(self, k):
+        """The target ``L(avg_pool(content, p_k))`` of the k-th pool size as a [3, h, w] tensor (a copy; st_plan_laplacian).
+        Raises HipLibraryError when no Laplacian is set."""
+        data, h, w = ctypes.c_void_p(), ctypes.c_int(), ctypes.c_int()
+        _check(self.lib.st_plan_laplacian(self.handle, int(k), ctypes.byref(data), ctypes.byref(h), ctypes.byref(w)))
+        out = torch.empty((3, h.value, w.value), device=self.device, dtype=torch.float32)
+        with torch.cuda.device(self.device):
+            _copy_d2d(out, data.value)
+        return out
+
+    def laplacian_terms(self):
+        """``[tv alone, term_p0, term_p1, ...]`` of the last closure as a device tensor (a copy; st_plan_laplacian_terms): the
+        last entry of ``term_losses`` is their fp32 sum in this order.  Raises HipLibraryError when no Laplacian is set."""
+        data, n = ctypes.c_void_p(), ctypes.c_int()
+        with torch.cuda.device(self.device):
+            _check(self.lib.st_plan_laplacian_terms(self.handle, ctypes.byref(data), ctypes.byref(n)))
+            out = torch.empty(n.value, device=self.device, dtype=torch.float32)
             _copy_d2d(out, data.value)
         return out
 
@@ -1173,4 +1220,44 @@ def op_tv_loss_backward(image, upstream):
     grad = torch.empty(image.shape, device=image.device, dtype=torch.float32)
     with torch.cuda.device(image.device):
         _check(lib.st_op_tv_loss_backward(_ptr(image), h, w, _ptr(upstream), _ptr(grad), _stream()))
+    return grad
+
+
+def _laplacian_shape(image, pool):
+    c, h, w = image.shape[-3:]
+    return int(c), int(h), int(w), int(pool)
+
+
+def op_laplacian_target(image, pool):
+    """``L(avg_pool2d(image, pool))`` of a [..., C, H, W] image (one image) as a [C, H // pool, W // pool] device tensor
+    (st_op_laplacian_target): the 4-neighbour Laplacian on the replicate-padded pooled map."""
+    lib = load_library()
+    c, h, w, pool = _laplacian_shape(image, pool)
+    target = torch.empty((c, h // pool, w // pool), device=image.device, dtype=torch.float32)
+    scratch = torch.empty(max(int(lib.st_op_laplacian_scratch_floats(c, h, w, pool)), 1), device=image.device, dtype=torch.float32)
+    with torch.cuda.device(image.device):
+        _check(lib.st_op_laplacian_target(_ptr(image), c, h, w, pool, _ptr(scratch), _ptr(target), _stream()))
+    return target
+
+
+def op_laplacian_value(image, target, pool):
+    """(mean((L(avg_pool2d(image, pool)) - target) ** 2) [0-dim], the residual [C, h, w]) - st_op_laplacian_value."""
+    lib = load_library()
+    c, h, w, pool = _laplacian_shape(image, pool)
+    loss = torch.empty((), device=image.device, dtype=torch.float32)
+    residual = torch.empty((c, h // pool, w // pool), device=image.device, dtype=torch.float32)
+    scratch = torch.empty(max(int(lib.st_op_laplacian_scratch_floats(c, h, w, pool)), 1), device=image.device, dtype=torch.float32)
+    with torch.cuda.device(image.device):
+        _check(lib.st_op_laplacian_value(_ptr(image), _ptr(target), c, h, w, pool, _ptr(scratch), _ptr(residual), _ptr(loss), _stream()))
+    return loss, residual
+
+
+def op_laplacian_backward(residual, shape, pool, upstream):
+    """The gradient of ``op_laplacian_value`` times the device scalar ``upstream``, as a tensor of the image's ``shape``
+    (st_op_laplacian_backward)."""
+    lib = load_library()
+    c, h, w = (int(d) for d in shape[-3:])
+    grad = torch.empty(tuple(shape), device=residual.device, dtype=torch.float32)
+    with torch.cuda.device(residual.device):
+        _check(lib.st_op_laplacian_backward(_ptr(residual), c, h, w, int(pool), _ptr(upstream), _ptr(grad), _stream()))
     return grad

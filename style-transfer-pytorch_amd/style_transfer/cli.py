@@ -323,6 +323,12 @@ def build_parser():
     p.add_argument('--tv-mask', type=str, default=None, metavar='PATH',
                    help='an image (read as greyscale, white = 1) saying where the output is smoothed: the TV term is weighed by '
                         'it per pixel; it is resized to every scale')
+    p.add_argument('--laplacian-weight', type=float, default=0., metavar='FLOAT',
+                   help='weight of the Laplacian loss (Li et al.): keeps the edges and fine structure of the content image - the '
+                        'mean squared difference between the Laplacians of the pooled output and the pooled content image '
+                        '(default 0: no such term)')
+    p.add_argument('--laplacian-pools', type=int, default=[4], nargs='+', metavar='INT',
+                   help='the pool sizes of the Laplacian loss, 1 to 4 distinct positive integers (default: 4)')
     p.add_argument('--trace', type=str, default='trace.json', help='where to write the iteration trace')
     return p
 
@@ -347,6 +353,13 @@ def apply_weight_maps(st, args):
             _fail(err)
     st.content_mask = None if args.content_mask is None else load(args.content_mask)
     st.tv_mask = None if args.tv_mask is None else load(args.tv_mask)
+    return st
+
+
+def apply_laplacian(st, args):
+    """--laplacian-weight / --laplacian-pools onto the StyleTransfer attributes that stylize() reads."""
+    st.laplacian_weight = args.laplacian_weight
+    st.laplacian_pools = tuple(args.laplacian_pools)
     return st
 
 
@@ -438,6 +451,7 @@ def main(argv=None):
     apply_loss_kinds(st, args)
     apply_style_masks(st, args)
     apply_weight_maps(st, args)
+    apply_laplacian(st, args)
     callback = Callback(st, args, image_type=image_type, web_interface=web_interface)
     atexit.register(callback.close)
 

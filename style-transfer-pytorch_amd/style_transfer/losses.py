@@ -5,7 +5,9 @@ section 2 row 2).
 libst_amd.so.  User code written against the reference can however import these names from
 ``style_transfer.style_transfer`` - ``ScaledMSELoss``, ``ContentLoss``, ``ContentLossMSE``, ``StyleLoss``,
 ``StyleLossW2``, ``TVLoss``, ``SumLoss``, ``Scale``, ``LayerApply``, ``eye_like`` (reference :93-234) - so they are
-provided here with the reference's constructor arguments, buffers, static helpers and arithmetic.
+provided here with the reference's constructor arguments, buffers, static helpers and arithmetic.  ``LaplacianLoss`` is this
+project's own (include/st_amd.h fixes its semantics): the module form of ``st_plan_set_laplacian``'s term, dispatched like the
+others - one dense fp32 HIP image, any channel count, runs st_op_laplacian_value / st_op_laplacian_backward per pool size.
 
 Native dispatch.  On an ELIGIBLE tensor (``eligible`` below: one dense fp32 tensor on a HIP device, batch 1 or absent, 64 /
 128 / 256 / 512 channels for the style modules, the module's buffers beside it in fp32) the five loss modules run in the
@@ -57,7 +59,7 @@ class native:
         native.enabled, native.precision = self._former
 
 
-# calls that went to the library, by kind ('w2', 'gram', 'mse', 'scaled_mse', 'tv', 'moments'): the native indicator of the
+# calls that went to the library, by kind ('w2', 'gram', 'mse', 'scaled_mse', 'tv', 'laplacian', 'moments'): the native indicator of the
 # modules that hold no head
 native_calls = {}
 _heads = weakref.WeakKeyDictionary()       # module -> its _hip.Head (no module attribute: deepcopy / pickle / state_dict never see it)
@@ -81,7 +83,7 @@ def _buffer_ok(b, like, numel):
 
 
 def eligible(input, kind, buffers=()):
-    """Can ``input`` take the native path of ``kind`` ('w2', 'gram', 'mse', 'scaled_mse', 'tv', 'moments')?  ``buffers``: the
+    """Can ``input`` take the native path of ``kind`` ('w2', 'gram', 'mse', 'scaled_mse', 'tv', 'laplacian', 'moments')?  ``buffers``: the
     module's tensors that the library would read in place - (mean, cov, cov_sqrt), (gram target,) or (target,).  Says nothing
     about the ``native`` switch."""
     if kind in ('w2', 'gram', 'moments'):
@@ -95,6 +97,10 @@ def eligible(input, kind, buffers=()):
         if not (_one_dense_fp32(input, 3) and input.ndim in (3, 4) and input.shape[-3] == 3 and input.numel() < 1 << 31):
             return False
         sizes = ()
+    elif kind == 'laplacian':
+        # (buffers: one target per pool size, each of its own size - checked by the module, which knows the pools)
+        return _one_dense_fp32(input, 3) and input.ndim in (3, 4) and input.numel() < 1 << 31 and \
+            all(_buffer_ok(b, input, b.numel()) for b in buffers)
     else:
         if not (torch.is_tensor(input) and _one_dense_fp32(input, min(input.ndim, 3))):
             return False
@@ -279,6 +285,40 @@ class _TVLoss(torch.autograd.Function):
         return _hip.op_tv_loss_backward(_dense(input), grad_output.contiguous()).view(input.shape), None
 
 
+class _LaplacianLoss(torch.autograd.Function):
+    """LaplacianLoss.forward: st_op_laplacian_value per pool size, the values added in list order; the residuals are what
+    st_op_laplacian_backward needs."""
+
+    @staticmethod
+    def forward(ctx, input, module, targets):
+        from . import _hip
+        x = _dense(input)
+        loss, residuals = None, []
+        for pool, target in zip(module.pools, targets):
+            value, residual = _hip.op_laplacian_value(x, target, pool)
+            loss = value if loss is None else loss + value
+            residuals.append(residual)
+        _count('laplacian')
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(input, *residuals)
+            ctx.torch_forward = module._forward_torch
+            ctx.pools = module.pools
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        from . import _hip
+        input, *residuals = ctx.saved_tensors
+        if torch.is_grad_enabled():
+            return _torch_vjp(ctx.torch_forward, input, grad_output), None, None
+        upstream = grad_output.contiguous()
+        grad = None
+        for pool, residual in zip(ctx.pools, residuals):
+            part = _hip.op_laplacian_backward(residual, input.shape, pool, upstream)
+            grad = part if grad is None else grad + part
+        return grad, None, None
+
+
 class ScaledMSELoss(nn.Module):
     """Sum of squared differences over the L1 norm of the difference (+ eps): an MSE whose gradient has an L1
     norm of about one (reference :93-106)."""
@@ -424,6 +464,83 @@ class TVLoss(nn.Module):
         diag_se = (x[..., 1:, 1:] - x[..., :-1, :-1]).pow(2).mean() / 12
         diag_sw = (x[..., 1:, :-1] - x[..., :-1, 1:]).pow(2).mean() / 12
         return 2 * (right + down + diag_se + diag_sw)
+
+
+def laplacian(x):
+    """The 4-neighbour Laplacian of a [..., h, w] map per channel, the map replicate-padded (as TVLoss pads the image):
+    ``4 x[i][j] - x[i-][j] - x[i+][j] - x[i][j-] - x[i][j+]`` with the neighbour indices clamped to the map."""
+    up = torch.cat([x[..., :1, :], x[..., :-1, :]], -2)
+    down = torch.cat([x[..., 1:, :], x[..., -1:, :]], -2)
+    left = torch.cat([x[..., :, :1], x[..., :, :-1]], -1)
+    right = torch.cat([x[..., :, 1:], x[..., :, -1:]], -1)
+    return 4 * x - up - down - left - right
+
+
+def check_laplacian_pools(pools, height=None, width=None):
+    """``pools`` as a tuple of 1 to 4 distinct positive integers, each - where a size is given - leaving a pooled map of at
+    least 2 x 2 (on a 1-wide map the clamped Laplacian vanishes).  Raises ``ValueError``."""
+    try:
+        pools = tuple(pools)
+    except TypeError:
+        raise ValueError(f'pools {pools!r}: must be a sequence of 1 to 4 distinct positive integers') from None
+    if not 1 <= len(pools) <= 4 or any(isinstance(p, bool) or not isinstance(p, int) or p < 1 for p in pools) or \
+            len(set(pools)) != len(pools):
+        raise ValueError(f'pools {pools!r}: must be 1 to 4 distinct positive integers')
+    if height is not None:
+        for p in pools:
+            if height // p < 2 or width // p < 2:
+                raise ValueError(f'pools {pools!r}: pool size {p} leaves a {height // p} x {width // p} map of the {height} x {width} '
+                                 'image; the pooled map must be at least 2 x 2')
+    return pools
+
+
+class LaplacianLoss(nn.Module):
+    """The Laplacian loss of Li et al., "Laplacian-Steered Neural Style Transfer", as this project fixes it (include/st_amd.h,
+    st_plan_set_laplacian): the sum over ``pools`` - in list order - of ``mean((L(avg_pool2d(input, p)) - T_p) ** 2)`` with
+    ``L`` the 4-neighbour Laplacian on the replicate-padded pooled map and ``T_p = L(avg_pool2d(content_image, p))``, a buffer.
+    Not in the reference.  The torch path serves any device, dtype and batch; one dense fp32 HIP image runs in the library
+    (lap_pool_kernel, lap_residual_kernel, lap_grad_kernel)."""
+
+    def __init__(self, content_image, pools=(4,)):
+        super().__init__()
+        content_image = torch.as_tensor(content_image)
+        if content_image.ndim < 3:
+            raise ValueError(f'content image of shape {tuple(content_image.shape)}: must be [..., C, H, W]')
+        self.pools = check_laplacian_pools(pools, *content_image.shape[-2:])
+        with torch.no_grad():
+            for k, p in enumerate(self.pools):
+                self.register_buffer(f'target_{k}', self._laplacian_of(content_image.detach(), p))
+
+    def extra_repr(self):
+        return f'pools={self.pools}'
+
+    @staticmethod
+    def _laplacian_of(image, pool):
+        if native.enabled and eligible(image, 'laplacian'):
+            from . import _hip
+            # the library's own kernels, so that the content image itself gives a residual of exactly 0 on the native path
+            return _hip.op_laplacian_target(_dense(image), pool).view(image.shape[:-2] + (image.shape[-2] // pool, image.shape[-1] // pool))
+        return laplacian(image if pool == 1 else F.avg_pool2d(image, pool))
+
+    def targets(self):
+        return [getattr(self, f'target_{k}') for k in range(len(self.pools))]
+
+    def forward(self, input):
+        targets = self.targets()
+        if native.enabled and eligible(input, 'laplacian', targets):
+            c, h, w = input.shape[-3:]
+            # (one target per pool size, of that pool size's shape for THIS input, batch 1 or absent)
+            if all(t.shape[-3:] == (c, h // p, w // p) and t.numel() == c * (h // p) * (w // p) for t, p in zip(targets, self.pools)):
+                return _LaplacianLoss.apply(input, self, targets)
+        return self._forward_torch(input)
+
+    def _forward_torch(self, input):
+        total = None
+        for p, target in zip(self.pools, self.targets()):
+            q = input if p == 1 else F.avg_pool2d(input, p)
+            term = (laplacian(q) - target).pow(2).mean()
+            total = term if total is None else total + term
+        return total
 
 
 class SumLoss(nn.ModuleList):

@@ -27,7 +27,7 @@ import torch
 from PIL import Image
 from torch.nn import functional as F
 
-from . import _hip, sqrtm, vgg  # noqa: F401  (sqrtm: importable as in the reference, :17)
+from . import _hip, losses, sqrtm, vgg  # noqa: F401  (sqrtm: importable as in the reference, :17)
 # the reference defines its loss / bookkeeping modules in this file (:93-234); user code imports them from here
 from .losses import (ContentLoss, ContentLossMSE, LayerApply, Scale, ScaledMSELoss, StyleLoss,  # noqa: F401
                      StyleLossW2, SumLoss, TVLoss, eye_like)
@@ -356,6 +356,34 @@ def _resolve_weight_maps(content_mask, tv_mask, world=1):
             raise ValueError(f'{attr} on {world} ranks: row strips take no content or TV map (the general closure serves them); '
                              'maps are out of scope for strips - run them on one device')
     return tuple(maps)
+
+
+def _resolve_laplacian(laplacian_weight, laplacian_pools, height=None, width=None, world=1):
+    """``StyleTransfer.laplacian_weight`` / ``laplacian_pools`` as stylize() takes them: None for a weight of 0 (no term, the
+    setter is not called), else (weight, pools) for ``Plan.set_laplacian``.  ``height`` x ``width`` is the SMALLEST scale's image
+    (None: no size to check): a pool size that leaves it a 2 x 2 map leaves every scale one.  Raises ``ValueError`` naming the attribute for a negative
+    or non-finite weight, pools that are not 1 to 4 distinct positive integers, a pool too large for that image, and for a
+    non-zero weight on several ranks, before any device work."""
+    try:
+        weight = float(laplacian_weight)
+    except (TypeError, ValueError):
+        raise ValueError(f'laplacian_weight {laplacian_weight!r}: must be a number >= 0') from None
+    if not math.isfinite(weight) or weight < 0:
+        raise ValueError(f'laplacian_weight {laplacian_weight!r}: must be finite and >= 0 (0: no Laplacian term)')
+    try:
+        pools = losses.check_laplacian_pools(laplacian_pools)
+        if weight > 0:
+            losses.check_laplacian_pools(pools, height, width)
+    except ValueError as exc:
+        detail = str(exc).split(': ', 1)[1]
+        raise ValueError(f'laplacian_pools {laplacian_pools!r}: {detail}' + (
+            ' at the smallest scale' if 'leaves' in detail else '')) from None
+    if weight == 0:
+        return None
+    if world > 1:
+        raise ValueError(f'laplacian_weight {weight:g} on {world} ranks: row strips take no Laplacian term (the general closure '
+                         'serves it); it is out of scope for strips - run it on one device')
+    return weight, pools
 
 
 MAX_STYLE_REGIONS = 4
@@ -809,6 +837,12 @@ class StyleTransfer:
     # of each other and of the style masks and regions; one device only.
     content_mask = None
     tv_mask = None
+    # A Laplacian loss on average-pooled images (Li et al., "Laplacian-Steered Neural Style Transfer"; read by stylize() next
+    # to content_mask; _hip.Plan.set_laplacian): laplacian_weight times, per pool size p of laplacian_pools, the mean squared
+    # difference between the 4-neighbour Laplacian of avg_pool2d(image, p) and that of the pooled content image - the
+    # content's edges and fine structure survive the style.  0: no term.  One device only.
+    laplacian_weight = 0.
+    laplacian_pools = (4,)
 
     def __init__(self, devices=['cuda:0'], pooling='max', weights=None, precision='fp16x3'):
         # reference :310 defaults to ['cpu']; this build has no CPU path, so the default is the first HIP device
@@ -1075,6 +1109,11 @@ class StyleTransfer:
                                          world=max(len(self.devices), _dist_info()[1]))
         content_map, tv_map = _resolve_weight_maps(self.content_mask, self.tv_mask,
                                                    world=max(len(self.devices), _dist_info()[1]))
+        # (the smallest scale's image bounds the pool sizes; a weight of 0 has no term and no size to check)
+        smallest = (None, None) if not self.laplacian_weight else size_to_fit(
+            content_image.size, gen_scales(min(min_scale, end_scale), end_scale)[0], scale_up=True)
+        laplacian = _resolve_laplacian(self.laplacian_weight, self.laplacian_pools, smallest[1], smallest[0],
+                                       world=max(len(self.devices), _dist_info()[1]))
         if len(self.devices) > 1 and self._job is None:
             return _device_list_stylize(self, content_image, style_images, dict(
                 style_weights=style_weights, content_weight=content_weight, tv_weight=tv_weight, optimizer=optimizer,
@@ -1213,6 +1252,9 @@ class StyleTransfer:
                     plan.set_content_mask(_sized_mask(content_map, cw, ch))
                 if tv_map is not None:
                     plan.set_tv_mask(_sized_mask(tv_map, cw, ch))
+                # ... and the Laplacian term, against this scale's content image
+                if laplacian is not None:
+                    plan.set_laplacian(content.to(device), laplacian[1], laplacian[0])
             plan.set_loss_weights(content_weights, layer_weights, tv_weight)
             if sharded and self.model.net.precision == 'fp16x3':
                 # ... sharded: on this rank's rows of the iterate, against the scale's style targets; the union of the ranks'
