@@ -348,7 +348,8 @@ int st_plan_loss_kinds(const st_plan* plan, int* content_kind, int* style_kind);
  * stay; a failed allocation leaves the plan as it was; strip plans take the defaults only.  A later st_plan_set_taps keeps
  * the kind of a list whose entries agree and returns a mixed list to kind 0.  st_plan_layer_loss_kinds writes n_content /
  * n_style codes (either pointer may be null).
- * Order of configuration: layers (st_plan_set_taps), kinds, eps (st_plan_set_loss_eps), weights, then the targets.
+ * Order of configuration: layers (st_plan_set_taps), kinds, eps (st_plan_set_loss_eps), diagonal (st_plan_set_w2_diagonal),
+ * weights, then the targets.
  */
 int st_plan_set_layer_loss_kinds(st_plan* plan, const int* content_kinds, const int* style_kinds);
 int st_plan_layer_loss_kinds(const st_plan* plan, int* content_kinds, int* style_kinds);
@@ -369,6 +370,35 @@ int st_plan_layer_loss_kinds(const st_plan* plan, int* content_kinds, int* style
  */
 int st_plan_set_loss_eps(st_plan* plan, const float* content_eps, const float* style_eps);
 int st_plan_loss_eps(const st_plan* plan, float* content_eps, float* style_eps);
+
+/*
+ * StyleLossW2 with BOTH covariances restricted to their diagonals, per W2 style layer: flags[n_style], 0 or 1 in list order;
+ * a null pointer clears all.  For two Gaussians with diagonal covariances W2^2 = sum_c (mu - mu_t)^2 + sum_c (sigma - sigma_t)^2:
+ * the mean / standard-deviation (batch-norm statistics) loss of Li et al., "Demystifying Neural Style Transfer", and the
+ * statistic AdaIN matches.  It is an OPTION of a w2 layer - the kind names and codes do not change - and the reference has no
+ * such module, so the semantics are fixed here.  On the tap F [C][h w] of flagged entry j, with pixel weights m_p and
+ * M = sum_p m_p (no style mask: m = 1, M = N; a mask or regions: the level and sum the entry's head already reads):
+ *   mu_c  = sum_p m_p f_cp / M          q_c = sum_p m_p f_cp^2 / M
+ *   v_c   = max(q_c - mu_c^2, 0) + eps  sigma_c = sqrt(v_c)             (eps: the layer's style eps, default 1e-4, as for W2)
+ *   target, from the SAME (mean, srm) that st_plan_set_style_target / st_plan_set_region_style_target are given:
+ *   mut_c = mean_c,  vt_c = max(srm_cc - mean_c^2, 0) + eps,  sigmat_c = sqrt(vt_c)   (only srm's diagonal is read; no sqrtm runs)
+ *   term_j = w_j (sum_c (mu_c - mut_c)^2 + sum_c (sigma_c - sigmat_c)^2) / C
+ *   dF_cp  = w_j (m_p / M) ((2 / C) (mu_c - mut_c) + 2 g_c (f_cp - mu_c)),  g_c = (1 - sigmat_c / sigma_c) / C, 0 where sigma_c = 0
+ * This is StyleLossW2.forward with cov -> diag(cov).  The variance term is (sigma - sigma_t)^2, not v + v_t - 2 sqrt(v v_t),
+ * which cancels near the target: the first form gives exactly 0 and an exactly zero gradient there.  With regions the entry's
+ * weight is style_weight[j] rho_r, the term lands in slot (r, j), region 0 writes the seed and regions r >= 1 add onto it in
+ * region order; a content term of the same layer is added after, as for every head.
+ * A flagged head is two memory-bound launches (csrc/st_w2diag.hip) - no Gram pass, no Newton-Schulz chain, no 1x1 step, no
+ * fp16x3 operand bound - and allocates 2 C target floats, the partial sums, 2 C coefficients and a ticket: no C x C buffer.
+ * Any set flag runs the general closure (csrc/st_taps.hip), on the default lists too; a plan whose flags are all 0 is, bit
+ * for bit, one on which this was never called, and the default configuration stays on its own closure.  Like
+ * st_plan_set_loss_eps the call drops every target set before and invalidates a captured graph; either kinds setter and
+ * st_plan_set_taps clear the flags.  Fails for a flag on a gram entry, for a value other than 0 or 1, and for any set flag on
+ * a strip plan.  st_plan_term_losses, st_plan_region_terms and the 8-float array keep their shapes.
+ * Order of configuration: layers, kinds, eps, diagonal, weights, then the targets.
+ */
+int st_plan_set_w2_diagonal(st_plan* plan, const int* flags);
+int st_plan_w2_diagonal(const st_plan* plan, int* flags);
 
 /* ContentLossMSE target (style_transfer.py:425-429): copies feat [512][H/8][W/8] into the plan (a configured plan: the
  * target of content layer 0, shaped like that layer). */
@@ -720,6 +750,22 @@ int st_op_scaled_mse_loss(const float* x, const float* target, long long count, 
 /* ... grad[i] = upstream[0] * (2 d - L sgn d)[i] / S1, sgn 0 = 0: where every d is zero the gradient is zero, not NaN. */
 int st_op_scaled_mse_loss_backward(const float* x, const float* target, long long count, const float* totals,
                                    const float* upstream, float* grad, void* stream);
+/* The diagonal W2 head of st_plan_set_w2_diagonal on ONE dense fp32 tensor feat [C][npix], any C >= 1 (at most 65535) and
+ * npix >= 1, at weight 1 and without a mask, by the same kernels.  `scratch`: st_op_channel_stats_scratch_floats(C, npix)
+ * floats of the caller's, per call (16 bytes for the last-block ticket, which the call zeroes, and two partials per channel
+ * and split of the pixel range; the split count depends on npix alone).  Two calls on the same data give the same bits. */
+long long st_op_channel_stats_scratch_floats(int channels, long long npix);
+/* mean_out[c] = sum_p f_cp / npix, srm_diag_out[c] = sum_p f_cp^2 / npix: the diagonal of StyleLossW2.get_target's second raw
+ * moment, linear in the statistics like it. */
+int st_op_channel_moments(const float* feat, int channels, long long npix, float* scratch, float* mean_out, float* srm_diag_out,
+                          void* stream);
+/* loss_out[0] = (sum_c (mu_c - mean_t[c])^2 + sum_c (sigma_c - std_t[c])^2) / C with sigma_c = sqrt(max(q_c - mu_c^2, 0) + eps);
+ * coeffs_out [2 C] = [a | b], what the gradient needs (autograd: saved on the node) ... */
+int st_op_w2_diag_loss(const float* feat, int channels, long long npix, const float* mean_t, const float* std_t, float eps,
+                       float* scratch, float* coeffs_out, float* loss_out, void* stream);
+/* ... grad[c][p] = upstream[0] * (a_c f_cp + b_c); upstream: a DEVICE scalar. */
+int st_op_w2_diag_loss_backward(const float* feat, int channels, long long npix, const float* coeffs, const float* upstream,
+                                float* grad, void* stream);
 /* TVLoss (style_transfer.py:184-195) on a [3][H][W] image, H, W >= 1: the value alone (st_op_tv_loss writes the unit
  * gradient with it) ... */
 int st_op_tv_value(const float* image, int height, int width, float* scratch, float* loss_out, void* stream);

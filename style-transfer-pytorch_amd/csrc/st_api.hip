@@ -459,7 +459,12 @@ int st_plan_set_region_style_target(st_plan* p, int region, int index, const flo
                p->n_style);
     hipStream_t s = static_cast<hipStream_t>(stream);
     StyleHead& h = region_head_at(p, region, p->style_op[index]);
-    if (ensure_style_alloc(p, h, p->style_kind[index])) return 1;
+    if (ensure_style_alloc(p, h, alloc_kind_of(p, index))) return 1;
+    if (p->style_diag[index]) {         // a diagonal W2 entry (st_plan_set_w2_diagonal): (mu_t, sigma_t) from srm's diagonal; no root
+        if (launch_diag_target(mean, srm, h.n, style_eps_of(p, index), h.diag_mean_t, h.diag_std_t, s)) return 1;
+        h.target_set = true;
+        return 0;
+    }
     if (p->style_kind[index] == 1) {    // StyleLoss.get_target (:136-139): the second raw moment IS the Gram target; no root
         ST_HIP(hipMemcpyAsync(h.gram_t, srm, (size_t)h.n * h.n * sizeof(float), hipMemcpyDeviceToDevice, s));
         h.target_set = true;
@@ -587,7 +592,7 @@ int st_plan_moment_sums(st_plan* p, int layer, float* sums, void* stream) {
     for (int k = 0; k < p->n_style; ++k)
         if (kProgram[p->style_op[k]].feat_index == layer) idx = k;
     ST_REQUIRE(idx >= 0, "st_plan_moment_sums: features[%d] is not a style layer", layer);
-    if (ensure_style_alloc(p, p->head[p->style_op[idx]], p->style_kind[idx])) return 1;
+    if (ensure_style_alloc(p, p->head[p->style_op[idx]], p->style_kind[idx])) return 1;      // (strip plans: never diagonal)
     return moment_sums_of_tap(p, idx, sums, static_cast<hipStream_t>(stream));
 }
 

@@ -358,7 +358,14 @@ int ensure_moment_alloc(st_plan* p, StyleHead& h) {
 
 // ... and the rest by the style kind of the entry that lists the head: a Gram head (st_plan::style_kind[j] == 1) holds its
 // target and nothing else - no covariance, no root, no Newton-Schulz workspace; a W2 head all of those
+// (kind 2, internal - alloc_kind_of: a W2 entry flagged diagonal, st_plan_set_w2_diagonal, holds its 2 C targets, the stats
+// launch's partials, 2 C coefficients and a ticket; no Gram workspace, no C x C buffer)
 int ensure_style_alloc(st_plan* p, StyleHead& h, int kind) {
+    if (kind == 2) {
+        if (alloc_head_diag(h, PlanAlloc{p})) return 1;
+        ST_HIP(hipStreamSynchronize(nullptr));
+        return 0;
+    }
     if (ensure_moment_alloc(p, h)) return 1;
     const size_t nn = (size_t)h.n * h.n;
     if (kind == 1) return h.gram_t ? 0 : plan_alloc(p, &h.gram_t, nn);

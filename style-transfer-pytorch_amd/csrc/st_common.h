@@ -684,6 +684,32 @@ int launch_mask_columns_add(float* dst, const float* src, const float* sqrt_mask
 // out[j] = region_terms[0][j] + region_terms[1][j] + ... in region order (fp32), j < n_style; region_terms is [regions][n_style].
 // One region: out[j] takes region_terms[0][j] as it is.
 int launch_sum_region_terms(const float* region_terms, int regions, int n_style, float* out, hipStream_t s);
+// ---- diagonal-covariance W2 heads (st_plan_set_w2_diagonal, st_op_channel_moments / st_op_w2_diag_*; st_w2diag.hip) ----
+// The pixel range of every channel is cut into channel_stats_splits(npix) pieces - a function of the shape alone - and the
+// scratch of a launch is 4 floats (the ticket's 16 bytes) and behind them two partials per (channel, split).
+int channel_stats_splits(long long npix);
+long long channel_stats_scratch_floats(int channels, long long npix);
+// what the last block of the stats launch makes of a channel's sums: the moments (mean_out / srm_out, optional) and, with a
+// target (mean_t, std_t), the weighted term and the gradient's coefficients coeffs = [a (C) | b (C)] (include/st_amd.h)
+struct ChannelStatsFinish {
+    const float* mean_t = nullptr;
+    const float* std_t = nullptr;
+    float eps = 0.f, weight = 1.f;
+    double norm = 1.0;                  // M: the pixel count, or a mask level's sum
+    float* coeffs = nullptr;
+    float* loss_out = nullptr;
+    float* mean_out = nullptr;
+    float* srm_out = nullptr;
+};
+// scratch: channel_stats_scratch_floats floats whose first word is zero (the ticket; the launch leaves it zero); sqrt_mask
+// (optional): [npix], the square root of the pixel weights
+int launch_channel_stats(const float* feat, const float* sqrt_mask, int channels, long long npix, float* scratch,
+                         const ChannelStatsFinish& fin, hipStream_t s);
+// grad [C][npix] = (or, accumulate != 0: +=) (a_c feat + b_c) m_p; upstream (optional): a device scalar on a and b
+int launch_channel_affine_grad(const float* feat, const float* sqrt_mask, const float* coeffs, const float* upstream, int channels,
+                               long long npix, float* grad, int accumulate, hipStream_t s);
+// a flagged head's target from the moments a W2 target is given: mean_t = mean, std_t = sqrt(max(srm_cc - mean_c^2, 0) + eps)
+int launch_diag_target(const float* mean, const float* srm, int n, float eps, float* mean_t, float* std_t, hipStream_t s);
 // ---- Laplacian loss on pooled images (st_plan_set_laplacian, st_op_laplacian_*; st_laplacian.hip) ----
 constexpr int kMaxLapPools = 4;
 constexpr int kLapBlocks = 1024;                  // workgroups of the residual pass at most: its partials

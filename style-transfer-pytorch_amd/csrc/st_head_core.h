@@ -29,7 +29,36 @@ struct StyleHead {
     GramWorkspace gram{};
     bool allocated = false;            // plans: alloc_head_moments has run ...
     bool w2_allocated = false;         // ... and alloc_head_w2, with the targets' buffers
+    // a W2 entry whose covariances are diagonal (st_plan_set_w2_diagonal): all it reads - the target (mu_t, sigma_t), the stats
+    // launch's scratch (ticket, partials) and the gradient's coefficients [a | b]; none of the buffers above
+    float *diag_mean_t = nullptr, *diag_std_t = nullptr, *diag_scratch = nullptr, *diag_coeffs = nullptr;
 };
+
+// what a diagonal head needs (alloc_head_diag); the ticket in front of its scratch is zeroed on the null stream, which the caller
+// synchronises
+template <class Alloc>
+int alloc_head_diag(StyleHead& h, Alloc&& alloc) {
+    if (alloc(&h.diag_mean_t, (size_t)h.n) || alloc(&h.diag_std_t, (size_t)h.n) || alloc(&h.diag_coeffs, 2 * (size_t)h.n)) return 1;
+    if (h.diag_scratch) return 0;
+    if (alloc(&h.diag_scratch, (size_t)channel_stats_scratch_floats(h.n, h.npix_local))) return 1;
+    ST_HIP(hipMemset(h.diag_scratch, 0, 4 * sizeof(float)));
+    return 0;
+}
+// The diagonal head on feat [n][npix]: the stats launch with the term and the coefficients, then dF written to (accumulate: added
+// onto) grad.  mask_sum > 0 with sqrt_mask: the weighted moments and their normaliser.
+inline int diag_head_run(const StyleHead& h, const float* feat, float weight, float eps, const float* sqrt_mask, float mask_sum,
+                         float* loss_out, float* grad, int accumulate, hipStream_t s) {
+    ChannelStatsFinish fin;
+    fin.mean_t = h.diag_mean_t;
+    fin.std_t = h.diag_std_t;
+    fin.eps = eps;
+    fin.weight = weight;
+    fin.norm = sqrt_mask ? (double)mask_sum : (double)h.npix;
+    fin.coeffs = h.diag_coeffs;
+    fin.loss_out = loss_out;
+    if (launch_channel_stats(feat, sqrt_mask, h.n, h.npix_local, h.diag_scratch, fin, s)) return 1;
+    return launch_channel_affine_grad(feat, sqrt_mask, h.diag_coeffs, nullptr, h.n, h.npix_local, grad, accumulate, s);
+}
 
 // The moments of a tap: max |feat| (optional), the Gram partials, finalize
 struct HeadMoments {

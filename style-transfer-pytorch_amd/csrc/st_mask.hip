@@ -417,7 +417,9 @@ int st_plan_set_style_regions(st_plan* p, int n_regions, const float* const* mas
     for (int r = 0; r < n_regions; ++r)
         for (int k = 0; k < kMaskLevels; ++k)
             if (!p->region_sqrt[r][k] && plan_alloc(p, &p->region_sqrt[r][k], (size_t)p->mask_h[k] * p->mask_w[k])) return 1;
-    if (ensure_region_heads(p, n_regions, p->style_op, p->n_style, p->style_kind)) return 1;
+    int alloc_kinds[16];
+    for (int j = 0; j < 16; ++j) alloc_kinds[j] = j < p->n_style ? alloc_kind_of(p, j) : 0;
+    if (ensure_region_heads(p, n_regions, p->style_op, p->n_style, alloc_kinds)) return 1;
     assign_head_bounds(p);
     // one pyramid call per region (the partials are reused in stream order), 8 results each, ONE read-back
     double* results = p->mask_stats + kPyramidPartials;

@@ -53,6 +53,11 @@
 // A Laplacian loss (st_plan_set_laplacian, st_laplacian.hip) runs it as well: a pure image-space term like TV, launched right
 // behind it - each pool size's term is added onto the TV term's slot (the image-space slot: the last entry of the terms) and
 // its gradient onto the TV gradient, which run_tap_backward then adds the trunk's onto.
+//
+// A W2 entry flagged diagonal (st_plan_set_w2_diagonal, st_w2diag.hip) runs it too, on the reference's lists as well: that entry's
+// head is two launches through the same site - the channel statistics with the term and the gradient's coefficients, then
+// dF m_p written to the seed buffer (a region r >= 1: added onto it) - with no Gram pass, chain, 1x1 step, bound word,
+// mask-column launch or region scratch.  Every other entry runs by its kind as above.
 #include <algorithm>
 #include <cmath>
 
@@ -99,6 +104,11 @@ static bool default_kinds(const st_plan* p) {
     for (int j = 0; j < p->n_style; ++j) ok = ok && p->style_kind[j] == 0;
     return ok;
 }
+static bool any_diagonal(const st_plan* p) {
+    bool any = false;
+    for (int j = 0; j < p->n_style; ++j) any = any || p->style_diag[j] != 0;
+    return any;
+}
 static bool default_eps(const st_plan* p) {
     bool ok = true;
     for (int i = 0; i < p->n_content; ++i) ok = ok && p->content_eps[i] < 0.f;
@@ -109,7 +119,7 @@ static bool default_eps(const st_plan* p) {
 bool general_taps(const st_plan* p) {
     static Option force("ST_GENERAL_TAPS", 0);
     return !p->strip && (!p->reference_taps || !default_kinds(p) || !default_eps(p) || p->style_mask || p->n_regions > 0 ||
-                         p->content_mask || p->tv_mask || p->n_lap > 0 || force.get() != 0);
+                         p->content_mask || p->tv_mask || p->n_lap > 0 || any_diagonal(p) || force.get() != 0);
 }
 
 float style_eps_of(const st_plan* p, int j) {
@@ -119,6 +129,8 @@ float style_eps_of(const st_plan* p, int j) {
 float content_eps_of(const st_plan* p, int i) {
     return p->content_kind[i] == 0 ? -1.f : p->content_eps[i] >= 0.f ? p->content_eps[i] : kScaledMseEps;
 }
+
+int alloc_kind_of(const st_plan* p, int j) { return p->style_diag[j] ? 2 : p->style_kind[j]; }
 
 int closure_top_op(const st_plan* p) {
     if (!general_taps(p)) return kNumOps - 1;
@@ -182,6 +194,13 @@ int gram_head(st_plan* p, const HeadSite& at, int term, hipStream_t s) {
     return style_head_gradient(p, at, s);
 }
 
+// A W2 entry flagged diagonal (st_plan_set_w2_diagonal, st_w2diag.hip): the stats launch - moments, term, coefficients - and the
+// gradient launch, which writes dF m_p to the seed (accumulate: adds it, a region r >= 1).  The site's mask and normaliser are
+// read by both, so no launch_mask_columns follows; no bound word is touched.
+int diag_head(st_plan* p, const HeadSite& at, float* seed, int accumulate, hipStream_t s) {
+    return diag_head_run(*at.h, at.tap->y, at.weight, at.eps, at.sqrt_mask, at.mask_sum, at.loss, seed, accumulate, s);
+}
+
 // Style regions in force: the heads of every listed entry, in `order`, one per region in region order.  dF_r's pixel columns
 // times m_r: region 0 in place on the seed it wrote (the masked plan's launches), region r >= 1 from the scratch buffer ONTO the
 // seed.  Then each entry's term from its regions' terms.
@@ -194,6 +213,10 @@ int region_heads(st_plan* p, const int* order, bool* styled, hipStream_t s) {
         float* seed = p->tap_seed[p->style_op[j]];
         for (int r = 0; r < regions; ++r) {
             const HeadSite at = region_head_site(p, j, r);
+            if (p->style_diag[j]) {            // region 0 writes the seed, region r >= 1 adds onto it: no scratch buffer
+                if (diag_head(p, at, seed, r > 0, s)) return 1;
+                continue;
+            }
             if (p->style_kind[j] == 1 ? gram_head(p, at, nc + j, s) : style_head(p, at, s)) return 1;
             if (r == 0 ? launch_mask_columns(seed, at.sqrt_mask, at.h->n, at.h->npix, s)
                        : launch_mask_columns_add(seed, at.grad, at.sqrt_mask, at.h->n, at.h->npix, s))
@@ -220,7 +243,8 @@ int ensure_tap_buffers(st_plan* p) {
         if (seed(p->style_op[i])) return 1;
     // style regions: one buffer of the largest listed style tap for the 1x1 steps of regions r >= 1
     size_t largest = 0;
-    for (int i = 0; p->n_regions > 1 && i < p->n_style; ++i) largest = std::max(largest, node_at(p, p->style_op[i]).count());
+    for (int i = 0; p->n_regions > 1 && i < p->n_style; ++i)
+        if (!p->style_diag[i]) largest = std::max(largest, node_at(p, p->style_op[i]).count());      // (a diagonal entry needs none)
     if (largest > p->region_scratch_floats) {
         p->region_scratch = nullptr;         // (the smaller one stays the plan's until it is destroyed)
         if (plan_alloc(p, &p->region_scratch, largest)) { p->region_scratch_floats = 0; return 1; }
@@ -255,6 +279,11 @@ int general_loss_and_grad(st_plan* p, const float* image, float* grad_out, float
     } else {
         for (int k = 0; k < ns; ++k) {
             const HeadSite at = general_head_site(p, order[k]);
+            if (p->style_diag[order[k]]) {
+                if (diag_head(p, at, at.grad, 0, s)) return 1;
+                styled[p->style_op[order[k]]] = true;
+                continue;
+            }
             if (p->style_kind[order[k]] == 1 ? gram_head(p, at, nc + order[k], s) : style_head(p, at, s)) return 1;
             // a style mask: dF's pixel columns times m, on the seed as the head's 1x1 step left it and BEFORE a content term of
             // the same layer adds onto it
@@ -381,6 +410,7 @@ int st_plan_set_taps(st_plan* p, int n_content, const int* content_layers, int n
         p->content_kind[i] = ckind;
         p->style_kind[i] = skind;
         p->content_eps[i] = p->style_eps[i] = -1.f;
+        p->style_diag[i] = 0;
         if (keep_weights) continue;
         p->content_weight[i] = i < n_content ? 0.015f / (float)n_content : 0.f;
         p->style_weight[i] = i >= n_style ? 0.f : ref ? kStyleWeight[i] : 1.f / (float)n_style;
@@ -403,6 +433,7 @@ int apply_loss_kinds(st_plan* p, const int* ck, const int* sk) {
         p->content_kind[i] = ck[i];
         p->style_kind[i] = sk[i];
         p->content_eps[i] = p->style_eps[i] = -1.f;      // an eps belongs to a module of one kind: set it after the kinds
+        p->style_diag[i] = 0;                            // ... and so does the diagonal flag of a W2 entry
     }
     // a target is kept in the form its kind reads (a root, or a Gram matrix): as after st_plan_set_taps, every target set
     // before is gone, every bound word is dealt again and nothing built on the former terms survives.  The lists and all
@@ -497,6 +528,34 @@ int st_plan_set_loss_eps(st_plan* p, const float* content_eps, const float* styl
     std::copy(se, se + 16, p->style_eps);
     // a W2 target is kept as the root of cov_t + eps I: every target set before is gone
     drop_targets(p);
+    return 0;
+}
+
+int st_plan_set_w2_diagonal(st_plan* p, const int* flags) {
+    ST_REQUIRE(p, "st_plan_set_w2_diagonal: null plan");
+    int fl[16] = {};
+    bool any = false;
+    for (int j = 0; flags && j < p->n_style; ++j) {
+        ST_REQUIRE(flags[j] == 0 || flags[j] == 1, "st_plan_set_w2_diagonal: flag %d of style layer %d: 0 or 1", flags[j], j);
+        ST_REQUIRE(flags[j] == 0 || p->style_kind[j] == 0,
+                   "st_plan_set_w2_diagonal: style layer %d is of kind gram (StyleLoss): only a w2 layer's covariances can be diagonal", j);
+        fl[j] = flags[j];
+        any = any || fl[j] != 0;
+    }
+    ST_REQUIRE(!p->strip || !any, "st_plan_set_w2_diagonal: strip plans run full W2 heads only");
+    // style regions in force: what their heads need under the new flags, now - a failed allocation leaves the plan as it was
+    int kinds[16] = {};
+    for (int j = 0; j < p->n_style; ++j) kinds[j] = fl[j] ? 2 : p->style_kind[j];
+    if (ensure_region_heads(p, p->n_regions, p->style_op, p->n_style, kinds)) return 1;
+    std::copy(fl, fl + 16, p->style_diag);
+    // a target is kept in the form its head reads - (mu_t, sigma_t), or a root: every target set before is gone
+    drop_targets(p);
+    return 0;
+}
+
+int st_plan_w2_diagonal(const st_plan* p, int* flags) {
+    ST_REQUIRE(p && flags, "st_plan_w2_diagonal: null argument");
+    for (int j = 0; j < p->n_style; ++j) flags[j] = p->style_diag[j];
     return 0;
 }
 

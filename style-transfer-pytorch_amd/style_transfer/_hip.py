@@ -87,6 +87,8 @@ def _declare(lib):
         'st_plan_layer_loss_kinds': (i32, [vp, ip, ip]),
         'st_plan_set_loss_eps': (i32, [vp, ctypes.POINTER(f32), ctypes.POINTER(f32)]),
         'st_plan_loss_eps': (i32, [vp, ctypes.POINTER(f32), ctypes.POINTER(f32)]),
+        'st_plan_set_w2_diagonal': (i32, [vp, ctypes.POINTER(i32)]),
+        'st_plan_w2_diagonal': (i32, [vp, ctypes.POINTER(i32)]),
         'st_plan_set_content_target_at': (i32, [vp, i32, vp, vp]),
         'st_plan_term_losses': (i32, [vp, pp, ip]),
         'st_plan_loss_and_grad': (i32, [vp, vp, vp, vp, vp]),
@@ -149,6 +151,10 @@ def _declare(lib):
         'st_op_mse_loss_backward': (i32, [vp, vp, i64, vp, vp, vp]),
         'st_op_scaled_mse_loss': (i32, [vp, vp, i64, f32, vp, vp, vp, vp]),
         'st_op_scaled_mse_loss_backward': (i32, [vp, vp, i64, vp, vp, vp, vp]),
+        'st_op_channel_stats_scratch_floats': (i64, [i32, i64]),
+        'st_op_channel_moments': (i32, [vp, i32, i64, vp, vp, vp, vp]),
+        'st_op_w2_diag_loss': (i32, [vp, i32, i64, vp, vp, f32, vp, vp, vp, vp]),
+        'st_op_w2_diag_loss_backward': (i32, [vp, i32, i64, vp, vp, vp, vp]),
         'st_op_tv_value': (i32, [vp, i32, i32, vp, vp, vp]),
         'st_op_tv_loss_backward': (i32, [vp, i32, i32, vp, vp, vp]),
         'st_op_laplacian_scratch_floats': (i64, [i32, i32, i32, i32]),
@@ -383,6 +389,33 @@ class Plan:
             arrays.append((ctypes.c_float * max(len(given), 1))(*[-1.0 if v is None else float(v) for v in given]))
         with torch.cuda.device(self.device):
             _check(self.lib.st_plan_set_loss_eps(self.handle, *arrays))
+
+    def set_w2_diagonal(self, flags=None):
+        """Restrict both covariances of a 'w2' style layer to their diagonals (st_plan_set_w2_diagonal): None or False (no
+        layer), True (every layer of the list - all must be 'w2') or a sequence with one bool per style layer.  A flagged
+        layer's term is ``sum (mu - mu_t)^2 + sum (sigma - sigma_t)^2`` over the channels, divided by their number: two
+        memory-bound launches, no C x C work.  Any set flag runs the general closure; drops every target.  Either kinds
+        setter and ``set_taps`` clear the flags: kinds, eps, then this, then the weights and targets."""
+        n = len(self.style_layers)
+        if flags is None or isinstance(flags, (bool, int)):
+            flags = [bool(flags)] * n
+        flags = list(flags)
+        if len(flags) != n:
+            raise ValueError(f'{len(flags)} diagonal flags for {n} style layers: one per layer')
+        for v in flags:
+            if v not in (0, 1, False, True):
+                raise ValueError(f'diagonal flag {v!r}: must be a bool')
+        fa = (ctypes.c_int * max(n, 1))(*[int(v) for v in flags])
+        with torch.cuda.device(self.device):
+            _check(self.lib.st_plan_set_w2_diagonal(self.handle, fa))
+
+    @property
+    def w2_diagonal(self):
+        """The diagonal flag of each style layer, a tuple of bools (st_plan_w2_diagonal)."""
+        n = len(self.style_layers)
+        fa = (ctypes.c_int * max(n, 1))()
+        _check(self.lib.st_plan_w2_diagonal(self.handle, fa))
+        return tuple(bool(v) for v in fa[:n])
 
     def _layer_values(self, entry, ctype):
         ca, sa = (ctype * max(len(self.content_layers), 1))(), (ctype * max(len(self.style_layers), 1))()
@@ -1201,6 +1234,45 @@ def op_scaled_mse_loss_backward(x, target, totals, upstream):
     with torch.cuda.device(x.device):
         _check(lib.st_op_scaled_mse_loss_backward(_ptr(x), _ptr(target), x.numel(), _ptr(totals), _ptr(upstream), _ptr(grad),
                                                   _stream()))
+    return grad
+
+
+def _channel_stats_scratch(x):
+    c, npix = int(x.shape[-3]), int(x.shape[-2]) * int(x.shape[-1])
+    floats = int(load_library().st_op_channel_stats_scratch_floats(c, npix))
+    return c, npix, torch.empty(max(floats, 1), device=x.device, dtype=torch.float32)
+
+
+def op_channel_moments(x):
+    """(mean [C], the diagonal of the second raw moment [C]) over the pixels of a [..., C, H, W] tensor (one image) -
+    st_op_channel_moments."""
+    lib = load_library()
+    c, npix, scratch = _channel_stats_scratch(x)
+    mean = torch.empty(c, device=x.device, dtype=torch.float32)
+    srm = torch.empty(c, device=x.device, dtype=torch.float32)
+    with torch.cuda.device(x.device):
+        _check(lib.st_op_channel_moments(_ptr(x), c, npix, _ptr(scratch), _ptr(mean), _ptr(srm), _stream()))
+    return mean, srm
+
+
+def op_w2_diag_loss(x, mean_t, std_t, eps):
+    """(the diagonal W2 loss [0-dim], the gradient's coefficients [2 C]) - st_op_w2_diag_loss."""
+    lib = load_library()
+    c, npix, scratch = _channel_stats_scratch(x)
+    loss = torch.empty((), device=x.device, dtype=torch.float32)
+    coeffs = torch.empty(2 * c, device=x.device, dtype=torch.float32)
+    with torch.cuda.device(x.device):
+        _check(lib.st_op_w2_diag_loss(_ptr(x), c, npix, _ptr(mean_t), _ptr(std_t), float(eps), _ptr(scratch), _ptr(coeffs),
+                                      _ptr(loss), _stream()))
+    return loss, coeffs
+
+
+def op_w2_diag_loss_backward(x, coeffs, upstream):
+    lib = load_library()
+    c, npix = int(x.shape[-3]), int(x.shape[-2]) * int(x.shape[-1])
+    grad = torch.empty(x.shape, device=x.device, dtype=torch.float32)
+    with torch.cuda.device(x.device):
+        _check(lib.st_op_w2_diag_loss_backward(_ptr(x), c, npix, _ptr(coeffs), _ptr(upstream), _ptr(grad), _stream()))
     return grad
 
 

@@ -304,6 +304,10 @@ def build_parser():
     p.add_argument('--style-eps', type=_loss_eps, default=None, metavar='EPS[,...]',
                    help="the eps of the style term's module (default: 1e-4 for 'w2', 1e-8 for 'gram'); a comma-separated "
                         "list gives one per style layer, an empty item the default, e.g. '1e-2,,,,1e-3'")
+    p.add_argument('--style-diagonal', type=_diagonal_flags, default=False, metavar='{0,1}[,...]',
+                   help="restrict both covariances of the 'w2' style layers to their diagonals (the mean / standard-deviation "
+                        "style loss: two memory-bound launches per layer, no C x C work): 1 for every 'w2' layer, or a "
+                        "comma-separated list with one flag per style layer, e.g. '0,0,0,1,1' (default 0)")
     p.add_argument('--style-mask', type=str, default=None, metavar='PATH',
                    help='an image (read as greyscale, white = 1) saying which pixels of the output take the style; it is '
                         'resized to every scale')
@@ -342,6 +346,16 @@ def _loss_names(choices):
                 raise argparse.ArgumentTypeError(f"invalid choice: {name!r} (choose from {', '.join(map(repr, choices))})")
         return names[0] if len(names) == 1 else names
     return parse
+
+
+def _diagonal_flags(text):
+    """argparse type of --style-diagonal: one flag stays the bool, a comma-separated list becomes the list of bools."""
+    items = text.split(',')
+    for item in items:
+        if item not in ('0', '1'):
+            raise argparse.ArgumentTypeError(f"invalid flag: {item!r} (0 or 1, or a comma-separated list of them)")
+    flags = [item == '1' for item in items]
+    return flags[0] if len(flags) == 1 else flags
 
 
 def apply_weight_maps(st, args):
@@ -395,9 +409,10 @@ def apply_style_masks(st, args):
 
 
 def apply_loss_kinds(st, args):
-    """--content-loss / --style-loss / --content-eps / --style-eps onto the StyleTransfer attributes that stylize() reads."""
+    """--content-loss / --style-loss / --content-eps / --style-eps / --style-diagonal onto the StyleTransfer attributes that stylize() reads."""
     st.content_loss, st.style_loss = args.content_loss, args.style_loss
     st.content_eps, st.style_eps = args.content_eps, args.style_eps
+    st.style_diagonal = args.style_diagonal
     return st
 
 

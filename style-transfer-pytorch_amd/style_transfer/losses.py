@@ -8,6 +8,9 @@ libst_amd.so.  User code written against the reference can however import these 
 provided here with the reference's constructor arguments, buffers, static helpers and arithmetic.  ``LaplacianLoss`` is this
 project's own (include/st_amd.h fixes its semantics): the module form of ``st_plan_set_laplacian``'s term, dispatched like the
 others - one dense fp32 HIP image, any channel count, runs st_op_laplacian_value / st_op_laplacian_backward per pool size.
+``StyleLossW2Diag`` is this project's own too: ``StyleLossW2`` with both covariances restricted to their diagonals, the module
+form of ``st_plan_set_w2_diagonal``'s term - one dense fp32 HIP tensor, any channel count, runs st_op_w2_diag_loss /
+st_op_w2_diag_loss_backward.
 
 Native dispatch.  On an ELIGIBLE tensor (``eligible`` below: one dense fp32 tensor on a HIP device, batch 1 or absent, 64 /
 128 / 256 / 512 channels for the style modules, the module's buffers beside it in fp32) the five loss modules run in the
@@ -59,7 +62,7 @@ class native:
         native.enabled, native.precision = self._former
 
 
-# calls that went to the library, by kind ('w2', 'gram', 'mse', 'scaled_mse', 'tv', 'laplacian', 'moments'): the native indicator of the
+# calls that went to the library, by kind ('w2', 'gram', 'mse', 'scaled_mse', 'tv', 'laplacian', 'w2_diag', 'moments'): the native indicator of the
 # modules that hold no head
 native_calls = {}
 _heads = weakref.WeakKeyDictionary()       # module -> its _hip.Head (no module attribute: deepcopy / pickle / state_dict never see it)
@@ -93,6 +96,11 @@ def eligible(input, kind, buffers=()):
             return False
         c = input.shape[-3]
         sizes = {'w2': (c, c * c, c * c), 'gram': (c * c,), 'moments': ()}[kind]
+    elif kind == 'w2_diag':
+        # (any channel count the launch's grid takes; buffers: none, or the module's (mean, std))
+        if not (_one_dense_fp32(input, 3) and input.ndim in (3, 4) and input.shape[-3] <= 65535):
+            return False
+        sizes = (input.shape[-3],) * len(buffers)
     elif kind == 'tv':
         if not (_one_dense_fp32(input, 3) and input.ndim in (3, 4) and input.shape[-3] == 3 and input.numel() < 1 << 31):
             return False
@@ -261,6 +269,30 @@ class _ScaledMSELoss(torch.autograd.Function):
             return _torch_vjp(ctx.torch_forward, input, grad_output), None, None, None
         grad = _hip.op_scaled_mse_loss_backward(_dense(input), target, totals, grad_output.contiguous())
         return grad.view(input.shape), None, None, None
+
+
+class _W2DiagLoss(torch.autograd.Function):
+    """StyleLossW2Diag.forward: st_op_w2_diag_loss; the 2 C coefficients of the gradient stay on the node for
+    st_op_w2_diag_loss_backward."""
+
+    @staticmethod
+    def forward(ctx, input, module, mean, std, eps):
+        from . import _hip
+        loss, coeffs = _hip.op_w2_diag_loss(_dense(input), mean, std, eps)
+        _count('w2_diag')
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(input, coeffs)
+            ctx.torch_forward = module._forward_torch
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        from . import _hip
+        input, coeffs = ctx.saved_tensors
+        if torch.is_grad_enabled():
+            return _torch_vjp(ctx.torch_forward, input, grad_output), None, None, None, None
+        grad = _hip.op_w2_diag_loss_backward(_dense(input), coeffs, grad_output.contiguous())
+        return grad.view(input.shape), None, None, None, None
 
 
 class _TVLoss(torch.autograd.Function):
@@ -446,6 +478,64 @@ class StyleLossW2(nn.Module):
         cross = self.sqrtm(self.cov_sqrt @ cov @ self.cov_sqrt)
         cov_term = torch.diagonal(self.cov + cov - 2 * cross, dim1=-2, dim2=-1).mean()
         return mean_term + cov_term
+
+
+class StyleLossW2Diag(nn.Module):
+    """``StyleLossW2`` with both covariances restricted to their diagonals: for two Gaussians with diagonal covariances W2^2 is
+    ``sum_c (mu - mu_t)^2 + sum_c (sigma - sigma_t)^2`` - the mean / standard-deviation (batch-norm statistics) loss of Li et
+    al., "Demystifying Neural Style Transfer", the statistic AdaIN matches - here divided by the channel count as ``StyleLossW2``
+    takes means.  Not in the reference; include/st_amd.h (st_plan_set_w2_diagonal) fixes the semantics:
+    ``sigma = sqrt(max(q - mu^2, 0) + eps)`` with ``q`` the channel's second raw moment, the variance term as
+    ``(sigma - sigma_t)^2`` so that the target's own features give exactly 0 with an exactly zero gradient, and a zero gradient
+    through ``sigma`` where it is 0.  ``target`` = (mean [..., C], srm) with ``srm`` of shape [..., C] or [..., C, C] (its
+    diagonal is taken), so a ``StyleLossW2`` target serves.  The torch path serves any device, dtype and batch; one dense fp32
+    HIP tensor of any channel count runs in the library (st_w2diag.hip: two memory-bound launches, no C x C work)."""
+
+    def __init__(self, target, eps=1e-4):
+        super().__init__()
+        mean, srm = target
+        if srm.ndim == mean.ndim + 1:
+            srm = torch.diagonal(srm, dim1=-2, dim2=-1)
+        if srm.shape != mean.shape:
+            raise ValueError(f'target of shapes {tuple(mean.shape)} and {tuple(srm.shape)}: (mean [..., C], srm [..., C] or [..., C, C])')
+        eps = mean.new_tensor(eps)
+        self.register_buffer('mean', mean)
+        self.register_buffer('std', self._std(mean, srm, eps))
+        self.register_buffer('eps', eps)
+
+    @staticmethod
+    def get_target(target):
+        """(mean, the diagonal of the second raw moment) over the spatial positions - like ``StyleLossW2``'s target linear
+        in the features' distribution, so targets of several style images can be blended."""
+        if native.enabled and eligible(target, 'w2_diag') and not _wants_grad(target):
+            from . import _hip
+            _count('moments')
+            mean, srm = _hip.op_channel_moments(_dense(target))
+            shape = tuple(target.shape[:-2])
+            return mean.view(shape), srm.view(shape)
+        return StyleLossW2Diag._get_target_torch(target)
+
+    @staticmethod
+    def _get_target_torch(target):
+        return target.mean([-2, -1]), (target * target).mean([-2, -1])
+
+    @staticmethod
+    def _std(mean, srm, eps):
+        var = srm - mean * mean
+        var = var + (var.clamp(min=0) - var).detach()       # max(var, 0) in value; the gradient passes as the header states it
+        v = var + eps
+        positive = v > 0
+        return torch.where(positive, v, torch.ones_like(v)).sqrt() * positive.to(v.dtype)
+
+    def forward(self, input):
+        if native.enabled and eligible(input, 'w2_diag', (self.mean, self.std)) and _buffer_ok(self.eps, input, 1):
+            return _W2DiagLoss.apply(input, self, self.mean, self.std, _eps_of(self))
+        return self._forward_torch(input)
+
+    def _forward_torch(self, input):
+        mean, srm = self._get_target_torch(input)
+        std = self._std(mean, srm, self.eps)
+        return torch.mean((mean - self.mean) ** 2) + torch.mean((std - self.std) ** 2)
 
 
 class TVLoss(nn.Module):

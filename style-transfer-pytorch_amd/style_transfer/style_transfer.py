@@ -291,6 +291,34 @@ def _resolve_layer_losses(content_loss, style_loss, content_eps, style_eps, n_co
     return kinds[0], kinds[1], epses[0], epses[1]
 
 
+def _resolve_style_diagonal(style_diagonal, style_loss, world=1):
+    """``StyleTransfer.style_diagonal`` as the fused closure takes it: one bool per entry of ``style_loss`` (the resolved
+    kinds, one per style layer).  A bool means every 'w2' layer; a sequence holds one bool per entry of style_layers.  Raises
+    ``ValueError`` naming the attribute for a wrong length, a value that is no bool, a true flag on a 'gram' layer, and for
+    any true flag on several ranks, before any device work."""
+    n = len(style_loss)
+    if isinstance(style_diagonal, (bool, np.bool_)):
+        flags = [bool(style_diagonal) and name == _hip.STYLE_LOSSES[0] for name in style_loss]
+    else:
+        if isinstance(style_diagonal, str) or not isinstance(style_diagonal, (list, tuple)):
+            raise ValueError(f'style_diagonal {style_diagonal!r}: give a bool, or a sequence with one bool per entry of style_layers')
+        flags = list(style_diagonal)
+        if len(flags) != n:
+            raise ValueError(f'style_diagonal {style_diagonal!r}: {len(flags)} flags for {n} layers; give one bool, or exactly '
+                             'one per entry of style_layers')
+        for i, (flag, name) in enumerate(zip(flags, style_loss)):
+            if not isinstance(flag, (bool, np.bool_)) and flag not in (0, 1):
+                raise ValueError(f'style_diagonal {style_diagonal!r}: {flag!r} is not a bool')
+            if flag and name != _hip.STYLE_LOSSES[0]:
+                raise ValueError(f"style_diagonal {style_diagonal!r}: layer {i} has the loss {name!r} (StyleLoss on Gram "
+                                 "matrices); only a 'w2' layer's covariances can be restricted to their diagonals")
+        flags = [bool(flag) for flag in flags]
+    if world > 1 and any(flags):
+        raise ValueError(f'style_diagonal {style_diagonal!r} on {world} ranks: row strips run full W2 heads only; diagonal '
+                         'heads are out of scope for strips - run them on one device')
+    return flags
+
+
 def _mask_image(mask, attr):
     """One mask as (PIL image, divisor): a PIL image becomes mode 'L' (divisor 255), a 2-D numpy / torch array with values
     in [0, 1] a mode 'F' image (divisor 1).  Raises ``ValueError`` naming ``attr``."""
@@ -814,6 +842,10 @@ class StyleTransfer:
     # number for every layer of the list, or a sequence with a number or None per layer
     content_eps = None
     style_eps = None
+    # 'w2' layers with both covariances restricted to their diagonals (_hip.Plan.set_w2_diagonal, losses.StyleLossW2Diag; the
+    # reference has none): the mean / standard-deviation style loss, two memory-bound launches per layer and no C x C work.
+    # False, True (every 'w2' layer) or a sequence with one bool per entry of style_layers.  One device only.
+    style_diagonal = False
     # Spatial masks for the style statistics (read by stylize() too; the reference has none).  style_mask: which pixels of the
     # OUTPUT take the style - a PIL image (read as 'L' / 255) or a 2-D numpy / torch array in [0, 1], resized bilinearly to
     # every scale; the style heads then take mask-weighted moments of the iterate's taps (_hip.Plan.set_style_mask).
@@ -1102,6 +1134,7 @@ class StyleTransfer:
         content_loss, style_loss, content_eps, style_eps = _resolve_layer_losses(
             self.content_loss, self.style_loss, self.content_eps, self.style_eps, len(content_layers), len(style_layers),
             world=max(len(self.devices), _dist_info()[1]))
+        style_diagonal = _resolve_style_diagonal(self.style_diagonal, style_loss, world=max(len(self.devices), _dist_info()[1]))
         style_mask, image_masks = _resolve_style_masks(self.style_mask, self.style_image_masks, len(style_images),
                                                        world=max(len(self.devices), _dist_info()[1]))
         regions = _resolve_style_regions(self.style_regions, self.style_image_regions, self.style_region_weights,
@@ -1244,6 +1277,8 @@ class StyleTransfer:
                     plan.set_layer_loss_kinds(content_loss, style_loss)
                 if any(value is not None for value in content_eps + style_eps):
                     plan.set_loss_eps(content_eps, style_eps)
+                if any(style_diagonal):
+                    plan.set_w2_diagonal(style_diagonal)
                 self._build_targets(plan, content.to(device), style_images, style_weights, scale, style_scale_fac,
                                     style_size, style_mask, image_masks, regions)
                 # the content and TV maps at this scale's size, on the iterate's plan only and after the targets (which they
