@@ -349,7 +349,7 @@ int st_plan_loss_kinds(const st_plan* plan, int* content_kind, int* style_kind);
  * the kind of a list whose entries agree and returns a mixed list to kind 0.  st_plan_layer_loss_kinds writes n_content /
  * n_style codes (either pointer may be null).
  * Order of configuration: layers (st_plan_set_taps), kinds, eps (st_plan_set_loss_eps), diagonal (st_plan_set_w2_diagonal),
- * weights, then the targets.
+ * marginal (st_plan_set_w2_marginal), weights, then the targets.
  */
 int st_plan_set_layer_loss_kinds(st_plan* plan, const int* content_kinds, const int* style_kinds);
 int st_plan_layer_loss_kinds(const st_plan* plan, int* content_kinds, int* style_kinds);
@@ -399,6 +399,48 @@ int st_plan_loss_eps(const st_plan* plan, float* content_eps, float* style_eps);
  */
 int st_plan_set_w2_diagonal(st_plan* plan, const int* flags);
 int st_plan_w2_diagonal(const st_plan* plan, int* flags);
+
+/*
+ * The exact per-channel Wasserstein (sorted) option of a W2 style layer: flags[n_style], 0 or 1 in list order; a null pointer
+ * clears all.  Every other style statistic of a plan is a second moment of the tap; this one is the W2 distance between the
+ * exact one-dimensional marginals of the tap's channels and of the style's - Risser et al.'s histogram loss in its exact form,
+ * the sliced Wasserstein loss of Heitz et al. ("A Sliced Wasserstein Loss for Neural Texture Synthesis") taken along the channel
+ * axes.  The diagonal head above is the same distance between the marginals' Gaussian fits.  It is an OPTION of a w2 layer - the
+ * kind names and codes do not change - and the reference has no such module, so the semantics are fixed here.  For flagged
+ * entry j with tap F [C][N], N = h w, and target T [C][N], every row non-decreasing:
+ *   pi_c    the stable ascending order of row c: ties are broken by ascending pixel index and -0.0 compares equal to +0.0
+ *           (torch.sort(f + 0.0, stable=True))
+ *   term_j = w_j sum_c sum_k (f_c,pi_c(k) - T_c,k)^2 / (C N)
+ *   dF_c,pi_c(k) = w_j (2 / (C N)) (f_c,pi_c(k) - T_c,k)
+ * The permutation is a constant of the gradient: the a.e. derivative, which autograd gives for sort.  Inputs are finite; with a
+ * NaN the result is unspecified, but the launches end (no loop's trip count depends on a comparison of values).  There is no
+ * eps.  The term is exactly 0 with an exactly zero gradient when the tap is the target's source.
+ * Target: Q [C][n_q], the quantile function of a style tap - its rows sorted - resampled to the plan's N by
+ *   T_c,i = lerp(Q_c, u),  u = clamp((i + 1/2) n_q / N - 1/2, 0, n_q - 1) evaluated in double,
+ * linear between floor(u) and floor(u) + 1 in fp32 (midpoint convention: order statistic k sits at (k + 1/2) / n_q); n_q == N is
+ * a copy, bit for bit.  Several style images blend as their resampled quantile functions, weighted - in one dimension the
+ * Wasserstein barycentre, as blending (mean, srm) is for the moments.
+ * A flagged head (csrc/st_sort.hip) is a segmented stable sort of the tap's rows on 64-bit keys (value image | pixel index: one
+ * LDS bitonic launch over chunks of st_op_sort_chunk() keys and ceil(log2(N / chunk)) merge passes) and a residual pass that writes
+ * the gradient through the permutation (a content term of the same layer adds after it) and reduces the term by per-block fp32
+ * partials, a ticket and the last block's index-order sum in double.  Integer atomics only: two runs give the same bits.  It
+ * allocates the C N target, two buffers of C N keys, the partials and a ticket; no C x C buffer, no Newton-Schulz workspace.
+ * Any set flag runs the general closure (csrc/st_taps.hip), on the default lists too; flags that are all 0, or set and then
+ * cleared, leave, bit for bit, a plan on which this was never called.  Like st_plan_set_w2_diagonal the call drops every target
+ * set before and invalidates a captured graph; either kinds setter and st_plan_set_taps clear the flags.
+ * Fails for a flag on a gram entry, on an entry flagged diagonal (and st_plan_set_w2_diagonal refuses an entry flagged here), on
+ * an entry with a non-default eps (and st_plan_set_loss_eps refuses one for an entry flagged here), for a value other than 0 or
+ * 1, for any set flag on a strip plan, and while a style mask or style regions are set (their setters refuse while a flag is
+ * set): weighted quantiles are not implemented.  st_plan_term_losses and the 8-float array keep their shapes.
+ * Order of configuration: layers, kinds, eps, diagonal, marginal, weights, then the targets.
+ */
+int st_plan_set_w2_marginal(st_plan* plan, const int* flags);
+int st_plan_w2_marginal(const st_plan* plan, int* flags);
+/* The target of flagged style entry `index`: q [C][n_q], sorted rows (device memory), resampled to the plan's N as above.  Fails
+ * on an entry that is not flagged; st_plan_set_style_target fails on a flagged one. */
+int st_plan_set_style_quantiles(st_plan* plan, int index, const float* q, long long n_q, void* stream);
+/* Borrows the resampled target of flagged entry `index`: *target [C][N] floats of the plan's, valid until the plan is destroyed. */
+int st_plan_style_quantiles(st_plan* plan, int index, float** target, int* channels, long long* n);
 
 /* ContentLossMSE target (style_transfer.py:425-429): copies feat [512][H/8][W/8] into the plan (a configured plan: the
  * target of content layer 0, shaped like that layer). */
@@ -766,6 +808,24 @@ int st_op_w2_diag_loss(const float* feat, int channels, long long npix, const fl
 /* ... grad[c][p] = upstream[0] * (a_c f_cp + b_c); upstream: a DEVICE scalar. */
 int st_op_w2_diag_loss_backward(const float* feat, int channels, long long npix, const float* coeffs, const float* upstream,
                                 float* grad, void* stream);
+/* The marginal W2 head of st_plan_set_w2_marginal on ONE dense fp32 tensor feat [C][n], by the same kernels: C >= 1 rows of
+ * 1 <= n <= 2^32 - 1 elements; a shape that needs more than 2^31 - 1 workgroups in one launch is refused, never wrapped.
+ * st_op_sort_chunk(): the keys one workgroup sorts in LDS (a row of at most that many elements needs no merge pass).
+ * `scratch`: st_op_sort_scratch_bytes(C, n) bytes of the caller's, 256-byte aligned, per call.
+ * st_op_channel_sort: per row the stable ascending order of feat + 0.0f - sorted_out [C][n] the values, perm_out [C][n] the
+ * element indices; either may be null.  Two calls on the same data give the same bits. */
+int st_op_sort_chunk(void);
+long long st_op_sort_scratch_bytes(int channels, long long n);
+int st_op_channel_sort(const float* feat, int channels, long long n, void* scratch, float* sorted_out, unsigned int* perm_out,
+                       void* stream);
+/* out [C][n_out] = the quantile functions q [C][n_in] at the n_out midpoints (st_plan_set_w2_marginal's target formula). */
+int st_op_resample_quantiles(const float* q, int channels, long long n_in, long long n_out, float* out, void* stream);
+/* loss_out[0] = sum_c sum_k (f_c,pi_c(k) - target_c,k)^2 / (C n) at weight 1, target [C][n] with sorted rows;
+ * unit_grad_out [C][n] = d loss / d feat (autograd: saved on the node) ... */
+int st_op_w2_marginal_loss(const float* feat, int channels, long long n, const float* target, void* scratch, float* unit_grad_out,
+                           float* loss_out, void* stream);
+/* ... grad[i] = upstream[0] * unit_grad[i], i < count; upstream: a DEVICE scalar. */
+int st_op_w2_marginal_loss_backward(const float* unit_grad, long long count, const float* upstream, float* grad, void* stream);
 /* TVLoss (style_transfer.py:184-195) on a [3][H][W] image, H, W >= 1: the value alone (st_op_tv_loss writes the unit
  * gradient with it) ... */
 int st_op_tv_value(const float* image, int height, int width, float* scratch, float* loss_out, void* stream);

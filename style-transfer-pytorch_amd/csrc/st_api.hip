@@ -457,6 +457,9 @@ int st_plan_set_region_style_target(st_plan* p, int region, int index, const flo
                p->n_regions);
     ST_REQUIRE(index >= 0 && index < p->n_style, "st_plan_set_region_style_target: index %d out of range (%d style layers)", index,
                p->n_style);
+    ST_REQUIRE(!p->style_marg[index],
+               "st_plan_set_style_target: style layer %d is flagged marginal (st_plan_set_w2_marginal): its target is a quantile function, "
+               "set by st_plan_set_style_quantiles", index);
     hipStream_t s = static_cast<hipStream_t>(stream);
     StyleHead& h = region_head_at(p, region, p->style_op[index]);
     if (ensure_style_alloc(p, h, alloc_kind_of(p, index))) return 1;
@@ -474,6 +477,31 @@ int st_plan_set_region_style_target(st_plan* p, int region, int index, const flo
     if (launch_cov_from_moments(mean, srm, h.cov_t, h.n, style_eps_of(p, index), s)) return 1;
     if (ns_sqrt_forward(h.cov_t, h.root_t, h.n, h.ns, s)) return 1;
     h.target_set = true;
+    return 0;
+}
+
+int st_plan_set_style_quantiles(st_plan* p, int index, const float* q, long long n_q, void* stream) {
+    ST_REQUIRE(p && q, "st_plan_set_style_quantiles: null argument");
+    ST_REQUIRE(index >= 0 && index < p->n_style, "st_plan_set_style_quantiles: index %d out of range (%d style layers)", index, p->n_style);
+    ST_REQUIRE(p->style_marg[index], "st_plan_set_style_quantiles: style layer %d is not flagged marginal (st_plan_set_w2_marginal): its "
+               "target is set by st_plan_set_style_target", index);
+    ST_REQUIRE(n_q >= 1, "st_plan_set_style_quantiles: %lld order statistics per channel: at least one", n_q);
+    StyleHead& h = p->head[p->style_op[index]];
+    if (ensure_style_alloc(p, h, 3)) return 1;
+    if (launch_resample_quantiles(q, h.n, n_q, h.npix_local, h.marg_t, static_cast<hipStream_t>(stream))) return 1;
+    h.target_set = true;
+    return 0;
+}
+
+int st_plan_style_quantiles(st_plan* p, int index, float** target, int* channels, long long* n) {
+    ST_REQUIRE(p && target && channels && n, "st_plan_style_quantiles: null argument");
+    ST_REQUIRE(index >= 0 && index < p->n_style, "st_plan_style_quantiles: index %d out of range (%d style layers)", index, p->n_style);
+    const StyleHead& h = p->head[p->style_op[index]];
+    ST_REQUIRE(p->style_marg[index] && h.target_set && h.marg_t,
+               "st_plan_style_quantiles: style layer %d holds no quantile target (st_plan_set_w2_marginal, st_plan_set_style_quantiles)", index);
+    *target = h.marg_t;
+    *channels = h.n;
+    *n = h.npix_local;
     return 0;
 }
 

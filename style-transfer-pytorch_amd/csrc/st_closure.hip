@@ -360,7 +360,14 @@ int ensure_moment_alloc(st_plan* p, StyleHead& h) {
 // target and nothing else - no covariance, no root, no Newton-Schulz workspace; a W2 head all of those
 // (kind 2, internal - alloc_kind_of: a W2 entry flagged diagonal, st_plan_set_w2_diagonal, holds its 2 C targets, the stats
 // launch's partials, 2 C coefficients and a ticket; no Gram workspace, no C x C buffer)
+// (kind 3, internal: a W2 entry flagged marginal, st_plan_set_w2_marginal, holds its C N target and the sort's scratch - the
+// ticket, the partials and two buffers of keys; no C x C buffer, no Newton-Schulz workspace)
 int ensure_style_alloc(st_plan* p, StyleHead& h, int kind) {
+    if (kind == 3) {
+        if (alloc_head_marginal(h, PlanAlloc{p})) return 1;
+        ST_HIP(hipStreamSynchronize(nullptr));
+        return 0;
+    }
     if (kind == 2) {
         if (alloc_head_diag(h, PlanAlloc{p})) return 1;
         ST_HIP(hipStreamSynchronize(nullptr));

@@ -710,6 +710,27 @@ int launch_channel_affine_grad(const float* feat, const float* sqrt_mask, const 
                                long long npix, float* grad, int accumulate, hipStream_t s);
 // a flagged head's target from the moments a W2 target is given: mean_t = mean, std_t = sqrt(max(srm_cc - mean_c^2, 0) + eps)
 int launch_diag_target(const float* mean, const float* srm, int n, float eps, float* mean_t, float* std_t, hipStream_t s);
+// ---- exact per-channel Wasserstein (sorted) W2 heads (st_plan_set_w2_marginal, st_op_channel_sort / st_op_w2_marginal_*; st_sort.hip) ----
+constexpr int kMarginalBlocks = 1024;             // workgroups of the residual pass at most: its partials
+constexpr long long kMarginalHeaderBytes = 8192;  // of a sort's scratch: the ticket's 16 bytes, at byte 256 the partials; then the keys
+int sort_chunk();                                 // keys one workgroup sorts in LDS: 4096, or 8192 under the option ST_SORT_CHUNK
+long long marginal_scratch_bytes(int channels, long long n);
+// a scratch of marginal_scratch_bytes bytes, 256-byte aligned, as the launches below read it: two buffers of C n 64-bit keys
+struct MarginalScratch {
+    unsigned int* ticket = nullptr;     // zero between launches
+    float* partials = nullptr;
+    unsigned long long *keys_a = nullptr, *keys_b = nullptr;
+};
+MarginalScratch marginal_scratch_of(void* scratch, int channels, long long n);
+// the rows of feat [C][n] in stable ascending order (ties by index, -0.0 as +0.0), as keys in m.keys_a: the order-preserving image
+// of the value in the high word, the element's index in the low word
+int launch_channel_sort(const float* feat, int channels, long long n, const MarginalScratch& m, hipStream_t s);
+int launch_unpack_keys(const unsigned long long* keys, long long count, float* sorted_out, unsigned int* perm_out, hipStream_t s);
+// out [C][n_out]: the quantile functions q [C][n_in] (sorted rows) at the n_out midpoints (include/st_amd.h); n_in == n_out: a copy
+int launch_resample_quantiles(const float* q, int channels, long long n_in, long long n_out, float* out, hipStream_t s);
+// the sort, then the residual pass against target [C][n]: grad [C][n] WRITTEN through the permutation, loss_out[0] the weighted term
+int marginal_head_run(const float* feat, int channels, long long n, const float* target, void* scratch, float weight, float* grad,
+                      float* loss_out, hipStream_t s);
 // ---- Laplacian loss on pooled images (st_plan_set_laplacian, st_op_laplacian_*; st_laplacian.hip) ----
 constexpr int kMaxLapPools = 4;
 constexpr int kLapBlocks = 1024;                  // workgroups of the residual pass at most: its partials

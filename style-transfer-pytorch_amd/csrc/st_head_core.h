@@ -32,7 +32,20 @@ struct StyleHead {
     // a W2 entry whose covariances are diagonal (st_plan_set_w2_diagonal): all it reads - the target (mu_t, sigma_t), the stats
     // launch's scratch (ticket, partials) and the gradient's coefficients [a | b]; none of the buffers above
     float *diag_mean_t = nullptr, *diag_std_t = nullptr, *diag_scratch = nullptr, *diag_coeffs = nullptr;
+    // a W2 entry matched on its exact per-channel marginals (st_plan_set_w2_marginal): the target's quantile functions [n][npix]
+    // and the sort's scratch (ticket, partials, two buffers of keys: marginal_scratch_bytes); none of the buffers above
+    float *marg_t = nullptr, *marg_scratch = nullptr;
 };
+
+// what a marginal head needs; the ticket in front of its scratch is zeroed on the null stream, which the caller synchronises
+template <class Alloc>
+int alloc_head_marginal(StyleHead& h, Alloc&& alloc) {
+    if (alloc(&h.marg_t, (size_t)h.n * (size_t)h.npix_local)) return 1;
+    if (h.marg_scratch) return 0;
+    if (alloc(&h.marg_scratch, (size_t)(marginal_scratch_bytes(h.n, h.npix_local) / 4))) return 1;
+    ST_HIP(hipMemset(h.marg_scratch, 0, 16));
+    return 0;
+}
 
 // what a diagonal head needs (alloc_head_diag); the ticket in front of its scratch is zeroed on the null stream, which the caller
 // synchronises

@@ -141,6 +141,10 @@ struct st_plan {
     // style entry, 0 on every Gram entry.  Any set flag runs the general closure (general_taps), on the reference's lists too;
     // either kinds setter and st_plan_set_taps clear them.
     int style_diag[16] = {};
+    // A W2 entry matched on its exact per-channel marginals (st_plan_set_w2_marginal, st_sort.hip): a flag per LISTED style entry,
+    // never together with style_diag, a custom eps, a style mask or regions.  Any set flag runs the general closure; either kinds
+    // setter and st_plan_set_taps clear them.
+    int style_marg[16] = {};
     float* kind_scratch = nullptr;                   // non-default kinds: [2 kStreamBlocks] per-block (sum d^2, sum |d|) of the
                                                      // term in flight, then [2] per term: sum d^2, sum |d| + eps (kind_totals)
     st::StyleHead head[st::kNumOps];                 // n / npix / npix_local of all 17 filled at create, buffers on first use;
@@ -385,7 +389,7 @@ bool targets_ready(const st_plan* p);
 float* loss_terms(st_plan* p);        // the array the closure's weighted terms go to, in SumLoss order
 float style_eps_of(const st_plan* p, int j);   // effective eps of style entry j / content entry i (mse: -1)
 float content_eps_of(const st_plan* p, int i);
-int alloc_kind_of(const st_plan* p, int j);    // what ensure_style_alloc is asked for entry j: its kind, or 2 for a diagonal W2 entry
+int alloc_kind_of(const st_plan* p, int j);    // what ensure_style_alloc is asked for entry j: its kind, 2 for a diagonal W2 entry, 3 for a marginal one
 
 // ---- st_laplacian.hip
 // the plan's Laplacian terms on `image`, behind the TV launch that wrote `grad` and `slot`: each pool size's term onto the

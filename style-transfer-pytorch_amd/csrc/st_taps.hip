@@ -58,6 +58,10 @@
 // head is two launches through the same site - the channel statistics with the term and the gradient's coefficients, then
 // dF m_p written to the seed buffer (a region r >= 1: added onto it) - with no Gram pass, chain, 1x1 step, bound word,
 // mask-column launch or region scratch.  Every other entry runs by its kind as above.
+//
+// So does a W2 entry flagged marginal (st_plan_set_w2_marginal, st_sort.hip): its head is the segmented sort of the tap's rows and
+// the residual pass against the target's quantile functions, which writes dF to the seed buffer through the permutation.  Such an
+// entry takes no style mask and no regions.
 #include <algorithm>
 #include <cmath>
 
@@ -109,6 +113,11 @@ static bool any_diagonal(const st_plan* p) {
     for (int j = 0; j < p->n_style; ++j) any = any || p->style_diag[j] != 0;
     return any;
 }
+static bool any_marginal(const st_plan* p) {
+    bool any = false;
+    for (int j = 0; j < p->n_style; ++j) any = any || p->style_marg[j] != 0;
+    return any;
+}
 static bool default_eps(const st_plan* p) {
     bool ok = true;
     for (int i = 0; i < p->n_content; ++i) ok = ok && p->content_eps[i] < 0.f;
@@ -119,7 +128,7 @@ static bool default_eps(const st_plan* p) {
 bool general_taps(const st_plan* p) {
     static Option force("ST_GENERAL_TAPS", 0);
     return !p->strip && (!p->reference_taps || !default_kinds(p) || !default_eps(p) || p->style_mask || p->n_regions > 0 ||
-                         p->content_mask || p->tv_mask || p->n_lap > 0 || any_diagonal(p) || force.get() != 0);
+                         p->content_mask || p->tv_mask || p->n_lap > 0 || any_diagonal(p) || any_marginal(p) || force.get() != 0);
 }
 
 float style_eps_of(const st_plan* p, int j) {
@@ -130,7 +139,7 @@ float content_eps_of(const st_plan* p, int i) {
     return p->content_kind[i] == 0 ? -1.f : p->content_eps[i] >= 0.f ? p->content_eps[i] : kScaledMseEps;
 }
 
-int alloc_kind_of(const st_plan* p, int j) { return p->style_diag[j] ? 2 : p->style_kind[j]; }
+int alloc_kind_of(const st_plan* p, int j) { return p->style_marg[j] ? 3 : p->style_diag[j] ? 2 : p->style_kind[j]; }
 
 int closure_top_op(const st_plan* p) {
     if (!general_taps(p)) return kNumOps - 1;
@@ -201,6 +210,13 @@ int diag_head(st_plan* p, const HeadSite& at, float* seed, int accumulate, hipSt
     return diag_head_run(*at.h, at.tap->y, at.weight, at.eps, at.sqrt_mask, at.mask_sum, at.loss, seed, accumulate, s);
 }
 
+// A W2 entry flagged marginal (st_plan_set_w2_marginal, st_sort.hip): the sort of the tap's rows, then the residual pass, which
+// writes dF to the seed through the permutation and the weighted term to the entry's slot.  No mask, no eps, no bound word.
+int marginal_head(st_plan* p, const HeadSite& at, float* seed, hipStream_t s) {
+    const StyleHead& h = *at.h;
+    return marginal_head_run(at.tap->y, h.n, h.npix_local, h.marg_t, h.marg_scratch, at.weight, seed, at.loss, s);
+}
+
 // Style regions in force: the heads of every listed entry, in `order`, one per region in region order.  dF_r's pixel columns
 // times m_r: region 0 in place on the seed it wrote (the masked plan's launches), region r >= 1 from the scratch buffer ONTO the
 // seed.  Then each entry's term from its regions' terms.
@@ -213,6 +229,7 @@ int region_heads(st_plan* p, const int* order, bool* styled, hipStream_t s) {
         float* seed = p->tap_seed[p->style_op[j]];
         for (int r = 0; r < regions; ++r) {
             const HeadSite at = region_head_site(p, j, r);
+            ST_REQUIRE(!p->style_marg[j], "style layer %d is flagged marginal (st_plan_set_w2_marginal): it takes no style regions", j);
             if (p->style_diag[j]) {            // region 0 writes the seed, region r >= 1 adds onto it: no scratch buffer
                 if (diag_head(p, at, seed, r > 0, s)) return 1;
                 continue;
@@ -279,6 +296,11 @@ int general_loss_and_grad(st_plan* p, const float* image, float* grad_out, float
     } else {
         for (int k = 0; k < ns; ++k) {
             const HeadSite at = general_head_site(p, order[k]);
+            if (p->style_marg[order[k]]) {
+                if (marginal_head(p, at, at.grad, s)) return 1;
+                styled[p->style_op[order[k]]] = true;
+                continue;
+            }
             if (p->style_diag[order[k]]) {
                 if (diag_head(p, at, at.grad, 0, s)) return 1;
                 styled[p->style_op[order[k]]] = true;
@@ -410,7 +432,7 @@ int st_plan_set_taps(st_plan* p, int n_content, const int* content_layers, int n
         p->content_kind[i] = ckind;
         p->style_kind[i] = skind;
         p->content_eps[i] = p->style_eps[i] = -1.f;
-        p->style_diag[i] = 0;
+        p->style_diag[i] = p->style_marg[i] = 0;
         if (keep_weights) continue;
         p->content_weight[i] = i < n_content ? 0.015f / (float)n_content : 0.f;
         p->style_weight[i] = i >= n_style ? 0.f : ref ? kStyleWeight[i] : 1.f / (float)n_style;
@@ -433,7 +455,7 @@ int apply_loss_kinds(st_plan* p, const int* ck, const int* sk) {
         p->content_kind[i] = ck[i];
         p->style_kind[i] = sk[i];
         p->content_eps[i] = p->style_eps[i] = -1.f;      // an eps belongs to a module of one kind: set it after the kinds
-        p->style_diag[i] = 0;                            // ... and so does the diagonal flag of a W2 entry
+        p->style_diag[i] = p->style_marg[i] = 0;         // ... and so do the diagonal and marginal flags of a W2 entry
     }
     // a target is kept in the form its kind reads (a root, or a Gram matrix): as after st_plan_set_taps, every target set
     // before is gone, every bound word is dealt again and nothing built on the former terms survives.  The lists and all
@@ -524,6 +546,9 @@ int st_plan_set_loss_eps(st_plan* p, const float* content_eps, const float* styl
         }
     }
     ST_REQUIRE(!p->strip || all_default, "st_plan_set_loss_eps: strip plans run the loss modules' default eps only");
+    for (int j = 0; j < p->n_style; ++j)
+        ST_REQUIRE(!p->style_marg[j] || se[j] < 0.f,
+                   "st_plan_set_loss_eps: style layer %d is flagged marginal (st_plan_set_w2_marginal), whose term has no eps", j);
     std::copy(ce, ce + 16, p->content_eps);
     std::copy(se, se + 16, p->style_eps);
     // a W2 target is kept as the root of cov_t + eps I: every target set before is gone
@@ -539,6 +564,8 @@ int st_plan_set_w2_diagonal(st_plan* p, const int* flags) {
         ST_REQUIRE(flags[j] == 0 || flags[j] == 1, "st_plan_set_w2_diagonal: flag %d of style layer %d: 0 or 1", flags[j], j);
         ST_REQUIRE(flags[j] == 0 || p->style_kind[j] == 0,
                    "st_plan_set_w2_diagonal: style layer %d is of kind gram (StyleLoss): only a w2 layer's covariances can be diagonal", j);
+        ST_REQUIRE(flags[j] == 0 || !p->style_marg[j],
+                   "st_plan_set_w2_diagonal: style layer %d is flagged marginal (st_plan_set_w2_marginal): a layer takes one of the two", j);
         fl[j] = flags[j];
         any = any || fl[j] != 0;
     }
@@ -556,6 +583,37 @@ int st_plan_set_w2_diagonal(st_plan* p, const int* flags) {
 int st_plan_w2_diagonal(const st_plan* p, int* flags) {
     ST_REQUIRE(p && flags, "st_plan_w2_diagonal: null argument");
     for (int j = 0; j < p->n_style; ++j) flags[j] = p->style_diag[j];
+    return 0;
+}
+
+int st_plan_set_w2_marginal(st_plan* p, const int* flags) {
+    ST_REQUIRE(p, "st_plan_set_w2_marginal: null plan");
+    int fl[16] = {};
+    bool any = false;
+    for (int j = 0; flags && j < p->n_style; ++j) {
+        ST_REQUIRE(flags[j] == 0 || flags[j] == 1, "st_plan_set_w2_marginal: flag %d of style layer %d: 0 or 1", flags[j], j);
+        ST_REQUIRE(flags[j] == 0 || p->style_kind[j] == 0,
+                   "st_plan_set_w2_marginal: style layer %d is of kind gram (StyleLoss): only a w2 layer can be matched on its marginals", j);
+        ST_REQUIRE(flags[j] == 0 || !p->style_diag[j],
+                   "st_plan_set_w2_marginal: style layer %d is flagged diagonal (st_plan_set_w2_diagonal): a layer takes one of the two", j);
+        ST_REQUIRE(flags[j] == 0 || p->style_eps[j] < 0.f,
+                   "st_plan_set_w2_marginal: style layer %d has a custom eps (st_plan_set_loss_eps); the marginal term has no eps", j);
+        fl[j] = flags[j];
+        any = any || fl[j] != 0;
+    }
+    ST_REQUIRE(!p->strip || !any, "st_plan_set_w2_marginal: strip plans run full W2 heads only");
+    ST_REQUIRE(!any || (!p->style_mask && !p->n_regions),
+               "st_plan_set_w2_marginal: a style mask or style regions are in force on this plan; weighted quantiles are not implemented - "
+               "clear them first");
+    std::copy(fl, fl + 16, p->style_marg);
+    // a target is kept in the form its head reads - quantile functions, or a root: every target set before is gone
+    drop_targets(p);
+    return 0;
+}
+
+int st_plan_w2_marginal(const st_plan* p, int* flags) {
+    ST_REQUIRE(p && flags, "st_plan_w2_marginal: null argument");
+    for (int j = 0; j < p->n_style; ++j) flags[j] = p->style_marg[j];
     return 0;
 }
 

@@ -89,6 +89,10 @@ def _declare(lib):
         'st_plan_loss_eps': (i32, [vp, ctypes.POINTER(f32), ctypes.POINTER(f32)]),
         'st_plan_set_w2_diagonal': (i32, [vp, ctypes.POINTER(i32)]),
         'st_plan_w2_diagonal': (i32, [vp, ctypes.POINTER(i32)]),
+        'st_plan_set_w2_marginal': (i32, [vp, ctypes.POINTER(i32)]),
+        'st_plan_w2_marginal': (i32, [vp, ctypes.POINTER(i32)]),
+        'st_plan_set_style_quantiles': (i32, [vp, i32, vp, i64, vp]),
+        'st_plan_style_quantiles': (i32, [vp, i32, pp, ip, ctypes.POINTER(i64)]),
         'st_plan_set_content_target_at': (i32, [vp, i32, vp, vp]),
         'st_plan_term_losses': (i32, [vp, pp, ip]),
         'st_plan_loss_and_grad': (i32, [vp, vp, vp, vp, vp]),
@@ -155,6 +159,12 @@ def _declare(lib):
         'st_op_channel_moments': (i32, [vp, i32, i64, vp, vp, vp, vp]),
         'st_op_w2_diag_loss': (i32, [vp, i32, i64, vp, vp, f32, vp, vp, vp, vp]),
         'st_op_w2_diag_loss_backward': (i32, [vp, i32, i64, vp, vp, vp, vp]),
+        'st_op_sort_chunk': (i32, []),
+        'st_op_sort_scratch_bytes': (i64, [i32, i64]),
+        'st_op_channel_sort': (i32, [vp, i32, i64, vp, vp, vp, vp]),
+        'st_op_resample_quantiles': (i32, [vp, i32, i64, i64, vp, vp]),
+        'st_op_w2_marginal_loss': (i32, [vp, i32, i64, vp, vp, vp, vp, vp]),
+        'st_op_w2_marginal_loss_backward': (i32, [vp, i64, vp, vp, vp]),
         'st_op_tv_value': (i32, [vp, i32, i32, vp, vp, vp]),
         'st_op_tv_loss_backward': (i32, [vp, i32, i32, vp, vp, vp]),
         'st_op_laplacian_scratch_floats': (i64, [i32, i32, i32, i32]),
@@ -417,6 +427,35 @@ class Plan:
         _check(self.lib.st_plan_w2_diagonal(self.handle, fa))
         return tuple(bool(v) for v in fa[:n])
 
+    def set_w2_marginal(self, flags=None):
+        """Match a 'w2' style layer on its exact per-channel marginals (st_plan_set_w2_marginal): None or False (no layer),
+        True (every layer of the list - all must be 'w2') or a sequence with one bool per style layer.  A flagged layer's
+        term is the mean over channels and ranks of ``(sort(f) - T)^2`` with ``T`` the style's quantile functions
+        (``set_style_quantiles``): a segmented sort of the tap and one residual pass, no C x C work.  Any set flag runs the
+        general closure; drops every target.  Refused together with a diagonal flag or a custom eps on the same layer, and
+        while a style mask or regions are set.  Either kinds setter and ``set_taps`` clear the flags: kinds, eps, diagonal,
+        then this, then the weights and targets."""
+        n = len(self.style_layers)
+        if flags is None or isinstance(flags, (bool, int)):
+            flags = [bool(flags)] * n
+        flags = list(flags)
+        if len(flags) != n:
+            raise ValueError(f'{len(flags)} marginal flags for {n} style layers: one per layer')
+        for v in flags:
+            if v not in (0, 1, False, True):
+                raise ValueError(f'marginal flag {v!r}: must be a bool')
+        fa = (ctypes.c_int * max(n, 1))(*[int(v) for v in flags])
+        with torch.cuda.device(self.device):
+            _check(self.lib.st_plan_set_w2_marginal(self.handle, fa))
+
+    @property
+    def w2_marginal(self):
+        """The marginal flag of each style layer, a tuple of bools (st_plan_w2_marginal)."""
+        n = len(self.style_layers)
+        fa = (ctypes.c_int * max(n, 1))()
+        _check(self.lib.st_plan_w2_marginal(self.handle, fa))
+        return tuple(bool(v) for v in fa[:n])
+
     def _layer_values(self, entry, ctype):
         ca, sa = (ctype * max(len(self.content_layers), 1))(), (ctype * max(len(self.style_layers), 1))()
         _check(entry(self.handle, ca, sa))
@@ -529,6 +568,37 @@ class Plan:
         with torch.cuda.device(self.device):
             _check(self.lib.st_plan_moments(self.handle, int(layer), _ptr(mean), _ptr(srm), _stream()))
         return mean, srm
+
+    def tap_pixels(self, layer):
+        """h w of a tap at this plan's size."""
+        data, h, w = ctypes.c_void_p(), ctypes.c_int(), ctypes.c_int()
+        _check(self.lib.st_plan_feature(self.handle, int(layer), ctypes.byref(data), None, ctypes.byref(h), ctypes.byref(w)))
+        return h.value * w.value
+
+    def quantiles(self, layer):
+        """The sorted tap of the last forward, [C, N] with N = h w: every channel's values in ascending order, its quantile
+        function (st_op_channel_sort on the tap) - what ``set_style_quantiles`` takes, beside ``moments``."""
+        if int(layer) not in TAPS:
+            raise ValueError(f'features[{int(layer)}] is not one of the taps {TAPS}')
+        return op_channel_sort(self.feature(layer)[0])[0]
+
+    def set_style_quantiles(self, index, q):
+        """The target of a style layer flagged by ``set_w2_marginal``: ``q`` [C, n_q], sorted rows - a style tap's
+        ``quantiles``, or a weighted blend of several - resampled to this plan's pixel count (st_plan_set_style_quantiles)."""
+        q = q.to(device=self.device, dtype=torch.float32).contiguous()
+        if q.ndim != 2:
+            raise ValueError(f'quantiles of shape {tuple(q.shape)}: [C, n_q]')
+        with torch.cuda.device(self.device):
+            _check(self.lib.st_plan_set_style_quantiles(self.handle, int(index), _ptr(q), int(q.shape[1]), _stream()))
+
+    def style_quantiles(self, index):
+        """Copy of a flagged layer's resampled target, [C, N] (st_plan_style_quantiles)."""
+        data, c, n = ctypes.c_void_p(), ctypes.c_int(), ctypes.c_longlong()
+        _check(self.lib.st_plan_style_quantiles(self.handle, int(index), ctypes.byref(data), ctypes.byref(c), ctypes.byref(n)))
+        out = torch.empty((c.value, n.value), device=self.device, dtype=torch.float32)
+        with torch.cuda.device(self.device):
+            _copy_d2d(out, data.value)
+        return out
 
     def set_style_mask(self, mask):
         """A spatial mask for the style statistics (st_plan_set_style_mask): a [height, width] tensor with values in [0, 1]
@@ -1273,6 +1343,70 @@ def op_w2_diag_loss_backward(x, coeffs, upstream):
     grad = torch.empty(x.shape, device=x.device, dtype=torch.float32)
     with torch.cuda.device(x.device):
         _check(lib.st_op_w2_diag_loss_backward(_ptr(x), c, npix, _ptr(coeffs), _ptr(upstream), _ptr(grad), _stream()))
+    return grad
+
+
+def sort_chunk():
+    """The keys one workgroup of the segmented sort orders in LDS (st_op_sort_chunk): rows up to this length need no merge pass."""
+    return int(load_library().st_op_sort_chunk())
+
+
+def _rows(x):
+    """A [..., C, h, w] tensor (one image) or a [C, N] matrix as (C, N)."""
+    if x.ndim == 2:
+        return int(x.shape[0]), int(x.shape[1])
+    return int(x.shape[-3]), int(x.shape[-2]) * int(x.shape[-1])
+
+
+def _sort_scratch(x, c, n):
+    nbytes = int(load_library().st_op_sort_scratch_bytes(c, n))
+    return torch.empty(max(nbytes, 16), device=x.device, dtype=torch.uint8)
+
+
+def op_channel_sort(x, values=True, indices=True):
+    """(sorted rows [C, N] fp32, permutation [C, N] int64) of a [C, N] matrix or a [..., C, h, w] tensor (one image): per
+    row the stable ascending order of ``x + 0.0`` (st_op_channel_sort).  An output not asked for is None."""
+    lib = load_library()
+    c, n = _rows(x)
+    scratch = _sort_scratch(x, c, n)
+    out = torch.empty((c, n), device=x.device, dtype=torch.float32) if values else None
+    perm = torch.empty((c, n), device=x.device, dtype=torch.int32) if indices else None
+    with torch.cuda.device(x.device):
+        _check(lib.st_op_channel_sort(_ptr(x), c, n, ctypes.c_void_p(scratch.data_ptr()), _ptr(out),
+                                      ctypes.c_void_p(perm.data_ptr()) if indices else None, _stream()))
+    if indices:                                    # (uint32 indices: the bits of an int32 tensor, widened without sign)
+        perm = perm.to(torch.int64) & 0xffffffff
+    return out, perm
+
+
+def op_resample_quantiles(q, n_out):
+    """The quantile functions q [C, n_in] (sorted rows) at n_out midpoints, [C, n_out] (st_op_resample_quantiles)."""
+    lib = load_library()
+    c, n_in = int(q.shape[0]), int(q.shape[1])
+    out = torch.empty((c, int(n_out)), device=q.device, dtype=torch.float32)
+    with torch.cuda.device(q.device):
+        _check(lib.st_op_resample_quantiles(_ptr(q), c, n_in, int(n_out), _ptr(out), _stream()))
+    return out
+
+
+def op_w2_marginal_loss(x, target):
+    """(the marginal W2 loss [0-dim], its gradient at weight 1, shaped like x) - st_op_w2_marginal_loss; target [C, N]."""
+    lib = load_library()
+    c, n = _rows(x)
+    scratch = _sort_scratch(x, c, n)
+    loss = torch.empty((), device=x.device, dtype=torch.float32)
+    unit = torch.empty(x.shape, device=x.device, dtype=torch.float32)
+    with torch.cuda.device(x.device):
+        _check(lib.st_op_w2_marginal_loss(_ptr(x), c, n, _ptr(target), ctypes.c_void_p(scratch.data_ptr()), _ptr(unit), _ptr(loss),
+                                          _stream()))
+    return loss, unit
+
+
+def op_w2_marginal_loss_backward(unit_grad, upstream):
+    lib = load_library()
+    grad = torch.empty(unit_grad.shape, device=unit_grad.device, dtype=torch.float32)
+    with torch.cuda.device(unit_grad.device):
+        _check(lib.st_op_w2_marginal_loss_backward(_ptr(unit_grad), unit_grad.numel(), _ptr(upstream), _ptr(grad), _stream()))
     return grad
 
 

@@ -308,6 +308,11 @@ def build_parser():
                    help="restrict both covariances of the 'w2' style layers to their diagonals (the mean / standard-deviation "
                         "style loss: two memory-bound launches per layer, no C x C work): 1 for every 'w2' layer, or a "
                         "comma-separated list with one flag per style layer, e.g. '0,0,0,1,1' (default 0)")
+    p.add_argument('--style-marginal', type=_diagonal_flags, default=False, metavar='{0,1}[,...]',
+                   help="match the 'w2' style layers on their exact per-channel marginals (per channel the sorted features "
+                        "against the style's: the histogram loss in its exact form; a segmented sort per layer and iteration): "
+                        "1 for every 'w2' layer, or a comma-separated list with one flag per style layer, e.g. '0,0,0,1,1' "
+                        "(default 0); not together with --style-diagonal on the same layer, style masks or regions")
     p.add_argument('--style-mask', type=str, default=None, metavar='PATH',
                    help='an image (read as greyscale, white = 1) saying which pixels of the output take the style; it is '
                         'resized to every scale')
@@ -349,7 +354,7 @@ def _loss_names(choices):
 
 
 def _diagonal_flags(text):
-    """argparse type of --style-diagonal: one flag stays the bool, a comma-separated list becomes the list of bools."""
+    """argparse type of --style-diagonal / --style-marginal: one flag stays the bool, a comma-separated list becomes the list of bools."""
     items = text.split(',')
     for item in items:
         if item not in ('0', '1'):
@@ -409,10 +414,11 @@ def apply_style_masks(st, args):
 
 
 def apply_loss_kinds(st, args):
-    """--content-loss / --style-loss / --content-eps / --style-eps / --style-diagonal onto the StyleTransfer attributes that stylize() reads."""
+    """--content-loss / --style-loss / --content-eps / --style-eps / --style-diagonal / --style-marginal onto the StyleTransfer attributes that stylize() reads."""
     st.content_loss, st.style_loss = args.content_loss, args.style_loss
     st.content_eps, st.style_eps = args.content_eps, args.style_eps
     st.style_diagonal = args.style_diagonal
+    st.style_marginal = args.style_marginal
     return st
 
 

@@ -11,6 +11,8 @@ others - one dense fp32 HIP image, any channel count, runs st_op_laplacian_value
 ``StyleLossW2Diag`` is this project's own too: ``StyleLossW2`` with both covariances restricted to their diagonals, the module
 form of ``st_plan_set_w2_diagonal``'s term - one dense fp32 HIP tensor, any channel count, runs st_op_w2_diag_loss /
 st_op_w2_diag_loss_backward.
+``StyleLossW2Marginal`` is the module form of ``st_plan_set_w2_marginal``'s term: per channel the sorted tap against the style's
+sorted tap - one dense fp32 HIP tensor, any channel count, runs st_op_w2_marginal_loss / st_op_w2_marginal_loss_backward.
 
 Native dispatch.  On an ELIGIBLE tensor (``eligible`` below: one dense fp32 tensor on a HIP device, batch 1 or absent, 64 /
 128 / 256 / 512 channels for the style modules, the module's buffers beside it in fp32) the five loss modules run in the
@@ -62,7 +64,7 @@ class native:
         native.enabled, native.precision = self._former
 
 
-# calls that went to the library, by kind ('w2', 'gram', 'mse', 'scaled_mse', 'tv', 'laplacian', 'w2_diag', 'moments'): the native indicator of the
+# calls that went to the library, by kind ('w2', 'gram', 'mse', 'scaled_mse', 'tv', 'laplacian', 'w2_diag', 'w2_marginal', 'moments'): the native indicator of the
 # modules that hold no head
 native_calls = {}
 _heads = weakref.WeakKeyDictionary()       # module -> its _hip.Head (no module attribute: deepcopy / pickle / state_dict never see it)
@@ -101,6 +103,11 @@ def eligible(input, kind, buffers=()):
         if not (_one_dense_fp32(input, 3) and input.ndim in (3, 4) and input.shape[-3] <= 65535):
             return False
         sizes = (input.shape[-3],) * len(buffers)
+    elif kind == 'w2_marginal':
+        # (any channel count; buffers: none, or the module's target resampled to the input's pixel count)
+        if not (_one_dense_fp32(input, 3) and input.ndim in (3, 4) and input.shape[-2] * input.shape[-1] < 1 << 32):
+            return False
+        sizes = (input.shape[-3] * input.shape[-2] * input.shape[-1],) * len(buffers)
     elif kind == 'tv':
         if not (_one_dense_fp32(input, 3) and input.ndim in (3, 4) and input.shape[-3] == 3 and input.numel() < 1 << 31):
             return False
@@ -293,6 +300,30 @@ class _W2DiagLoss(torch.autograd.Function):
             return _torch_vjp(ctx.torch_forward, input, grad_output), None, None, None, None
         grad = _hip.op_w2_diag_loss_backward(_dense(input), coeffs, grad_output.contiguous())
         return grad.view(input.shape), None, None, None, None
+
+
+class _W2MarginalLoss(torch.autograd.Function):
+    """StyleLossW2Marginal.forward: st_op_w2_marginal_loss; the gradient at weight 1 - written through the sort's permutation
+    by the same pass - stays on the node for st_op_w2_marginal_loss_backward."""
+
+    @staticmethod
+    def forward(ctx, input, module, target):
+        from . import _hip
+        loss, unit = _hip.op_w2_marginal_loss(_dense(input), target)
+        _count('w2_marginal')
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(input, unit)
+            ctx.torch_forward = module._forward_torch
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        from . import _hip
+        input, unit = ctx.saved_tensors
+        if torch.is_grad_enabled():
+            return _torch_vjp(ctx.torch_forward, input, grad_output), None, None
+        grad = _hip.op_w2_marginal_loss_backward(unit, grad_output.contiguous())
+        return grad.view(input.shape), None, None
 
 
 class _TVLoss(torch.autograd.Function):
@@ -536,6 +567,82 @@ class StyleLossW2Diag(nn.Module):
         mean, srm = self._get_target_torch(input)
         std = self._std(mean, srm, self.eps)
         return torch.mean((mean - self.mean) ** 2) + torch.mean((std - self.std) ** 2)
+
+
+class StyleLossW2Marginal(nn.Module):
+    """The W2 distance between the exact one-dimensional marginals of the input's channels and of a style tap's: per channel
+    the sorted input against the style's sorted tap, ``mean((sort(f) - T)^2)`` - Risser et al.'s histogram loss in its exact
+    form, the sliced Wasserstein loss of Heitz et al. along the channel axes (a user's own projections compose as
+    ``R @ F`` in front).  Not in the reference; include/st_amd.h (st_plan_set_w2_marginal) fixes the semantics: the sort is
+    the stable ascending one of ``f + 0.0``, its permutation a constant of the gradient, and ``T`` is the target's quantile
+    function at the input's pixel count (``resample``: midpoint convention, a copy when the counts agree), so the target's own
+    features give exactly 0 with an exactly zero gradient.  ``target`` = [C, n_q], sorted rows (``get_target``).  The torch
+    path serves any device, dtype and batch; one dense fp32 HIP tensor of any channel count runs in the library
+    (st_sort.hip: a segmented sort and one residual pass)."""
+
+    def __init__(self, target):
+        super().__init__()
+        if target.ndim != 2:
+            raise ValueError(f'target of shape {tuple(target.shape)}: [C, n_q], every row sorted')
+        self.register_buffer('target', target)
+
+    @staticmethod
+    def get_target(target):
+        """The sorted rows of the features, [..., C, h w]: every channel's quantile function.  Quantile functions resampled to
+        one length (``resample``) can be blended, as moments can."""
+        if native.enabled and eligible(target, 'w2_marginal') and not _wants_grad(target):
+            from . import _hip
+            _count('moments')
+            values, _ = _hip.op_channel_sort(_dense(target), indices=False)
+            return values.view(*target.shape[:-2], -1)
+        return StyleLossW2Marginal._get_target_torch(target)
+
+    @staticmethod
+    def _get_target_torch(target):
+        return torch.sort(target.flatten(-2) + 0.0, dim=-1, stable=True).values
+
+    @staticmethod
+    def resample(q, n):
+        """Quantile functions q [..., n_q] at n midpoints: ``lerp(q, u)`` with ``u = clamp((i + 1/2) n_q / n - 1/2, 0, n_q - 1)``
+        evaluated in float64, linear between ``floor(u)`` and ``floor(u) + 1`` in q's dtype."""
+        n_q = q.shape[-1]
+        if n_q == n:
+            return q
+        u = ((torch.arange(n, dtype=torch.float64, device=q.device) + 0.5) * n_q / n - 0.5).clamp(0, n_q - 1)
+        i0 = u.floor().long()
+        i1 = (i0 + 1).clamp(max=n_q - 1)
+        t = (u - i0).to(q.dtype)
+        a, b = q[..., i0], q[..., i1]
+        return torch.where(t == 0, a, a + t * (b - a))
+
+    def _target_for(self, input):
+        """The target at the input's pixel count, resampled once per (count, target buffer, version)."""
+        n = input.shape[-2] * input.shape[-1]
+        target = self.target
+        if target.shape[-1] == n:
+            return target
+        cached = self.__dict__.get('_resampled')
+        if cached is None or cached[0] is not target or cached[1] != target._version or cached[2].shape[-1] != n:
+            if native.enabled and _one_dense_fp32(target, 2) and target.is_contiguous():
+                from . import _hip
+                resampled = _hip.op_resample_quantiles(target, n)
+            else:
+                resampled = self.resample(target, n)
+            cached = self.__dict__['_resampled'] = (target, target._version, resampled)
+        return cached[2]
+
+    def forward(self, input):
+        if native.enabled and eligible(input, 'w2_marginal') and self.target.shape[0] == input.shape[-3] and \
+                not self.target.requires_grad and self.target.device == input.device and self.target.dtype == torch.float32:
+            target = self._target_for(input)
+            if eligible(input, 'w2_marginal', (target,)):
+                return _W2MarginalLoss.apply(input, self, target)
+        return self._forward_torch(input)
+
+    def _forward_torch(self, input):
+        n = input.shape[-2] * input.shape[-1]
+        values = torch.sort(input.flatten(-2) + 0.0, dim=-1, stable=True).values
+        return torch.mean((values - self.resample(self.target, n)) ** 2)
 
 
 class TVLoss(nn.Module):

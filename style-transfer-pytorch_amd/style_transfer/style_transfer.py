@@ -319,6 +319,48 @@ def _resolve_style_diagonal(style_diagonal, style_loss, world=1):
     return flags
 
 
+def _resolve_style_marginal(style_marginal, style_loss, style_diagonal=None, style_eps=None, masked=False, world=1):
+    """``StyleTransfer.style_marginal`` as the fused closure takes it: one bool per entry of ``style_loss`` (the resolved
+    kinds).  A bool means every 'w2' layer that is not flagged diagonal; a sequence holds one bool per entry of style_layers.
+    ``style_diagonal`` / ``style_eps``: the resolved lists (one per layer, eps None = default).  Raises ``ValueError``
+    naming the attribute for a wrong length, a value that is no bool, a true flag on a 'gram' layer, on a layer flagged
+    diagonal or with a custom eps, for any true flag together with style masks or regions (``masked``) or on several
+    ranks, before any device work."""
+    n = len(style_loss)
+    diagonal = list(style_diagonal) if style_diagonal is not None else [False] * n
+    epses = list(style_eps) if style_eps is not None else [None] * n
+    if isinstance(style_marginal, (bool, np.bool_)):
+        flags = [bool(style_marginal) and name == _hip.STYLE_LOSSES[0] and not diag for name, diag in zip(style_loss, diagonal)]
+    else:
+        if isinstance(style_marginal, str) or not isinstance(style_marginal, (list, tuple)):
+            raise ValueError(f'style_marginal {style_marginal!r}: give a bool, or a sequence with one bool per entry of style_layers')
+        flags = list(style_marginal)
+        if len(flags) != n:
+            raise ValueError(f'style_marginal {style_marginal!r}: {len(flags)} flags for {n} layers; give one bool, or exactly '
+                             'one per entry of style_layers')
+        for i, (flag, name) in enumerate(zip(flags, style_loss)):
+            if not isinstance(flag, (bool, np.bool_)) and flag not in (0, 1):
+                raise ValueError(f'style_marginal {style_marginal!r}: {flag!r} is not a bool')
+            if flag and name != _hip.STYLE_LOSSES[0]:
+                raise ValueError(f"style_marginal {style_marginal!r}: layer {i} has the loss {name!r} (StyleLoss on Gram "
+                                 "matrices); only a 'w2' layer can be matched on its marginals")
+            if flag and diagonal[i]:
+                raise ValueError(f'style_marginal {style_marginal!r}: layer {i} is flagged in style_diagonal too; a layer takes '
+                                 'one of the two')
+        flags = [bool(flag) for flag in flags]
+    for i, flag in enumerate(flags):
+        if flag and epses[i] is not None:
+            raise ValueError(f'style_marginal {style_marginal!r}: layer {i} has the custom style_eps {epses[i]!r}; the marginal '
+                             'term has no eps')
+    if masked and any(flags):
+        raise ValueError(f'style_marginal {style_marginal!r} together with style_mask, style_regions or style_image_masks: '
+                         'weighted quantiles are out of scope - clear one of them')
+    if world > 1 and any(flags):
+        raise ValueError(f'style_marginal {style_marginal!r} on {world} ranks: row strips run full W2 heads only; marginal '
+                         'heads are out of scope for strips - run them on one device')
+    return flags
+
+
 def _mask_image(mask, attr):
     """One mask as (PIL image, divisor): a PIL image becomes mode 'L' (divisor 255), a 2-D numpy / torch array with values
     in [0, 1] a mode 'F' image (divisor 1).  Raises ``ValueError`` naming ``attr``."""
@@ -846,6 +888,12 @@ class StyleTransfer:
     # reference has none): the mean / standard-deviation style loss, two memory-bound launches per layer and no C x C work.
     # False, True (every 'w2' layer) or a sequence with one bool per entry of style_layers.  One device only.
     style_diagonal = False
+    # 'w2' layers matched on their exact per-channel marginals (_hip.Plan.set_w2_marginal, losses.StyleLossW2Marginal; the
+    # reference has none): per channel the sorted tap against the style's sorted tap - the histogram loss in its exact form,
+    # which tells sparse from dense where every second-moment statistic cannot.  A segmented sort per layer and iteration.
+    # False, True (every 'w2' layer) or a sequence with one bool per entry of style_layers.  Not together with
+    # style_diagonal or a custom style_eps on the same layer, nor with style masks or regions.  One device only.
+    style_marginal = False
     # Spatial masks for the style statistics (read by stylize() too; the reference has none).  style_mask: which pixels of the
     # OUTPUT take the style - a PIL image (read as 'L' / 255) or a 2-D numpy / torch array in [0, 1], resized bilinearly to
     # every scale; the style heads then take mask-weighted moments of the iterate's taps (_hip.Plan.set_style_mask).
@@ -960,6 +1008,7 @@ class StyleTransfer:
             plan.forward(content, max(content_layers))
             plan.set_content_target_from_forward()
         blends = [{} for _ in range(len(regions[0]) if regions else 1)]
+        marginal, quantiles = plan.w2_marginal, {}      # (flagged layers: never with a mask or regions, _resolve_style_marginal)
         for i, image in enumerate(style_images):
             blended = blends[region_of[i]]
             if style_size is None:
@@ -979,7 +1028,17 @@ class StyleTransfer:
             image_mask = image_masks[i] if image_masks else None
             if image_mask is not None:
                 splan.set_style_mask(_sized_mask(image_mask, sw, sh))
-            for layer in style_layers:
+            for idx, layer in enumerate(style_layers):
+                if marginal[idx]:
+                    # a layer matched on its marginals: the style tap's quantile functions at the iterate's pixel count,
+                    # blended by the images' weights (in one dimension the Wasserstein barycentre)
+                    q = _hip.op_resample_quantiles(splan.quantiles(layer), plan.tap_pixels(layer))
+                    q *= style_weights[i]
+                    if layer not in quantiles:
+                        quantiles[layer] = q
+                    else:
+                        quantiles[layer].add_(q)
+                    continue
                 mean, srm = splan.moments(layer)
                 mean *= style_weights[i]
                 srm *= style_weights[i]
@@ -995,7 +1054,9 @@ class StyleTransfer:
             plan.set_region_weights(regions[2])
         for r, blended in enumerate(blends):
             for idx, layer in enumerate(style_layers):
-                if regions:
+                if marginal[idx]:
+                    plan.set_style_quantiles(idx, quantiles[layer])
+                elif regions:
                     plan.set_region_style_target(r, idx, *blended[layer])
                 else:
                     plan.set_style_target(idx, *blended[layer])
@@ -1140,6 +1201,10 @@ class StyleTransfer:
         regions = _resolve_style_regions(self.style_regions, self.style_image_regions, self.style_region_weights,
                                          len(style_images), style_weights, self.style_mask,
                                          world=max(len(self.devices), _dist_info()[1]))
+        style_marginal = _resolve_style_marginal(self.style_marginal, style_loss, style_diagonal, style_eps,
+                                                 masked=any(value is not None for value in (self.style_mask, self.style_regions,
+                                                                                            self.style_image_masks)),
+                                                 world=max(len(self.devices), _dist_info()[1]))
         content_map, tv_map = _resolve_weight_maps(self.content_mask, self.tv_mask,
                                                    world=max(len(self.devices), _dist_info()[1]))
         # (the smallest scale's image bounds the pool sizes; a weight of 0 has no term and no size to check)
@@ -1279,6 +1344,8 @@ class StyleTransfer:
                     plan.set_loss_eps(content_eps, style_eps)
                 if any(style_diagonal):
                     plan.set_w2_diagonal(style_diagonal)
+                if any(style_marginal):
+                    plan.set_w2_marginal(style_marginal)
                 self._build_targets(plan, content.to(device), style_images, style_weights, scale, style_scale_fac,
                                     style_size, style_mask, image_masks, regions)
                 # the content and TV maps at this scale's size, on the iterate's plan only and after the targets (which they
