@@ -349,7 +349,7 @@ int st_plan_loss_kinds(const st_plan* plan, int* content_kind, int* style_kind);
  * the kind of a list whose entries agree and returns a mixed list to kind 0.  st_plan_layer_loss_kinds writes n_content /
  * n_style codes (either pointer may be null).
  * Order of configuration: layers (st_plan_set_taps), kinds, eps (st_plan_set_loss_eps), diagonal (st_plan_set_w2_diagonal),
- * marginal (st_plan_set_w2_marginal), weights, then the targets.
+ * marginal (st_plan_set_w2_marginal), nearest (st_plan_set_style_nearest), weights, then the targets.
  */
 int st_plan_set_layer_loss_kinds(st_plan* plan, const int* content_kinds, const int* style_kinds);
 int st_plan_layer_loss_kinds(const st_plan* plan, int* content_kinds, int* style_kinds);
@@ -441,6 +441,58 @@ int st_plan_w2_marginal(const st_plan* plan, int* flags);
 int st_plan_set_style_quantiles(st_plan* plan, int index, const float* q, long long n_q, void* stream);
 /* Borrows the resampled target of flagged entry `index`: *target [C][N] floats of the plan's, valid until the plan is destroyed. */
 int st_plan_style_quantiles(st_plan* plan, int index, float** target, int* channels, long long* n);
+
+/*
+ * The nearest-neighbour feature-matching option of a W2 style layer: flags[n_style], 0 or 1 in list order; a null pointer clears
+ * all.  Every other style statistic of a plan is a SUMMARY of the tap - second moments, or the per-channel distributions; this one
+ * says that each pixel's feature vector should look like some particular feature vector of the style image: the MRF /
+ * neural-neighbour family of style losses (Li & Wand, "Combining Markov Random Fields and Convolutional Neural Networks for Image
+ * Synthesis"; Kolkin et al., "Neural Neighbor Style Transfer"; the contextual loss), which copies local structure that moment
+ * matching smears.  It is an OPTION of a w2 layer - the kind names and codes do not change - and the reference has no such
+ * module, so the semantics are fixed here.  For flagged entry j with tap F [C][N], columns f_i, and the style's feature vectors
+ * S [C][M], columns s_k (M need not equal N; nothing is resampled):
+ *   k*(i)  = argmin_k |f_i - s_k|^2 = argmax_k (<f_i, s_k> - |s_k|^2 / 2),   ties: the lowest k
+ *   term_j = w_j sum_i |f_i - s_k*(i)|^2 / (C N)
+ *   dF_ci  = w_j (2 / (C N)) (f_ci - s_c,k*(i))
+ * The match is a constant of the gradient: the a.e. derivative of min_k, so the gradient is the true gradient of the term.  The
+ * matching is L2, not cosine, for that reason: the term is the quantity the search minimises - the one-sided Chamfer distance
+ * from the tap to the style set.  There is no eps.  Inputs are finite; with a NaN the result is unspecified, but every launch
+ * ends (no loop's trip count depends on a comparison of values, and an index is clamped into [0, M) before it is an address).
+ * bias_k = -|s_k|^2 / 2 is formed once by st_plan_set_style_vectors, in double, and rounded to fp32.  The search
+ * (csrc/st_nearest.hip) runs in the trunk's fp16x3 arithmetic with fp32 accumulation - S^T [M_pad][C] against the tap, both
+ * scaled by a power of two under their bounds and split into two fp16 planes while they are staged - so a match is optimal up
+ * to that arithmetic: |f_i - s_k*(i)|^2 exceeds the minimum by at most a few 2^-21 C max|F| max|S| (tests/test_style_nearest_gpu.py
+ * derives the bound), and at the style's own tap the term is at most that, not promised to be exactly 0.  The scores are never
+ * written: a workgroup owns 128 pixels and a contiguous range of k tiles, keeps a running (score, k) per lane, and writes one
+ * (score, k) per pixel and split; the split count depends on the shape alone.  The finish pass merges the splits in split order
+ * under the same rule (greater, or equal and lower k), gathers s_k* as a row of S^T, WRITES dF to the tap's seed buffer (a
+ * content term of the same layer adds after it), keeps the matches (st_plan_nearest_indices) and reduces the term by per-block
+ * fp32 partials, a ticket and the last block's index-order sum in double.  No floating-point atomics: two closures give the same
+ * bits, indices included.  A flagged head allocates S^T, the bias, the split partials, N indices, the partials and a ticket; no
+ * C x C buffer, no Newton-Schulz workspace.  The cost is 2 C N M flop per iteration (three times that on the 16-bit pipe).
+ * Several style images give the UNION of their vectors: the caller concatenates them in image order.  An image of weight 0 is
+ * left out; otherwise the per-image weights do not enter (a union has no weights).
+ * Any set flag runs the general closure (csrc/st_taps.hip), on the default lists too; flags that are all 0, or set and then
+ * cleared, leave, bit for bit, a plan on which this was never called.  Like st_plan_set_w2_diagonal the call drops every target
+ * set before and invalidates a captured graph; either kinds setter and st_plan_set_taps clear the flags.
+ * Fails for a flag on a gram entry, on an entry flagged diagonal or marginal (and their setters refuse an entry flagged here), on
+ * an entry with a non-default eps (and st_plan_set_loss_eps refuses one for an entry flagged here), on an entry whose channel
+ * count is no multiple of 32, for a value other than 0 or 1, for any set flag on a strip plan, and while a style mask or style
+ * regions are set (their setters refuse while a flag is set).  st_plan_term_losses and the 8-float array keep their shapes.
+ * Order of configuration: layers, kinds, eps, diagonal, marginal, nearest, weights, then the targets.
+ */
+int st_plan_set_style_nearest(st_plan* plan, const int* flags);
+int st_plan_style_nearest(const st_plan* plan, int* flags);
+/* The target of flagged style entry `index`: feat [C][m], the style's feature vectors as columns (device memory; a style tap as
+ * it lies in a plan, or several side by side).  Transposed once into S^T [M_pad][C] with zero rows and a bias of -inf in the
+ * padding, so padding never wins.  A set that needs larger buffers than the entry holds allocates new ones; the former stay
+ * the plan's until it is destroyed (st_plan_device_bytes counts them), a smaller or equal set allocates nothing.  Until the call
+ * has succeeded the entry holds no target.  Fails on an entry that is not flagged; st_plan_set_style_target and
+ * st_plan_set_style_quantiles fail on a flagged one. */
+int st_plan_set_style_vectors(st_plan* plan, int index, const float* feat, long long m, void* stream);
+/* Borrows the matches of the last closure for flagged entry `index`: *idx [n] ints of the plan's (device memory), k*(i) in
+ * [0, m), valid until the plan is destroyed and rewritten by every closure. */
+int st_plan_nearest_indices(st_plan* plan, int index, const int** idx, long long* n);
 
 /* ContentLossMSE target (style_transfer.py:425-429): copies feat [512][H/8][W/8] into the plan (a configured plan: the
  * target of content layer 0, shaped like that layer). */
@@ -826,6 +878,30 @@ int st_op_w2_marginal_loss(const float* feat, int channels, long long n, const f
                            float* loss_out, void* stream);
 /* ... grad[i] = upstream[0] * unit_grad[i], i < count; upstream: a DEVICE scalar. */
 int st_op_w2_marginal_loss_backward(const float* unit_grad, long long count, const float* upstream, float* grad, void* stream);
+/* The nearest head of st_plan_set_style_nearest on ONE dense fp32 tensor feat [C][n], by the same kernels: C a multiple of
+ * st_op_nearest_k_chunk() (32), n >= 1 pixels against m >= 1 style vectors.  st_op_nearest_pixel_tile() / _k_tile(): the pixels a
+ * workgroup owns and the style vectors of one k tile (128 each); st_op_nearest_splits(n, m): the splits of the k range, by the
+ * shape alone.
+ * st_op_nearest_prepare: vectors [C][m] -> prepared, st_op_nearest_prepared_floats(C, m) floats of the caller's, 256-byte aligned:
+ * S^T, the bias, the bound on max |S|.
+ * `scratch`: st_op_nearest_scratch_floats(C, n, m) floats of the caller's, 256-byte aligned, per call.
+ * st_op_nearest_search: idx_out [n] = k*(i), score_out [n] (optional) = <f_i, s_k*> - |s_k*|^2 / 2 as the search saw it.
+ * Two calls on the same data give the same bits. */
+int st_op_nearest_k_chunk(void);
+int st_op_nearest_pixel_tile(void);
+int st_op_nearest_k_tile(void);
+int st_op_nearest_splits(long long n, long long m);
+long long st_op_nearest_prepared_floats(int channels, long long m);
+long long st_op_nearest_scratch_floats(int channels, long long n, long long m);
+int st_op_nearest_prepare(const float* vectors, int channels, long long m, float* prepared, void* stream);
+int st_op_nearest_search(const float* feat, int channels, long long n, const float* prepared, long long m, float* scratch, int* idx_out,
+                         float* score_out, void* stream);
+/* loss_out[0] = sum_i |f_i - s_k*(i)|^2 / (C n) at weight 1; idx_out [n] the matches; unit_grad_out [C][n] = d loss / d feat
+ * (autograd: saved on the node) ... */
+int st_op_nearest_loss(const float* feat, int channels, long long n, const float* prepared, long long m, float* scratch, int* idx_out,
+                       float* unit_grad_out, float* loss_out, void* stream);
+/* ... grad[i] = upstream[0] * unit_grad[i], i < count; upstream: a DEVICE scalar. */
+int st_op_nearest_loss_backward(const float* unit_grad, long long count, const float* upstream, float* grad, void* stream);
 /* TVLoss (style_transfer.py:184-195) on a [3][H][W] image, H, W >= 1: the value alone (st_op_tv_loss writes the unit
  * gradient with it) ... */
 int st_op_tv_value(const float* image, int height, int width, float* scratch, float* loss_out, void* stream);

@@ -460,6 +460,9 @@ int st_plan_set_region_style_target(st_plan* p, int region, int index, const flo
     ST_REQUIRE(!p->style_marg[index],
                "st_plan_set_style_target: style layer %d is flagged marginal (st_plan_set_w2_marginal): its target is a quantile function, "
                "set by st_plan_set_style_quantiles", index);
+    ST_REQUIRE(!p->style_near[index],
+               "st_plan_set_style_target: style layer %d is flagged nearest (st_plan_set_style_nearest): its target is a set of style vectors, "
+               "set by st_plan_set_style_vectors", index);
     hipStream_t s = static_cast<hipStream_t>(stream);
     StyleHead& h = region_head_at(p, region, p->style_op[index]);
     if (ensure_style_alloc(p, h, alloc_kind_of(p, index))) return 1;
@@ -483,6 +486,8 @@ int st_plan_set_region_style_target(st_plan* p, int region, int index, const flo
 int st_plan_set_style_quantiles(st_plan* p, int index, const float* q, long long n_q, void* stream) {
     ST_REQUIRE(p && q, "st_plan_set_style_quantiles: null argument");
     ST_REQUIRE(index >= 0 && index < p->n_style, "st_plan_set_style_quantiles: index %d out of range (%d style layers)", index, p->n_style);
+    ST_REQUIRE(!p->style_near[index], "st_plan_set_style_quantiles: style layer %d is flagged nearest (st_plan_set_style_nearest): its target "
+               "is set by st_plan_set_style_vectors", index);
     ST_REQUIRE(p->style_marg[index], "st_plan_set_style_quantiles: style layer %d is not flagged marginal (st_plan_set_w2_marginal): its "
                "target is set by st_plan_set_style_target", index);
     ST_REQUIRE(n_q >= 1, "st_plan_set_style_quantiles: %lld order statistics per channel: at least one", n_q);
@@ -501,6 +506,36 @@ int st_plan_style_quantiles(st_plan* p, int index, float** target, int* channels
                "st_plan_style_quantiles: style layer %d holds no quantile target (st_plan_set_w2_marginal, st_plan_set_style_quantiles)", index);
     *target = h.marg_t;
     *channels = h.n;
+    *n = h.npix_local;
+    return 0;
+}
+
+int st_plan_set_style_vectors(st_plan* p, int index, const float* feat, long long m, void* stream) {
+    ST_REQUIRE(p && feat, "st_plan_set_style_vectors: null argument");
+    ST_REQUIRE(index >= 0 && index < p->n_style, "st_plan_set_style_vectors: index %d out of range (%d style layers)", index, p->n_style);
+    ST_REQUIRE(p->style_near[index], "st_plan_set_style_vectors: style layer %d is not flagged nearest (st_plan_set_style_nearest): its "
+               "target is set by st_plan_set_style_target", index);
+    StyleHead& h = p->head[p->style_op[index]];
+    if (nearest_check_shape("st_plan_set_style_vectors", h.n, h.npix_local, m)) return 1;
+    // (a closure in flight may still read the former set: the buffers are rewritten behind it on the caller's stream)
+    // the entry holds no target until the new set is written
+    h.target_set = false;
+    invalidate_graph(p);
+    if (alloc_head_nearest(h, m, PlanAlloc{p})) return 1;
+    ST_HIP(hipStreamSynchronize(nullptr));
+    if (launch_nearest_prepare(feat, h.n, m, nearest_prepared_of(h.near_prep, h.n, m), static_cast<hipStream_t>(stream))) return 1;
+    h.near_m = m;
+    h.target_set = true;
+    return 0;
+}
+
+int st_plan_nearest_indices(st_plan* p, int index, const int** idx, long long* n) {
+    ST_REQUIRE(p && idx && n, "st_plan_nearest_indices: null argument");
+    ST_REQUIRE(index >= 0 && index < p->n_style, "st_plan_nearest_indices: index %d out of range (%d style layers)", index, p->n_style);
+    const StyleHead& h = p->head[p->style_op[index]];
+    ST_REQUIRE(p->style_near[index] && h.target_set && h.near_idx,
+               "st_plan_nearest_indices: style layer %d holds no matches (st_plan_set_style_nearest, st_plan_set_style_vectors)", index);
+    *idx = h.near_idx;
     *n = h.npix_local;
     return 0;
 }

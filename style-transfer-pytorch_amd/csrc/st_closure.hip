@@ -362,7 +362,15 @@ int ensure_moment_alloc(st_plan* p, StyleHead& h) {
 // launch's partials, 2 C coefficients and a ticket; no Gram workspace, no C x C buffer)
 // (kind 3, internal: a W2 entry flagged marginal, st_plan_set_w2_marginal, holds its C N target and the sort's scratch - the
 // ticket, the partials and two buffers of keys; no C x C buffer, no Newton-Schulz workspace)
+// (kind 4, internal: a W2 entry flagged nearest, st_plan_set_style_nearest, holds N indices here; S^T, the bias, the split partials,
+// the partials and the ticket are sized by the style set and allocated by st_plan_set_style_vectors; no C x C buffer, no
+// Newton-Schulz workspace)
 int ensure_style_alloc(st_plan* p, StyleHead& h, int kind) {
+    if (kind == 4) {
+        if (alloc_head_nearest(h, std::max<long long>(h.near_m, 1), PlanAlloc{p})) return 1;
+        ST_HIP(hipStreamSynchronize(nullptr));
+        return 0;
+    }
     if (kind == 3) {
         if (alloc_head_marginal(h, PlanAlloc{p})) return 1;
         ST_HIP(hipStreamSynchronize(nullptr));

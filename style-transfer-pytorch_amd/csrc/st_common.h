@@ -731,6 +731,41 @@ int launch_resample_quantiles(const float* q, int channels, long long n_in, long
 // the sort, then the residual pass against target [C][n]: grad [C][n] WRITTEN through the permutation, loss_out[0] the weighted term
 int marginal_head_run(const float* feat, int channels, long long n, const float* target, void* scratch, float weight, float* grad,
                       float* loss_out, hipStream_t s);
+// ---- nearest-neighbour feature-matching W2 heads (st_plan_set_style_nearest, st_op_nearest_*; st_nearest.hip) ----
+constexpr int kNearestChunk = 32;                 // channels per K chunk of the search: a head's channel count is a multiple
+constexpr int kNearestPixelTile = 128;            // pixels a workgroup of the search owns
+constexpr int kNearestKTile = 128;                // style vectors per k tile: M is padded to a multiple
+constexpr int kNearestMinTiles = 4;               // k tiles a split owns at least
+long long nearest_m_pad(long long m);
+int nearest_splits(long long n, long long m, int* tiles_per_split);     // by the shape alone
+int nearest_check_shape(const char* who, int channels, long long n, long long m);
+// the style set as the kernels read it, nearest_prepared_floats floats, 256-byte aligned: the bound on max |S|, bias [M_pad], S^T [M_pad][C]
+long long nearest_prepared_floats(int channels, long long m);
+struct NearestPrepared {
+    long long m = 0, m_pad = 0;
+    unsigned int* bound = nullptr;
+    float *bias = nullptr, *st_t = nullptr;
+};
+NearestPrepared nearest_prepared_of(float* prepared, int channels, long long m);
+// per call, nearest_scratch_floats floats, 256-byte aligned: the ticket (zero between launches), a bound for a tap no trunk kernel
+// wrote, the finish pass's partials, one (score, k) per pixel and split
+long long nearest_scratch_floats(int channels, long long n, long long m);
+struct NearestScratch {
+    int splits = 1, tiles_per_split = 1;
+    unsigned int *ticket = nullptr, *bound = nullptr;
+    float *partials = nullptr, *part_score = nullptr;
+    int* part_k = nullptr;
+};
+NearestScratch nearest_scratch_of(float* scratch, int channels, long long n, long long m);
+// vectors [C][m] -> pr: the transpose with zero rows in the padding, bias_k = -|s_k|^2 / 2 (double, rounded once; -inf in the padding), the bound
+int launch_nearest_prepare(const float* vectors, int channels, long long m, const NearestPrepared& pr, hipStream_t s);
+// one (score, k) per pixel and split into sc; feat_bound: the tap's bound word, or null - measured into sc.bound first
+int launch_nearest_search(const float* feat, int channels, long long n, const NearestPrepared& pr, const NearestScratch& sc,
+                          const unsigned int* feat_bound, hipStream_t s);
+// the search, then the finish pass: idx_out [n], score_out [n] (optional), grad [C][n] WRITTEN, loss_out[0] the weighted term
+int nearest_head_run(const float* feat, int channels, long long n, const NearestPrepared& pr, const NearestScratch& sc,
+                     const unsigned int* feat_bound, float weight, int* idx_out, float* score_out, float* grad, float* loss_out,
+                     hipStream_t s);
 // ---- Laplacian loss on pooled images (st_plan_set_laplacian, st_op_laplacian_*; st_laplacian.hip) ----
 constexpr int kMaxLapPools = 4;
 constexpr int kLapBlocks = 1024;                  // workgroups of the residual pass at most: its partials

@@ -35,7 +35,43 @@ struct StyleHead {
     // a W2 entry matched on its exact per-channel marginals (st_plan_set_w2_marginal): the target's quantile functions [n][npix]
     // and the sort's scratch (ticket, partials, two buffers of keys: marginal_scratch_bytes); none of the buffers above
     float *marg_t = nullptr, *marg_scratch = nullptr;
+    // a W2 entry matched on nearest style vectors (st_plan_set_style_nearest): the prepared style set (bound, bias, S^T for near_m
+    // vectors), the search's scratch and the last closure's matches [npix]; near_prep_floats / near_scratch_floats: what the two
+    // buffers hold
+    float *near_prep = nullptr, *near_scratch = nullptr;
+    int* near_idx = nullptr;
+    long long near_m = 0;
+    size_t near_prep_floats = 0, near_scratch_floats = 0;
 };
+
+// what a nearest head needs for m style vectors.  Each buffer is sized by its own function of (C, N, m) and grows when that
+// function asks for more than it holds - the split count, hence the scratch, is not monotone in m.  A buffer that is outgrown
+// stays the allocator's until the plan is destroyed (plans free nothing before that), so a style set that keeps growing
+// accumulates dead device memory; one that shrinks or repeats allocates nothing.  The ticket in front of the scratch is zeroed on
+// the null stream, which the caller synchronises
+template <class Alloc>
+int alloc_head_nearest(StyleHead& h, long long m, Alloc&& alloc) {
+    if (!h.near_idx) {
+        float* idx = nullptr;
+        if (alloc(&idx, (size_t)h.npix_local)) return 1;
+        h.near_idx = reinterpret_cast<int*>(idx);
+    }
+    const size_t prep = (size_t)nearest_prepared_floats(h.n, m), scratch = (size_t)nearest_scratch_floats(h.n, h.npix_local, m);
+    if (prep > h.near_prep_floats) {
+        h.near_prep = nullptr;
+        h.near_prep_floats = 0;
+        if (alloc(&h.near_prep, prep)) return 1;
+        h.near_prep_floats = prep;
+    }
+    if (scratch > h.near_scratch_floats) {
+        h.near_scratch = nullptr;
+        h.near_scratch_floats = 0;
+        if (alloc(&h.near_scratch, scratch)) return 1;
+        ST_HIP(hipMemset(h.near_scratch, 0, 16));
+        h.near_scratch_floats = scratch;
+    }
+    return 0;
+}
 
 // what a marginal head needs; the ticket in front of its scratch is zeroed on the null stream, which the caller synchronises
 template <class Alloc>

@@ -302,6 +302,9 @@ int st_plan_set_style_mask(st_plan* p, const float* mask, void* stream) {
     for (int j = 0; j < p->n_style; ++j)
         ST_REQUIRE(!p->style_marg[j], "st_plan_set_style_mask: style layer %d is flagged marginal (st_plan_set_w2_marginal), which takes no "
                    "style mask: clear the flag first", j);
+    for (int j = 0; j < p->n_style; ++j)
+        ST_REQUIRE(!p->style_near[j], "st_plan_set_style_mask: style layer %d is flagged nearest (st_plan_set_style_nearest), which takes no "
+                   "style mask: clear the flag first", j);
     ST_REQUIRE(!p->n_regions, "st_plan_set_style_mask: %d style regions are in force on this plan (st_plan_set_style_regions): "
                "clear them first", p->n_regions);
     constexpr size_t kPartials = kPyramidPartials;
@@ -409,6 +412,9 @@ int st_plan_set_style_regions(st_plan* p, int n_regions, const float* const* mas
     hipStream_t s = static_cast<hipStream_t>(stream);
     for (int j = 0; n_regions != 0 && j < p->n_style; ++j)
         ST_REQUIRE(!p->style_marg[j], "st_plan_set_style_regions: style layer %d is flagged marginal (st_plan_set_w2_marginal), which takes "
+                   "no style regions: clear the flag first", j);
+    for (int j = 0; n_regions != 0 && j < p->n_style; ++j)
+        ST_REQUIRE(!p->style_near[j], "st_plan_set_style_regions: style layer %d is flagged nearest (st_plan_set_style_nearest), which takes "
                    "no style regions: clear the flag first", j);
     // no regions are in force until every one of them is accepted
     p->n_regions = 0;

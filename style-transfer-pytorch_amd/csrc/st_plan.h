@@ -145,6 +145,10 @@ struct st_plan {
     // never together with style_diag, a custom eps, a style mask or regions.  Any set flag runs the general closure; either kinds
     // setter and st_plan_set_taps clear them.
     int style_marg[16] = {};
+    // A W2 entry matched on nearest style vectors (st_plan_set_style_nearest, st_nearest.hip): a flag per LISTED style entry, never
+    // together with style_diag, style_marg, a custom eps, a style mask or regions.  Any set flag runs the general closure; either
+    // kinds setter and st_plan_set_taps clear them.
+    int style_near[16] = {};
     float* kind_scratch = nullptr;                   // non-default kinds: [2 kStreamBlocks] per-block (sum d^2, sum |d|) of the
                                                      // term in flight, then [2] per term: sum d^2, sum |d| + eps (kind_totals)
     st::StyleHead head[st::kNumOps];                 // n / npix / npix_local of all 17 filled at create, buffers on first use;
@@ -389,7 +393,7 @@ bool targets_ready(const st_plan* p);
 float* loss_terms(st_plan* p);        // the array the closure's weighted terms go to, in SumLoss order
 float style_eps_of(const st_plan* p, int j);   // effective eps of style entry j / content entry i (mse: -1)
 float content_eps_of(const st_plan* p, int i);
-int alloc_kind_of(const st_plan* p, int j);    // what ensure_style_alloc is asked for entry j: its kind, 2 for a diagonal W2 entry, 3 for a marginal one
+int alloc_kind_of(const st_plan* p, int j);    // what ensure_style_alloc is asked for entry j: its kind, 2 for a diagonal W2 entry, 3 for a marginal one, 4 for a nearest one
 
 // ---- st_laplacian.hip
 // the plan's Laplacian terms on `image`, behind the TV launch that wrote `grad` and `slot`: each pool size's term onto the

@@ -62,6 +62,11 @@
 // So does a W2 entry flagged marginal (st_plan_set_w2_marginal, st_sort.hip): its head is the segmented sort of the tap's rows and
 // the residual pass against the target's quantile functions, which writes dF to the seed buffer through the permutation.  Such an
 // entry takes no style mask and no regions.
+//
+// So does a W2 entry flagged nearest (st_plan_set_style_nearest, st_nearest.hip): its head is the fused search - the scores of the
+// tap's pixels against the style's feature vectors, reduced to one match per pixel without ever being written - and the finish
+// pass, which writes dF = w (2 / (C N)) (f - s_k*) to the seed buffer and keeps the matches (st_plan_nearest_indices).  Such an
+// entry takes no style mask and no regions either.
 #include <algorithm>
 #include <cmath>
 
@@ -118,6 +123,11 @@ static bool any_marginal(const st_plan* p) {
     for (int j = 0; j < p->n_style; ++j) any = any || p->style_marg[j] != 0;
     return any;
 }
+static bool any_nearest(const st_plan* p) {
+    bool any = false;
+    for (int j = 0; j < p->n_style; ++j) any = any || p->style_near[j] != 0;
+    return any;
+}
 static bool default_eps(const st_plan* p) {
     bool ok = true;
     for (int i = 0; i < p->n_content; ++i) ok = ok && p->content_eps[i] < 0.f;
@@ -128,7 +138,8 @@ static bool default_eps(const st_plan* p) {
 bool general_taps(const st_plan* p) {
     static Option force("ST_GENERAL_TAPS", 0);
     return !p->strip && (!p->reference_taps || !default_kinds(p) || !default_eps(p) || p->style_mask || p->n_regions > 0 ||
-                         p->content_mask || p->tv_mask || p->n_lap > 0 || any_diagonal(p) || any_marginal(p) || force.get() != 0);
+                         p->content_mask || p->tv_mask || p->n_lap > 0 || any_diagonal(p) || any_marginal(p) || any_nearest(p) ||
+                         force.get() != 0);
 }
 
 float style_eps_of(const st_plan* p, int j) {
@@ -139,7 +150,7 @@ float content_eps_of(const st_plan* p, int i) {
     return p->content_kind[i] == 0 ? -1.f : p->content_eps[i] >= 0.f ? p->content_eps[i] : kScaledMseEps;
 }
 
-int alloc_kind_of(const st_plan* p, int j) { return p->style_marg[j] ? 3 : p->style_diag[j] ? 2 : p->style_kind[j]; }
+int alloc_kind_of(const st_plan* p, int j) { return p->style_near[j] ? 4 : p->style_marg[j] ? 3 : p->style_diag[j] ? 2 : p->style_kind[j]; }
 
 int closure_top_op(const st_plan* p) {
     if (!general_taps(p)) return kNumOps - 1;
@@ -217,6 +228,17 @@ int marginal_head(st_plan* p, const HeadSite& at, float* seed, hipStream_t s) {
     return marginal_head_run(at.tap->y, h.n, h.npix_local, h.marg_t, h.marg_scratch, at.weight, seed, at.loss, s);
 }
 
+// A W2 entry flagged nearest (st_plan_set_style_nearest, st_nearest.hip): the search against the style set, then the finish pass,
+// which writes dF to the seed, the matches to the head and the weighted term to the entry's slot.  No mask, no eps.  The tap's
+// bound word where the producing convolution leaves one (fp16x3 trunks), otherwise measured by the search's launcher.
+int nearest_head(st_plan* p, const HeadSite& at, float* seed, hipStream_t s) {
+    const StyleHead& h = *at.h;
+    const NearestPrepared pr = nearest_prepared_of(h.near_prep, h.n, h.near_m);
+    const NearestScratch sc = nearest_scratch_of(h.near_scratch, h.n, h.npix_local, h.near_m);
+    const unsigned int* bound = p->net->conv_elem == 1 ? at.tap->y_amax : nullptr;
+    return nearest_head_run(at.tap->y, h.n, h.npix_local, pr, sc, bound, at.weight, h.near_idx, nullptr, seed, at.loss, s);
+}
+
 // Style regions in force: the heads of every listed entry, in `order`, one per region in region order.  dF_r's pixel columns
 // times m_r: region 0 in place on the seed it wrote (the masked plan's launches), region r >= 1 from the scratch buffer ONTO the
 // seed.  Then each entry's term from its regions' terms.
@@ -230,6 +252,7 @@ int region_heads(st_plan* p, const int* order, bool* styled, hipStream_t s) {
         for (int r = 0; r < regions; ++r) {
             const HeadSite at = region_head_site(p, j, r);
             ST_REQUIRE(!p->style_marg[j], "style layer %d is flagged marginal (st_plan_set_w2_marginal): it takes no style regions", j);
+            ST_REQUIRE(!p->style_near[j], "style layer %d is flagged nearest (st_plan_set_style_nearest): it takes no style regions", j);
             if (p->style_diag[j]) {            // region 0 writes the seed, region r >= 1 adds onto it: no scratch buffer
                 if (diag_head(p, at, seed, r > 0, s)) return 1;
                 continue;
@@ -296,6 +319,11 @@ int general_loss_and_grad(st_plan* p, const float* image, float* grad_out, float
     } else {
         for (int k = 0; k < ns; ++k) {
             const HeadSite at = general_head_site(p, order[k]);
+            if (p->style_near[order[k]]) {
+                if (nearest_head(p, at, at.grad, s)) return 1;
+                styled[p->style_op[order[k]]] = true;
+                continue;
+            }
             if (p->style_marg[order[k]]) {
                 if (marginal_head(p, at, at.grad, s)) return 1;
                 styled[p->style_op[order[k]]] = true;
@@ -432,7 +460,7 @@ int st_plan_set_taps(st_plan* p, int n_content, const int* content_layers, int n
         p->content_kind[i] = ckind;
         p->style_kind[i] = skind;
         p->content_eps[i] = p->style_eps[i] = -1.f;
-        p->style_diag[i] = p->style_marg[i] = 0;
+        p->style_diag[i] = p->style_marg[i] = p->style_near[i] = 0;
         if (keep_weights) continue;
         p->content_weight[i] = i < n_content ? 0.015f / (float)n_content : 0.f;
         p->style_weight[i] = i >= n_style ? 0.f : ref ? kStyleWeight[i] : 1.f / (float)n_style;
@@ -455,7 +483,7 @@ int apply_loss_kinds(st_plan* p, const int* ck, const int* sk) {
         p->content_kind[i] = ck[i];
         p->style_kind[i] = sk[i];
         p->content_eps[i] = p->style_eps[i] = -1.f;      // an eps belongs to a module of one kind: set it after the kinds
-        p->style_diag[i] = p->style_marg[i] = 0;         // ... and so do the diagonal and marginal flags of a W2 entry
+        p->style_diag[i] = p->style_marg[i] = p->style_near[i] = 0;      // ... and so do the diagonal, marginal and nearest flags of a W2 entry
     }
     // a target is kept in the form its kind reads (a root, or a Gram matrix): as after st_plan_set_taps, every target set
     // before is gone, every bound word is dealt again and nothing built on the former terms survives.  The lists and all
@@ -549,6 +577,9 @@ int st_plan_set_loss_eps(st_plan* p, const float* content_eps, const float* styl
     for (int j = 0; j < p->n_style; ++j)
         ST_REQUIRE(!p->style_marg[j] || se[j] < 0.f,
                    "st_plan_set_loss_eps: style layer %d is flagged marginal (st_plan_set_w2_marginal), whose term has no eps", j);
+    for (int j = 0; j < p->n_style; ++j)
+        ST_REQUIRE(!p->style_near[j] || se[j] < 0.f,
+                   "st_plan_set_loss_eps: style layer %d is flagged nearest (st_plan_set_style_nearest), whose term has no eps", j);
     std::copy(ce, ce + 16, p->content_eps);
     std::copy(se, se + 16, p->style_eps);
     // a W2 target is kept as the root of cov_t + eps I: every target set before is gone
@@ -566,6 +597,8 @@ int st_plan_set_w2_diagonal(st_plan* p, const int* flags) {
                    "st_plan_set_w2_diagonal: style layer %d is of kind gram (StyleLoss): only a w2 layer's covariances can be diagonal", j);
         ST_REQUIRE(flags[j] == 0 || !p->style_marg[j],
                    "st_plan_set_w2_diagonal: style layer %d is flagged marginal (st_plan_set_w2_marginal): a layer takes one of the two", j);
+        ST_REQUIRE(flags[j] == 0 || !p->style_near[j],
+                   "st_plan_set_w2_diagonal: style layer %d is flagged nearest (st_plan_set_style_nearest): a layer takes one of the two", j);
         fl[j] = flags[j];
         any = any || fl[j] != 0;
     }
@@ -598,6 +631,8 @@ int st_plan_set_w2_marginal(st_plan* p, const int* flags) {
                    "st_plan_set_w2_marginal: style layer %d is flagged diagonal (st_plan_set_w2_diagonal): a layer takes one of the two", j);
         ST_REQUIRE(flags[j] == 0 || p->style_eps[j] < 0.f,
                    "st_plan_set_w2_marginal: style layer %d has a custom eps (st_plan_set_loss_eps); the marginal term has no eps", j);
+        ST_REQUIRE(flags[j] == 0 || !p->style_near[j],
+                   "st_plan_set_w2_marginal: style layer %d is flagged nearest (st_plan_set_style_nearest): a layer takes one of the two", j);
         fl[j] = flags[j];
         any = any || fl[j] != 0;
     }
@@ -614,6 +649,41 @@ int st_plan_set_w2_marginal(st_plan* p, const int* flags) {
 int st_plan_w2_marginal(const st_plan* p, int* flags) {
     ST_REQUIRE(p && flags, "st_plan_w2_marginal: null argument");
     for (int j = 0; j < p->n_style; ++j) flags[j] = p->style_marg[j];
+    return 0;
+}
+
+int st_plan_set_style_nearest(st_plan* p, const int* flags) {
+    ST_REQUIRE(p, "st_plan_set_style_nearest: null plan");
+    int fl[16] = {};
+    bool any = false;
+    for (int j = 0; flags && j < p->n_style; ++j) {
+        ST_REQUIRE(flags[j] == 0 || flags[j] == 1, "st_plan_set_style_nearest: flag %d of style layer %d: 0 or 1", flags[j], j);
+        ST_REQUIRE(flags[j] == 0 || p->style_kind[j] == 0,
+                   "st_plan_set_style_nearest: style layer %d is of kind gram (StyleLoss): only a w2 layer can be matched on nearest vectors", j);
+        ST_REQUIRE(flags[j] == 0 || !p->style_diag[j],
+                   "st_plan_set_style_nearest: style layer %d is flagged diagonal (st_plan_set_w2_diagonal): a layer takes one of the two", j);
+        ST_REQUIRE(flags[j] == 0 || !p->style_marg[j],
+                   "st_plan_set_style_nearest: style layer %d is flagged marginal (st_plan_set_w2_marginal): a layer takes one of the two", j);
+        ST_REQUIRE(flags[j] == 0 || p->style_eps[j] < 0.f,
+                   "st_plan_set_style_nearest: style layer %d has a custom eps (st_plan_set_loss_eps); the nearest term has no eps", j);
+        ST_REQUIRE(flags[j] == 0 || p->head[p->style_op[j]].n % kNearestChunk == 0,
+                   "st_plan_set_style_nearest: style layer %d has %d channels: a multiple of %d", j, p->head[p->style_op[j]].n, kNearestChunk);
+        fl[j] = flags[j];
+        any = any || fl[j] != 0;
+    }
+    ST_REQUIRE(!p->strip || !any, "st_plan_set_style_nearest: strip plans run full W2 heads only");
+    ST_REQUIRE(!any || (!p->style_mask && !p->n_regions),
+               "st_plan_set_style_nearest: a style mask or style regions are in force on this plan; masked matching is not implemented - "
+               "clear them first");
+    std::copy(fl, fl + 16, p->style_near);
+    // a target is kept in the form its head reads - a set of style vectors, or a root: every target set before is gone
+    drop_targets(p);
+    return 0;
+}
+
+int st_plan_style_nearest(const st_plan* p, int* flags) {
+    ST_REQUIRE(p && flags, "st_plan_style_nearest: null argument");
+    for (int j = 0; j < p->n_style; ++j) flags[j] = p->style_near[j];
     return 0;
 }
 

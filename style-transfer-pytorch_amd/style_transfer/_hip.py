@@ -93,6 +93,10 @@ def _declare(lib):
         'st_plan_w2_marginal': (i32, [vp, ctypes.POINTER(i32)]),
         'st_plan_set_style_quantiles': (i32, [vp, i32, vp, i64, vp]),
         'st_plan_style_quantiles': (i32, [vp, i32, pp, ip, ctypes.POINTER(i64)]),
+        'st_plan_set_style_nearest': (i32, [vp, ctypes.POINTER(i32)]),
+        'st_plan_style_nearest': (i32, [vp, ctypes.POINTER(i32)]),
+        'st_plan_set_style_vectors': (i32, [vp, i32, vp, i64, vp]),
+        'st_plan_nearest_indices': (i32, [vp, i32, pp, ctypes.POINTER(i64)]),
         'st_plan_set_content_target_at': (i32, [vp, i32, vp, vp]),
         'st_plan_term_losses': (i32, [vp, pp, ip]),
         'st_plan_loss_and_grad': (i32, [vp, vp, vp, vp, vp]),
@@ -165,6 +169,16 @@ def _declare(lib):
         'st_op_resample_quantiles': (i32, [vp, i32, i64, i64, vp, vp]),
         'st_op_w2_marginal_loss': (i32, [vp, i32, i64, vp, vp, vp, vp, vp]),
         'st_op_w2_marginal_loss_backward': (i32, [vp, i64, vp, vp, vp]),
+        'st_op_nearest_k_chunk': (i32, []),
+        'st_op_nearest_pixel_tile': (i32, []),
+        'st_op_nearest_k_tile': (i32, []),
+        'st_op_nearest_splits': (i32, [i64, i64]),
+        'st_op_nearest_prepared_floats': (i64, [i32, i64]),
+        'st_op_nearest_scratch_floats': (i64, [i32, i64, i64]),
+        'st_op_nearest_prepare': (i32, [vp, i32, i64, vp, vp]),
+        'st_op_nearest_search': (i32, [vp, i32, i64, vp, i64, vp, vp, vp, vp]),
+        'st_op_nearest_loss': (i32, [vp, i32, i64, vp, i64, vp, vp, vp, vp, vp]),
+        'st_op_nearest_loss_backward': (i32, [vp, i64, vp, vp, vp]),
         'st_op_tv_value': (i32, [vp, i32, i32, vp, vp, vp]),
         'st_op_tv_loss_backward': (i32, [vp, i32, i32, vp, vp, vp]),
         'st_op_laplacian_scratch_floats': (i64, [i32, i32, i32, i32]),
@@ -456,6 +470,35 @@ class Plan:
         _check(self.lib.st_plan_w2_marginal(self.handle, fa))
         return tuple(bool(v) for v in fa[:n])
 
+    def set_style_nearest(self, flags=None):
+        """Match a 'w2' style layer on nearest style vectors (st_plan_set_style_nearest): None or False (no layer), True (every
+        layer of the list - all must be 'w2') or a sequence with one bool per style layer.  A flagged layer's term is the mean
+        over channels and pixels of ``|f_i - s_k*(i)|^2`` with ``s_k*(i)`` the closest of the style's feature vectors
+        (``set_style_vectors``): one fused search - ``2 C N M`` flop, no N x M matrix - and one finish pass, no C x C work.  Any
+        set flag runs the general closure; drops every target.  Refused together with a diagonal or marginal flag or a custom
+        eps on the same layer, and while a style mask or regions are set.  Either kinds setter and ``set_taps`` clear the
+        flags: kinds, eps, diagonal, marginal, then this, then the weights and targets."""
+        n = len(self.style_layers)
+        if flags is None or isinstance(flags, (bool, int)):
+            flags = [bool(flags)] * n
+        flags = list(flags)
+        if len(flags) != n:
+            raise ValueError(f'{len(flags)} nearest flags for {n} style layers: one per layer')
+        for v in flags:
+            if v not in (0, 1, False, True):
+                raise ValueError(f'nearest flag {v!r}: must be a bool')
+        fa = (ctypes.c_int * max(n, 1))(*[int(v) for v in flags])
+        with torch.cuda.device(self.device):
+            _check(self.lib.st_plan_set_style_nearest(self.handle, fa))
+
+    @property
+    def style_nearest(self):
+        """The nearest flag of each style layer, a tuple of bools (st_plan_style_nearest)."""
+        n = len(self.style_layers)
+        fa = (ctypes.c_int * max(n, 1))()
+        _check(self.lib.st_plan_style_nearest(self.handle, fa))
+        return tuple(bool(v) for v in fa[:n])
+
     def _layer_values(self, entry, ctype):
         ca, sa = (ctype * max(len(self.content_layers), 1))(), (ctype * max(len(self.style_layers), 1))()
         _check(entry(self.handle, ca, sa))
@@ -599,6 +642,32 @@ class Plan:
         with torch.cuda.device(self.device):
             _copy_d2d(out, data.value)
         return out
+
+    def set_style_vectors(self, index, vectors):
+        """The target of a style layer flagged by ``set_style_nearest``: ``vectors`` [C, M] (or [C, h, w]), the style's feature
+        vectors as columns - a style tap (``feature(layer)[0]``), or several concatenated along the columns
+        (st_plan_set_style_vectors).  M need not be this plan's pixel count."""
+        vectors = vectors.to(device=self.device, dtype=torch.float32)
+        if vectors.ndim == 3:
+            vectors = vectors.flatten(1)
+        if vectors.ndim != 2:
+            raise ValueError(f'style vectors of shape {tuple(vectors.shape)}: [C, M]')
+        vectors = vectors.contiguous()
+        with torch.cuda.device(self.device):
+            _check(self.lib.st_plan_set_style_vectors(self.handle, int(index), _ptr(vectors), int(vectors.shape[1]), _stream()))
+
+    def nearest_indices(self, layer):
+        """Copy of the last closure's matches of the flagged style layer ``layer`` (a features index of ``style_layers``), [N]
+        int64: the style vector each pixel of the tap was matched to (st_plan_nearest_indices)."""
+        if int(layer) not in self.style_layers:
+            raise ValueError(f'features[{int(layer)}] is not one of the style layers {tuple(self.style_layers)}')
+        index = list(self.style_layers).index(int(layer))
+        data, n = ctypes.c_void_p(), ctypes.c_longlong()
+        _check(self.lib.st_plan_nearest_indices(self.handle, index, ctypes.byref(data), ctypes.byref(n)))
+        out = torch.empty((n.value,), device=self.device, dtype=torch.int32)
+        with torch.cuda.device(self.device):
+            _copy_d2d(out, data.value)
+        return out.to(torch.int64)
 
     def set_style_mask(self, mask):
         """A spatial mask for the style statistics (st_plan_set_style_mask): a [height, width] tensor with values in [0, 1]
@@ -1407,6 +1476,67 @@ def op_w2_marginal_loss_backward(unit_grad, upstream):
     grad = torch.empty(unit_grad.shape, device=unit_grad.device, dtype=torch.float32)
     with torch.cuda.device(unit_grad.device):
         _check(lib.st_op_w2_marginal_loss_backward(_ptr(unit_grad), unit_grad.numel(), _ptr(upstream), _ptr(grad), _stream()))
+    return grad
+
+
+def nearest_geometry():
+    """(K chunk, pixel tile, k tile) of the nearest-neighbour search kernel (st_op_nearest_k_chunk / _pixel_tile / _k_tile)."""
+    lib = load_library()
+    return int(lib.st_op_nearest_k_chunk()), int(lib.st_op_nearest_pixel_tile()), int(lib.st_op_nearest_k_tile())
+
+
+def nearest_splits(n, m):
+    """The splits of the k range the search runs for n pixels against m style vectors (st_op_nearest_splits): by the shape alone."""
+    return int(load_library().st_op_nearest_splits(int(n), int(m)))
+
+
+def op_nearest_prepare(vectors):
+    """The style set [C, M] as the search kernels read it (st_op_nearest_prepare): an opaque fp32 buffer for ``op_nearest_*``."""
+    lib = load_library()
+    c, m = int(vectors.shape[0]), int(vectors.shape[1])
+    prepared = torch.empty(max(int(lib.st_op_nearest_prepared_floats(c, m)), 1), device=vectors.device, dtype=torch.float32)
+    with torch.cuda.device(vectors.device):
+        _check(lib.st_op_nearest_prepare(_ptr(vectors), c, m, _ptr(prepared), _stream()))
+    return prepared
+
+
+def _nearest_scratch(x, c, n, m):
+    return torch.empty(max(int(load_library().st_op_nearest_scratch_floats(c, n, m)), 4), device=x.device, dtype=torch.float32)
+
+
+def op_nearest_search(x, prepared, m):
+    """(indices [N] int64, best scores [N] fp32) of a [C, N] matrix or a [..., C, h, w] tensor (one image) against a prepared
+    set of m style vectors (st_op_nearest_search): ``argmax_k <f_i, s_k> - |s_k|^2 / 2``, ties to the lowest k."""
+    lib = load_library()
+    c, n = _rows(x)
+    scratch = _nearest_scratch(x, c, n, m)
+    idx = torch.empty((n,), device=x.device, dtype=torch.int32)
+    score = torch.empty((n,), device=x.device, dtype=torch.float32)
+    with torch.cuda.device(x.device):
+        _check(lib.st_op_nearest_search(_ptr(x), c, n, _ptr(prepared), int(m), _ptr(scratch), ctypes.c_void_p(idx.data_ptr()),
+                                        _ptr(score), _stream()))
+    return idx.to(torch.int64), score
+
+
+def op_nearest_loss(x, prepared, m):
+    """(the nearest-neighbour loss [0-dim], its gradient at weight 1 shaped like x, the matches [N] int64) - st_op_nearest_loss."""
+    lib = load_library()
+    c, n = _rows(x)
+    scratch = _nearest_scratch(x, c, n, m)
+    idx = torch.empty((n,), device=x.device, dtype=torch.int32)
+    loss = torch.empty((), device=x.device, dtype=torch.float32)
+    unit = torch.empty(x.shape, device=x.device, dtype=torch.float32)
+    with torch.cuda.device(x.device):
+        _check(lib.st_op_nearest_loss(_ptr(x), c, n, _ptr(prepared), int(m), _ptr(scratch), ctypes.c_void_p(idx.data_ptr()), _ptr(unit),
+                                      _ptr(loss), _stream()))
+    return loss, unit, idx.to(torch.int64)
+
+
+def op_nearest_loss_backward(unit_grad, upstream):
+    lib = load_library()
+    grad = torch.empty(unit_grad.shape, device=unit_grad.device, dtype=torch.float32)
+    with torch.cuda.device(unit_grad.device):
+        _check(lib.st_op_nearest_loss_backward(_ptr(unit_grad), unit_grad.numel(), _ptr(upstream), _ptr(grad), _stream()))
     return grad
 
 

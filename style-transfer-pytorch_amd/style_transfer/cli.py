@@ -313,6 +313,15 @@ def build_parser():
                         "against the style's: the histogram loss in its exact form; a segmented sort per layer and iteration): "
                         "1 for every 'w2' layer, or a comma-separated list with one flag per style layer, e.g. '0,0,0,1,1' "
                         "(default 0); not together with --style-diagonal on the same layer, style masks or regions")
+    p.add_argument('--style-nearest', type=_diagonal_flags, default=False, metavar='{0,1}[,...]',
+                   help="match the 'w2' style layers on nearest style vectors (every pixel's feature vector against the closest "
+                        "feature vector of the style images: the MRF / neural-neighbour style loss; one fused search per layer "
+                        "and iteration): 1 for every 'w2' layer, or a comma-separated list with one flag per style layer, e.g. "
+                        "'0,0,0,1,1' (default 0); not together with --style-diagonal or --style-marginal on the same layer, "
+                        "style masks or regions")
+    p.add_argument('--style-nearest-samples', type=_positive_int, default=None, metavar='INT',
+                   help='keep at most INT evenly spaced feature vectors of every style image per --style-nearest layer (the '
+                        'search costs 2 C N M flop per iteration: this is what makes a shallow layer affordable; default: all)')
     p.add_argument('--style-mask', type=str, default=None, metavar='PATH',
                    help='an image (read as greyscale, white = 1) saying which pixels of the output take the style; it is '
                         'resized to every scale')
@@ -353,8 +362,19 @@ def _loss_names(choices):
     return parse
 
 
+def _positive_int(text):
+    """argparse type of --style-nearest-samples: an int >= 1."""
+    try:
+        value = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f'{text!r}: an integer >= 1') from None
+    if value < 1:
+        raise argparse.ArgumentTypeError(f'{text!r}: an integer >= 1')
+    return value
+
+
 def _diagonal_flags(text):
-    """argparse type of --style-diagonal / --style-marginal: one flag stays the bool, a comma-separated list becomes the list of bools."""
+    """argparse type of --style-diagonal / --style-marginal / --style-nearest: one flag stays the bool, a comma-separated list becomes the list of bools."""
     items = text.split(',')
     for item in items:
         if item not in ('0', '1'):
@@ -414,11 +434,12 @@ def apply_style_masks(st, args):
 
 
 def apply_loss_kinds(st, args):
-    """--content-loss / --style-loss / --content-eps / --style-eps / --style-diagonal / --style-marginal onto the StyleTransfer attributes that stylize() reads."""
+    """--content-loss / --style-loss / --content-eps / --style-eps / --style-diagonal / --style-marginal / --style-nearest / --style-nearest-samples onto the StyleTransfer attributes that stylize() reads."""
     st.content_loss, st.style_loss = args.content_loss, args.style_loss
     st.content_eps, st.style_eps = args.content_eps, args.style_eps
     st.style_diagonal = args.style_diagonal
     st.style_marginal = args.style_marginal
+    st.style_nearest, st.style_nearest_samples = args.style_nearest, args.style_nearest_samples
     return st
 
 

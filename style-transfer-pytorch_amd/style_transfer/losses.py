@@ -13,6 +13,9 @@ form of ``st_plan_set_w2_diagonal``'s term - one dense fp32 HIP tensor, any chan
 st_op_w2_diag_loss_backward.
 ``StyleLossW2Marginal`` is the module form of ``st_plan_set_w2_marginal``'s term: per channel the sorted tap against the style's
 sorted tap - one dense fp32 HIP tensor, any channel count, runs st_op_w2_marginal_loss / st_op_w2_marginal_loss_backward.
+``StyleLossNearest`` is the module form of ``st_plan_set_style_nearest``'s term: every feature vector of the input against the
+closest of the style's feature vectors - one dense fp32 HIP tensor whose channel count is a multiple of 32 runs st_op_nearest_loss /
+st_op_nearest_loss_backward.
 
 Native dispatch.  On an ELIGIBLE tensor (``eligible`` below: one dense fp32 tensor on a HIP device, batch 1 or absent, 64 /
 128 / 256 / 512 channels for the style modules, the module's buffers beside it in fp32) the five loss modules run in the
@@ -64,9 +67,10 @@ class native:
         native.enabled, native.precision = self._former
 
 
-# calls that went to the library, by kind ('w2', 'gram', 'mse', 'scaled_mse', 'tv', 'laplacian', 'w2_diag', 'w2_marginal', 'moments'): the native indicator of the
+# calls that went to the library, by kind ('w2', 'gram', 'mse', 'scaled_mse', 'tv', 'laplacian', 'w2_diag', 'w2_marginal', 'nearest', 'moments'): the native indicator of the
 # modules that hold no head
 native_calls = {}
+_prepared_sets = weakref.WeakKeyDictionary()       # StyleLossNearest module -> (target, version, its prepared style set), kept off the module as the heads are
 _heads = weakref.WeakKeyDictionary()       # module -> its _hip.Head (no module attribute: deepcopy / pickle / state_dict never see it)
 _target_heads = {}                         # get_target's moments-only heads (the static helpers have no module), the six most
                                            # recent shapes; release_target_heads() frees them
@@ -108,6 +112,12 @@ def eligible(input, kind, buffers=()):
         if not (_one_dense_fp32(input, 3) and input.ndim in (3, 4) and input.shape[-2] * input.shape[-1] < 1 << 32):
             return False
         sizes = (input.shape[-3] * input.shape[-2] * input.shape[-1],) * len(buffers)
+    elif kind == 'nearest':
+        # (a channel count that is a multiple of the search kernel's K chunk; buffers: none)
+        if not (_one_dense_fp32(input, 3) and input.ndim in (3, 4) and input.shape[-3] >= 32 and input.shape[-3] % 32 == 0 and
+                input.shape[-2] * input.shape[-1] < 1 << 31):
+            return False
+        sizes = ()
     elif kind == 'tv':
         if not (_one_dense_fp32(input, 3) and input.ndim in (3, 4) and input.shape[-3] == 3 and input.numel() < 1 << 31):
             return False
@@ -324,6 +334,30 @@ class _W2MarginalLoss(torch.autograd.Function):
             return _torch_vjp(ctx.torch_forward, input, grad_output), None, None
         grad = _hip.op_w2_marginal_loss_backward(unit, grad_output.contiguous())
         return grad.view(input.shape), None, None
+
+
+class _NearestLoss(torch.autograd.Function):
+    """StyleLossNearest.forward: st_op_nearest_loss; the gradient at weight 1 - written by the finish pass with the matches held
+    constant - stays on the node for st_op_nearest_loss_backward."""
+
+    @staticmethod
+    def forward(ctx, input, module, prepared, m):
+        from . import _hip
+        loss, unit, _ = _hip.op_nearest_loss(_dense(input), prepared, m)
+        _count('nearest')
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(input, unit)
+            ctx.torch_forward = module._forward_torch
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        from . import _hip
+        input, unit = ctx.saved_tensors
+        if torch.is_grad_enabled():
+            return _torch_vjp(ctx.torch_forward, input, grad_output), None, None, None
+        grad = _hip.op_nearest_loss_backward(unit, grad_output.contiguous())
+        return grad.view(input.shape), None, None, None
 
 
 class _TVLoss(torch.autograd.Function):
@@ -643,6 +677,77 @@ class StyleLossW2Marginal(nn.Module):
         n = input.shape[-2] * input.shape[-1]
         values = torch.sort(input.flatten(-2) + 0.0, dim=-1, stable=True).values
         return torch.mean((values - self.resample(self.target, n)) ** 2)
+
+
+class StyleLossNearest(nn.Module):
+    """Nearest-neighbour feature matching: every feature vector ``f_i`` of the input against the closest of a style tap's
+    feature vectors, ``mean_i,c (f_i - s_k*(i))^2`` with ``k*(i) = argmin_k |f_i - s_k|^2`` (ties: the lowest k) - the MRF /
+    neural-neighbour family of style losses (Li & Wand's CNNMRF, Kolkin et al.'s NNST) in its L2 form, the one-sided Chamfer
+    distance from the input to the style set.  Not in the reference; include/st_amd.h (st_plan_set_style_nearest) fixes the
+    semantics: the match is a constant of the gradient (the a.e. derivative of the minimum), there is no eps, and nothing is
+    resampled - ``target`` = [C, M] with any M (``get_target``).  The cost is ``2 C N M`` flop per call.  The torch path serves
+    any device, dtype and batch, chunked over the pixels so that no N x M matrix exists; one dense fp32 HIP tensor whose channel
+    count is a multiple of 32 runs in the library (st_nearest.hip: one fused search, which writes no score, and one finish
+    pass; the search runs in fp16x3, so a match is optimal up to that arithmetic)."""
+
+    chunk = 4096        # pixels per block of the torch path's distance matrix
+
+    def __init__(self, target):
+        super().__init__()
+        if target.ndim != 2:
+            raise ValueError(f'target of shape {tuple(target.shape)}: [C, M], the style feature vectors as columns')
+        self.register_buffer('target', target)
+
+    @staticmethod
+    def get_target(target):
+        """The flattened features, [..., C, h w]: every pixel's feature vector as a column.  Several style images give the
+        union of their vectors: concatenate along the last axis."""
+        return target.flatten(-2)
+
+    @staticmethod
+    def match(feat, target, chunk=4096):
+        """k*(i) for feat [..., C, N] against target [C, M], [..., N] int64: the arg-min of ``|f_i - s_k|^2`` evaluated as
+        ``|s_k|^2 / 2 - <f_i, s_k>``, the first minimum."""
+        half = 0.5 * (target * target).sum(0)
+        out = []
+        for start in range(0, feat.shape[-1], chunk):
+            f = feat[..., start:start + chunk]
+            out.append(_first_argmin(half[:, None] - torch.einsum('ck,...cn->...kn', target, f), dim=-2))
+        return torch.cat(out, dim=-1)
+
+    def _prepared(self):
+        """The target as the kernels read it, made once per (target buffer, version); kept beside the module, not on it, so
+        deepcopy / pickle / state_dict never see it."""
+        target = self.target
+        cached = _prepared_sets.get(self)
+        if cached is None or cached[0] is not target or cached[1] != target._version:
+            from . import _hip
+            cached = _prepared_sets[self] = (target, target._version, _hip.op_nearest_prepare(target.contiguous()))
+        return cached[2]
+
+    def forward(self, input):
+        if native.enabled and eligible(input, 'nearest') and self.target.shape[0] == input.shape[-3] and \
+                not self.target.requires_grad and self.target.device == input.device and self.target.dtype == torch.float32:
+            return _NearestLoss.apply(input, self, self._prepared(), int(self.target.shape[1]))
+        return self._forward_torch(input)
+
+    def _forward_torch(self, input):
+        feat = input.flatten(-2)
+        with torch.no_grad():
+            k = self.match(feat, self.target.to(feat.dtype), self.chunk)
+        matched = self.target.to(feat.dtype)[:, k]              # [C, ..., N]
+        matched = matched.movedim(0, -2) if k.ndim > 1 else matched
+        return torch.mean((feat - matched) ** 2)
+
+
+def _first_argmin(x, dim):
+    """argmin along ``dim`` that returns the FIRST minimum (torch.argmin leaves the choice among equal values open)."""
+    least = x.amin(dim=dim, keepdim=True)
+    n = x.shape[dim]
+    shape = [1] * x.ndim
+    shape[dim] = n
+    index = torch.arange(n, device=x.device).view(shape)
+    return torch.where(x == least, index, n).amin(dim=dim)
 
 
 class TVLoss(nn.Module):

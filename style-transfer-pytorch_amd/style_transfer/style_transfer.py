@@ -361,6 +361,65 @@ def _resolve_style_marginal(style_marginal, style_loss, style_diagonal=None, sty
     return flags
 
 
+def _resolve_style_nearest(style_nearest, style_loss, style_diagonal=None, style_marginal=None, style_eps=None, masked=False,
+                           world=1, samples=None):
+    """``StyleTransfer.style_nearest`` as the fused closure takes it: one bool per entry of ``style_loss`` (the resolved
+    kinds).  A bool means every 'w2' layer that is flagged neither diagonal nor marginal; a sequence holds one bool per entry
+    of style_layers.  ``style_diagonal`` / ``style_marginal`` / ``style_eps``: the resolved lists (one per layer, eps None =
+    default).  ``samples``: ``StyleTransfer.style_nearest_samples``, checked here too.  Raises ``ValueError`` naming the
+    attribute for a wrong length, a value that is no bool, a true flag on a 'gram' layer, on a layer flagged diagonal or
+    marginal or with a custom eps, for any true flag together with style masks or regions (``masked``) or on several ranks,
+    and for ``style_nearest_samples`` that is neither None nor an int >= 1, before any device work."""
+    if samples is not None and (isinstance(samples, (bool, np.bool_)) or not isinstance(samples, (int, np.integer)) or samples < 1):
+        raise ValueError(f'style_nearest_samples {samples!r}: None, or an int >= 1 (the style vectors kept per layer and image)')
+    n = len(style_loss)
+    diagonal = list(style_diagonal) if style_diagonal is not None else [False] * n
+    marginal = list(style_marginal) if style_marginal is not None else [False] * n
+    epses = list(style_eps) if style_eps is not None else [None] * n
+    if isinstance(style_nearest, (bool, np.bool_)):
+        flags = [bool(style_nearest) and name == _hip.STYLE_LOSSES[0] and not diag and not marg
+                 for name, diag, marg in zip(style_loss, diagonal, marginal)]
+    else:
+        if isinstance(style_nearest, str) or not isinstance(style_nearest, (list, tuple)):
+            raise ValueError(f'style_nearest {style_nearest!r}: give a bool, or a sequence with one bool per entry of style_layers')
+        flags = list(style_nearest)
+        if len(flags) != n:
+            raise ValueError(f'style_nearest {style_nearest!r}: {len(flags)} flags for {n} layers; give one bool, or exactly '
+                             'one per entry of style_layers')
+        for i, (flag, name) in enumerate(zip(flags, style_loss)):
+            if not isinstance(flag, (bool, np.bool_)) and flag not in (0, 1):
+                raise ValueError(f'style_nearest {style_nearest!r}: {flag!r} is not a bool')
+            if flag and name != _hip.STYLE_LOSSES[0]:
+                raise ValueError(f"style_nearest {style_nearest!r}: layer {i} has the loss {name!r} (StyleLoss on Gram "
+                                 "matrices); only a 'w2' layer can be matched on nearest style vectors")
+            if flag and diagonal[i]:
+                raise ValueError(f'style_nearest {style_nearest!r}: layer {i} is flagged in style_diagonal too; a layer takes '
+                                 'one of the two')
+            if flag and marginal[i]:
+                raise ValueError(f'style_nearest {style_nearest!r}: layer {i} is flagged in style_marginal too; a layer takes '
+                                 'one of the two')
+        flags = [bool(flag) for flag in flags]
+    for i, flag in enumerate(flags):
+        if flag and epses[i] is not None:
+            raise ValueError(f'style_nearest {style_nearest!r}: layer {i} has the custom style_eps {epses[i]!r}; the nearest '
+                             'term has no eps')
+    if masked and any(flags):
+        raise ValueError(f'style_nearest {style_nearest!r} together with style_mask, style_regions or style_image_masks: '
+                         'masked matching is out of scope - clear one of them')
+    if world > 1 and any(flags):
+        raise ValueError(f'style_nearest {style_nearest!r} on {world} ranks: row strips run full W2 heads only; nearest '
+                         'heads are out of scope for strips - run them on one device')
+    return flags
+
+
+def _nearest_sample_columns(m, samples):
+    """The columns of a style tap of m pixels that ``style_nearest_samples`` keeps: all of them, or ``floor(t m / K)``,
+    t = 0 ... K - 1, when m > K."""
+    if samples is None or m <= samples:
+        return list(range(m))
+    return [(t * m) // samples for t in range(samples)]
+
+
 def _mask_image(mask, attr):
     """One mask as (PIL image, divisor): a PIL image becomes mode 'L' (divisor 255), a 2-D numpy / torch array with values
     in [0, 1] a mode 'F' image (divisor 1).  Raises ``ValueError`` naming ``attr``."""
@@ -894,6 +953,18 @@ class StyleTransfer:
     # False, True (every 'w2' layer) or a sequence with one bool per entry of style_layers.  Not together with
     # style_diagonal or a custom style_eps on the same layer, nor with style masks or regions.  One device only.
     style_marginal = False
+    # 'w2' layers matched on nearest style vectors (_hip.Plan.set_style_nearest, losses.StyleLossNearest; the reference has
+    # none): every pixel's feature vector is pulled towards the closest feature vector of the style images - the MRF /
+    # neural-neighbour family of style losses, which copies local structure that moment matching smears.  One fused search per
+    # layer and iteration: 2 C N M flop for N pixels against M style vectors, and no N x M matrix.  False, True (every 'w2'
+    # layer) or a sequence with one bool per entry of style_layers.  Several style images give the union of their vectors in
+    # image order; an image of weight 0 is left out, otherwise style_weights do not enter such a layer.  Not together with
+    # style_diagonal, style_marginal or a custom style_eps on the same layer, nor with style masks or regions.  One device only.
+    style_nearest = False
+    # None, or an int K >= 1: when a style tap has more than K pixels the host keeps the columns floor(t M / K), t = 0 ... K - 1,
+    # per image and flagged layer.  This is what makes a shallow layer affordable: the search costs 2 C N M flop per iteration
+    # (relu1_1 at 512^2 has N = M = 262144).
+    style_nearest_samples = None
     # Spatial masks for the style statistics (read by stylize() too; the reference has none).  style_mask: which pixels of the
     # OUTPUT take the style - a PIL image (read as 'L' / 255) or a 2-D numpy / torch array in [0, 1], resized bilinearly to
     # every scale; the style heads then take mask-weighted moments of the iterate's taps (_hip.Plan.set_style_mask).
@@ -1009,6 +1080,7 @@ class StyleTransfer:
             plan.set_content_target_from_forward()
         blends = [{} for _ in range(len(regions[0]) if regions else 1)]
         marginal, quantiles = plan.w2_marginal, {}      # (flagged layers: never with a mask or regions, _resolve_style_marginal)
+        nearest, vectors = plan.style_nearest, {}       # (the same, _resolve_style_nearest)
         for i, image in enumerate(style_images):
             blended = blends[region_of[i]]
             if style_size is None:
@@ -1029,6 +1101,16 @@ class StyleTransfer:
             if image_mask is not None:
                 splan.set_style_mask(_sized_mask(image_mask, sw, sh))
             for idx, layer in enumerate(style_layers):
+                if nearest[idx]:
+                    # a layer matched on nearest vectors: the union of the images' feature vectors in image order, an image
+                    # of weight 0 left out; the weights do not enter otherwise
+                    if style_weights[i] != 0:
+                        tap = splan.feature(layer)[0].flatten(1)
+                        columns = _nearest_sample_columns(tap.shape[1], self.style_nearest_samples)
+                        if len(columns) < tap.shape[1]:
+                            tap = tap[:, torch.tensor(columns, device=tap.device)]
+                        vectors.setdefault(layer, []).append(tap)
+                    continue
                 if marginal[idx]:
                     # a layer matched on its marginals: the style tap's quantile functions at the iterate's pixel count,
                     # blended by the images' weights (in one dimension the Wasserstein barycentre)
@@ -1054,7 +1136,12 @@ class StyleTransfer:
             plan.set_region_weights(regions[2])
         for r, blended in enumerate(blends):
             for idx, layer in enumerate(style_layers):
-                if marginal[idx]:
+                if nearest[idx]:
+                    if layer not in vectors:
+                        raise ValueError('style_nearest: every style image has weight 0; a flagged layer needs at least one '
+                                         'style vector')
+                    plan.set_style_vectors(idx, torch.cat(vectors[layer], dim=1))
+                elif marginal[idx]:
                     plan.set_style_quantiles(idx, quantiles[layer])
                 elif regions:
                     plan.set_region_style_target(r, idx, *blended[layer])
@@ -1205,6 +1292,10 @@ class StyleTransfer:
                                                  masked=any(value is not None for value in (self.style_mask, self.style_regions,
                                                                                             self.style_image_masks)),
                                                  world=max(len(self.devices), _dist_info()[1]))
+        style_nearest = _resolve_style_nearest(self.style_nearest, style_loss, style_diagonal, style_marginal, style_eps,
+                                               masked=any(value is not None for value in (self.style_mask, self.style_regions,
+                                                                                          self.style_image_masks)),
+                                               world=max(len(self.devices), _dist_info()[1]), samples=self.style_nearest_samples)
         content_map, tv_map = _resolve_weight_maps(self.content_mask, self.tv_mask,
                                                    world=max(len(self.devices), _dist_info()[1]))
         # (the smallest scale's image bounds the pool sizes; a weight of 0 has no term and no size to check)
@@ -1346,6 +1437,8 @@ class StyleTransfer:
                     plan.set_w2_diagonal(style_diagonal)
                 if any(style_marginal):
                     plan.set_w2_marginal(style_marginal)
+                if any(style_nearest):
+                    plan.set_style_nearest(style_nearest)
                 self._build_targets(plan, content.to(device), style_images, style_weights, scale, style_scale_fac,
                                     style_size, style_mask, image_masks, regions)
                 # the content and TV maps at this scale's size, on the iterate's plan only and after the targets (which they
