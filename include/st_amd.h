@@ -349,7 +349,8 @@ int st_plan_loss_kinds(const st_plan* plan, int* content_kind, int* style_kind);
  * the kind of a list whose entries agree and returns a mixed list to kind 0.  st_plan_layer_loss_kinds writes n_content /
  * n_style codes (either pointer may be null).
  * Order of configuration: layers (st_plan_set_taps), kinds, eps (st_plan_set_loss_eps), diagonal (st_plan_set_w2_diagonal),
- * marginal (st_plan_set_w2_marginal), nearest (st_plan_set_style_nearest), weights, then the targets.
+ * marginal (st_plan_set_w2_marginal), nearest (st_plan_set_style_nearest), sliced (st_plan_set_style_sliced and its options and
+ * seed), weights, then the targets.
  */
 int st_plan_set_layer_loss_kinds(st_plan* plan, const int* content_kinds, const int* style_kinds);
 int st_plan_layer_loss_kinds(const st_plan* plan, int* content_kinds, int* style_kinds);
@@ -493,6 +494,90 @@ int st_plan_set_style_vectors(st_plan* plan, int index, const float* feat, long 
 /* Borrows the matches of the last closure for flagged entry `index`: *idx [n] ints of the plan's (device memory), k*(i) in
  * [0, m), valid until the plan is destroyed and rewritten by every closure. */
 int st_plan_nearest_indices(st_plan* plan, int index, const int** idx, long long* n);
+
+/*
+ * The sliced Wasserstein option of a W2 style layer: flags[n_style], 0 or 1 in list order; a null pointer clears all.  The
+ * second-moment heads see two moments of the tap, the marginal head the exact one-dimensional distributions along the C channel
+ * axes only, the nearest head single vectors.  This one is the W2 distance between the projections of the tap and of the style
+ * onto P random unit directions, with new directions at every evaluation, so that over a run it sees the whole C-dimensional
+ * distribution (Heitz et al., "A Sliced Wasserstein Loss for Neural Texture Synthesis").  It is an OPTION of a w2 layer - the
+ * kind names and codes do not change - and the reference has no such module, so the semantics are fixed here.  For flagged
+ * entry j with tap F [C][N], the style images' feature vectors S_i [C][M_i] in image order with blend weights a_i (the image's
+ * weight over the sum of the weights; an image of weight 0 is left out) and directions R [P][C], every row of unit length:
+ *   Y      = R F;  pi_p the stable ascending order of row p of Y + 0.0: ties by ascending pixel index, -0.0 equal to +0.0 (the
+ *            marginal head's rule)
+ *   T      = sum_i a_i resample_N(sort_rows(R S_i)),  resample_N: st_op_resample_quantiles' midpoint rule, M_i == N a copy; per
+ *            direction the one-dimensional Wasserstein barycentre.  Image 0 writes a_0 q, image i > 0 adds a_i q, in fp32
+ *   term_j = w_j sum_p sum_k (Y_p,pi_p(k) - T_p,k)^2 / (P N)
+ *   dF     = w_j (2 / (P N)) R^T G,   G_p,pi_p(k) = Y_p,pi_p(k) - T_p,k
+ * R and the permutations are constants of the gradient.  There is no eps.  With R = I and P = C the term is the marginal
+ * head's term; the division is by P N, so a weight means the same for any P.  Inputs are finite; with a NaN the result is
+ * unspecified, but every launch ends (no loop's trip count depends on a comparison of values).
+ * Directions are generated on the device (csrc/st_sliced.hip), a wave per row.  Row p of entry j at epoch e is a vector of C
+ * standard normals divided by its norm:
+ *   mix(z):  z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9;  z = (z ^ (z >> 27)) * 0x94d049bb133111eb;  z ^ (z >> 31)   (64-bit words:
+ *            splitmix64's finaliser)
+ *   key    = mix(mix(mix(seed ^ 0x9e3779b97f4a7c15) ^ (j + 1)) ^ e)
+ *   h      = mix(key ^ (p << 32 | c))                      one hash word per element: a counter-based generator, no state
+ *   u1     = ((h >> 41) + 1/2) 2^-23  in (0, 1),   u2 = ((h & 0xffffffff) >> 8) 2^-24  in [0, 1)
+ *   z_pc   = sqrt(-2 ln u1) cos(2 pi u2)                   (Box-Muller, fp32; the device's fast log and cosine)
+ *   r_pc   = z_pc / sqrt(sum_c z_pc^2): the sum in double, lane l of the wave adds c = l, l + 64, ... in ascending order and the
+ *            64 sums meet in an xor butterfly (offsets 32, 16, ..., 1); the quotient in double, rounded once
+ * Bit-equality with a host implementation is not promised (the device's log and cosine); st_plan_sliced_directions borrows R.
+ * The same launch writes R [P][C] and R^T [C][P], the two weight layouts of the 1x1 step.  P is a multiple of 64 in [64, 512],
+ * by default C (st_plan_set_sliced_options).
+ * Epoch: one plan-wide counter, the epoch at which the NEXT evaluation of the general closure draws its directions.  While any
+ * flagged entry resamples, every evaluation of the general closure advances it by one: st_plan_loss_and_grad, both native steps
+ * and the range guard.  It is a HOST counter handed to the direction kernel as an argument: the general closure is never
+ * captured into a graph (st_plan_set_graph replays the default closure only), so no replay can reuse an epoch.
+ * st_plan_set_sliced_seed sets the seed and returns the epoch to 0.  An entry whose resampling is off draws its directions at
+ * epoch 0, once, in st_plan_set_style_sliced_vectors, where its target is derived once too.  The same seed and the same sequence
+ * of calls give the same bits; with resampling off two closures give the same bits.  No floating-point atomics anywhere.
+ * A flagged head: with resampling on the direction kernel and, per style image, the target's share - R S_i through the 1x1 step,
+ * the segmented sort of csrc/st_sort.hip on P rows, unpack, resample to N, blend; then Y = R F through the 1x1 step, the sort
+ * and the residual pass on P rows, which writes G to a buffer of the head, and dF = R^T G through the 1x1 step (C_in = P,
+ * C_out = C), WRITTEN to the tap's seed buffer (a content term of the same layer adds after it).  On an fp16x3 network the
+ * three products run in fp16x3: the bound of R is 1 by construction, the tap's is the word its producer left, an image's is
+ * measured once by the setter, and max |G| is measured on the device by the integer atomicMax pass that measures every other
+ * operand (no host read); on an fp32 network they run on the exact fp32 MFMA.  At the style's own tap (M = N, one image) the
+ * term is below 1e-10 of mean(Y^2) but not promised to be exactly 0: the tap's projection is scaled by its producer's bound, the
+ * style's by a measured one, and the two can differ by a power of two.
+ * It allocates R and R^T (for P = 512), T [P][N], the S_i, Y and G [P][max(N, max M_i)], two buffers of P max(N, max M_i)
+ * keys, the partials, a ticket and the bound words; no C x C buffer, no Newton-Schulz workspace.
+ * Any set flag runs the general closure (csrc/st_taps.hip), on the default lists too; flags that are all 0, or set and then
+ * cleared, leave, bit for bit, a plan on which this was never called.  Like st_plan_set_style_nearest the call drops every
+ * target set before and invalidates a captured graph; it also returns the flagged entries' options to their defaults and the
+ * epoch to 0; either kinds setter and st_plan_set_taps clear the flags.
+ * Fails for a flag on a gram entry, on an entry flagged diagonal, marginal or nearest (and their setters refuse an entry flagged
+ * here), on an entry with a non-default eps (and st_plan_set_loss_eps refuses one for an entry flagged here), on an entry whose
+ * channel count is no multiple of 64, for a value other than 0 or 1, for any set flag on a strip plan, and while a style mask or
+ * style regions are set (st_plan_set_style_mask and st_plan_set_style_regions refuse while a flag is set): weighted quantiles
+ * are not implemented.  st_plan_term_losses and the 8-float array keep their shapes.
+ * Order of configuration: layers, kinds, eps, diagonal, marginal, nearest, sliced (flags, options, seed), weights, then the targets.
+ */
+int st_plan_set_style_sliced(st_plan* plan, const int* flags);
+int st_plan_style_sliced(const st_plan* plan, int* flags);
+/* Flagged entry `index`: `projections` directions (0: the tap's C; else a multiple of 64 in [64, 512]) and whether every closure
+ * draws new ones (`resample` 1, the default) or the entry keeps those of epoch 0 (0).  Drops that entry's target.  Fails on an
+ * entry that is not flagged. */
+int st_plan_set_sliced_options(st_plan* plan, int index, int projections, int resample);
+/* The seed of every flagged entry's directions (default 0); the epoch returns to 0 and the flagged entries' targets are dropped:
+ * set it before the style vectors. */
+int st_plan_set_sliced_seed(st_plan* plan, unsigned long long seed);
+/* The target of flagged style entry `index`: n_images style images, feats[i] = S_i [C][ms[i]] in device memory (a style tap as it
+ * lies in a plan), weights[i] >= 0 (host; null: equal weights).  The vectors are copied into the plan, each image's bound is
+ * measured, and the directions of the current epoch and the target under them are derived on `stream`.  At most 16 images of
+ * weight > 0, each of 1 to 2^24 - 1 vectors.  A set that needs larger buffers than the entry holds allocates new ones; the
+ * former stay the plan's until it is destroyed (st_plan_device_bytes counts them).  Until the call has succeeded the entry holds
+ * no target.  Fails on an entry that is not flagged; st_plan_set_style_target, st_plan_set_style_quantiles and
+ * st_plan_set_style_vectors fail on a flagged one. */
+int st_plan_set_style_sliced_vectors(st_plan* plan, int index, int n_images, const float* const* feats, const long long* ms,
+                                     const float* weights, void* stream);
+/* Borrows the directions the last closure used for flagged entry `index` (before any closure: those the setter drew):
+ * *r [P][C] floats of the plan's (device memory), rewritten by every closure while the entry resamples; *epoch: theirs. */
+int st_plan_sliced_directions(st_plan* plan, int index, const float** r, int* projections, int* channels, unsigned long long* epoch);
+/* Borrows the target under those directions: *target [P][N] floats of the plan's (device memory). */
+int st_plan_sliced_target(st_plan* plan, int index, const float** target, int* projections, long long* n);
 
 /* ContentLossMSE target (style_transfer.py:425-429): copies feat [512][H/8][W/8] into the plan (a configured plan: the
  * target of content layer 0, shaped like that layer). */
@@ -902,6 +987,31 @@ int st_op_nearest_loss(const float* feat, int channels, long long n, const float
                        float* unit_grad_out, float* loss_out, void* stream);
 /* ... grad[i] = upstream[0] * unit_grad[i], i < count; upstream: a DEVICE scalar. */
 int st_op_nearest_loss_backward(const float* unit_grad, long long count, const float* upstream, float* grad, void* stream);
+/* The sliced head of st_plan_set_style_sliced on ONE dense fp32 tensor feat [C][n], by the same kernels: C a multiple of 32, P a
+ * multiple of 64 in [64, 512], rows of 1 to 2^24 - 1 elements.  The directions are ARGUMENTS - r [P][C] and its transpose
+ * rt [C][P], both layouts of the 1x1 step - so a caller's own work as well as st_op_sliced_directions' (rows of at most unit
+ * length are not required: max |r| is measured).  Both products run in fp16x3 with max |feat|, max |r| and max |G| measured on the
+ * device (the option ST_SLICED_FP32 = 1: on the exact fp32 MFMA).
+ * st_op_sliced_directions: r_out [P][C], rt_out [C][P] of (seed, entry, epoch), the generator written down above.
+ * `scratch`: st_op_sliced_scratch_bytes(C, P, n) bytes of the caller's, 256-byte aligned, per call, n the longest row of the call
+ * (st_op_sliced_target: max(m, n_out)).
+ * st_op_sliced_target: one style image's share, target [P][n_out] = (accumulate ? target : 0) + weight resample_n_out(sort_rows(r feat)),
+ * feat [C][m].  Two calls on the same data give the same bits. */
+int st_op_sliced_directions(unsigned long long seed, int entry, unsigned long long epoch, int projections, int channels, float* r_out,
+                            float* rt_out, void* stream);
+long long st_op_sliced_scratch_bytes(int channels, int projections, long long n);
+int st_op_sliced_target(const float* feat, int channels, long long m, const float* r, const float* rt, int projections, long long n_out,
+                        void* scratch, float* target, int accumulate, float weight, void* stream);
+/* y_out [P][n] = r feat, bit for bit the projection st_op_sliced_loss sorts (the same launch under the same measured bounds): its
+ * stable order is the permutation the gradient goes through, which can differ from the float64 order of r feat at near-ties. */
+int st_op_sliced_project(const float* feat, int channels, long long n, const float* r, const float* rt, int projections, void* scratch,
+                         float* y_out, void* stream);
+/* loss_out[0] = sum_p sum_k (Y_p,pi_p(k) - target_p,k)^2 / (P n) at weight 1, Y = r feat, target [P][n] with sorted rows;
+ * unit_grad_out [C][n] = d loss / d feat = (2 / (P n)) rt G (autograd: saved on the node) ... */
+int st_op_sliced_loss(const float* feat, int channels, long long n, const float* r, const float* rt, int projections, const float* target,
+                      void* scratch, float* unit_grad_out, float* loss_out, void* stream);
+/* ... grad[i] = upstream[0] * unit_grad[i], i < count; upstream: a DEVICE scalar. */
+int st_op_sliced_loss_backward(const float* unit_grad, long long count, const float* upstream, float* grad, void* stream);
 /* TVLoss (style_transfer.py:184-195) on a [3][H][W] image, H, W >= 1: the value alone (st_op_tv_loss writes the unit
  * gradient with it) ... */
 int st_op_tv_value(const float* image, int height, int width, float* scratch, float* loss_out, void* stream);

@@ -463,6 +463,9 @@ int st_plan_set_region_style_target(st_plan* p, int region, int index, const flo
     ST_REQUIRE(!p->style_near[index],
                "st_plan_set_style_target: style layer %d is flagged nearest (st_plan_set_style_nearest): its target is a set of style vectors, "
                "set by st_plan_set_style_vectors", index);
+    ST_REQUIRE(!p->style_sliced[index],
+               "st_plan_set_style_target: style layer %d is flagged sliced (st_plan_set_style_sliced): its target is derived from the style "
+               "images' feature vectors, set by st_plan_set_style_sliced_vectors", index);
     hipStream_t s = static_cast<hipStream_t>(stream);
     StyleHead& h = region_head_at(p, region, p->style_op[index]);
     if (ensure_style_alloc(p, h, alloc_kind_of(p, index))) return 1;
@@ -488,6 +491,8 @@ int st_plan_set_style_quantiles(st_plan* p, int index, const float* q, long long
     ST_REQUIRE(index >= 0 && index < p->n_style, "st_plan_set_style_quantiles: index %d out of range (%d style layers)", index, p->n_style);
     ST_REQUIRE(!p->style_near[index], "st_plan_set_style_quantiles: style layer %d is flagged nearest (st_plan_set_style_nearest): its target "
                "is set by st_plan_set_style_vectors", index);
+    ST_REQUIRE(!p->style_sliced[index], "st_plan_set_style_quantiles: style layer %d is flagged sliced (st_plan_set_style_sliced): its target "
+               "is set by st_plan_set_style_sliced_vectors", index);
     ST_REQUIRE(p->style_marg[index], "st_plan_set_style_quantiles: style layer %d is not flagged marginal (st_plan_set_w2_marginal): its "
                "target is set by st_plan_set_style_target", index);
     ST_REQUIRE(n_q >= 1, "st_plan_set_style_quantiles: %lld order statistics per channel: at least one", n_q);
@@ -513,6 +518,8 @@ int st_plan_style_quantiles(st_plan* p, int index, float** target, int* channels
 int st_plan_set_style_vectors(st_plan* p, int index, const float* feat, long long m, void* stream) {
     ST_REQUIRE(p && feat, "st_plan_set_style_vectors: null argument");
     ST_REQUIRE(index >= 0 && index < p->n_style, "st_plan_set_style_vectors: index %d out of range (%d style layers)", index, p->n_style);
+    ST_REQUIRE(!p->style_sliced[index], "st_plan_set_style_vectors: style layer %d is flagged sliced (st_plan_set_style_sliced): its target "
+               "is set by st_plan_set_style_sliced_vectors", index);
     ST_REQUIRE(p->style_near[index], "st_plan_set_style_vectors: style layer %d is not flagged nearest (st_plan_set_style_nearest): its "
                "target is set by st_plan_set_style_target", index);
     StyleHead& h = p->head[p->style_op[index]];
@@ -536,6 +543,87 @@ int st_plan_nearest_indices(st_plan* p, int index, const int** idx, long long* n
     ST_REQUIRE(p->style_near[index] && h.target_set && h.near_idx,
                "st_plan_nearest_indices: style layer %d holds no matches (st_plan_set_style_nearest, st_plan_set_style_vectors)", index);
     *idx = h.near_idx;
+    *n = h.npix_local;
+    return 0;
+}
+
+int st_plan_set_style_sliced_vectors(st_plan* p, int index, int n_images, const float* const* feats, const long long* ms,
+                                     const float* weights, void* stream) {
+    ST_REQUIRE(p && feats && ms, "st_plan_set_style_sliced_vectors: null argument");
+    ST_REQUIRE(index >= 0 && index < p->n_style, "st_plan_set_style_sliced_vectors: index %d out of range (%d style layers)", index,
+               p->n_style);
+    ST_REQUIRE(p->style_sliced[index], "st_plan_set_style_sliced_vectors: style layer %d is not flagged sliced (st_plan_set_style_sliced): "
+               "its target is set by st_plan_set_style_target", index);
+    ST_REQUIRE(n_images >= 1, "st_plan_set_style_sliced_vectors: %d style images: at least one", n_images);
+    StyleHead& h = p->head[p->style_op[index]];
+    const int proj = sliced_projections_of(p, index);
+    // the images that enter: those of weight > 0 (a null list: every image, equal weights), their weights over their sum
+    int kept[kSlicedMaxImages] = {};
+    int n_kept = 0;
+    long long total = 0, rows = h.npix_local;
+    double sum = 0.0;
+    for (int i = 0; i < n_images; ++i) {
+        const float w = weights ? weights[i] : 1.f;
+        ST_REQUIRE(w >= 0.f && w <= 3.0e38f, "st_plan_set_style_sliced_vectors: weight %g of style image %d: finite and not negative", (double)w, i);
+        if (w == 0.f) continue;
+        ST_REQUIRE(feats[i], "st_plan_set_style_sliced_vectors: null feature vectors for style image %d", i);
+        ST_REQUIRE(n_kept < kSlicedMaxImages, "st_plan_set_style_sliced_vectors: more than %d style images of weight > 0", kSlicedMaxImages);
+        if (sliced_check_shape("st_plan_set_style_sliced_vectors", h.n, proj, ms[i])) return 1;
+        kept[n_kept++] = i;
+        total += ms[i];
+        rows = std::max(rows, ms[i]);
+        sum += (double)w;
+    }
+    ST_REQUIRE(n_kept >= 1, "st_plan_set_style_sliced_vectors: every style image has weight 0");
+    if (sliced_check_shape("st_plan_set_style_sliced_vectors", h.n, proj, h.npix_local)) return 1;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // (a closure in flight may still read the former set: the buffers are rewritten behind it on the caller's stream)
+    // the entry holds no target until the new one is derived
+    h.target_set = false;
+    invalidate_graph(p);
+    if (alloc_head_sliced(h, proj, total, rows, PlanAlloc{p})) return 1;
+    ST_HIP(hipStreamSynchronize(nullptr));
+    h.sl_rows = rows;
+    h.sl_images = n_kept;
+    unsigned int* bounds = reinterpret_cast<unsigned int*>(h.sl_bounds);
+    ST_HIP(hipMemsetAsync(bounds + kAmaxWordUints, 0, (size_t)kSlicedMaxImages * kAmaxWordUints * sizeof(unsigned int), s));
+    float* dst = h.sl_feats;
+    for (int k = 0; k < n_kept; ++k) {
+        const int i = kept[k];
+        const size_t count = (size_t)h.n * (size_t)ms[i];
+        ST_HIP(hipMemcpyAsync(dst, feats[i], count * sizeof(float), hipMemcpyDeviceToDevice, s));
+        if (launch_amax(dst, (long long)count, bounds + (size_t)(1 + k) * kAmaxWordUints, 0, s)) return 1;
+        h.sl_m[k] = ms[i];
+        h.sl_a[k] = (float)((double)(weights ? weights[i] : 1.f) / sum);
+        dst += count;
+    }
+    // the directions of the epoch the next closure runs at - 0 for an entry that keeps its directions - and the target under them
+    if (sliced_refresh(p, index, p->sliced_resample[index] ? p->sliced_epoch : 0ull, s)) return 1;
+    h.target_set = true;
+    return 0;
+}
+
+int st_plan_sliced_directions(st_plan* p, int index, const float** r, int* projections, int* channels, unsigned long long* epoch) {
+    ST_REQUIRE(p && r && projections && channels && epoch, "st_plan_sliced_directions: null argument");
+    ST_REQUIRE(index >= 0 && index < p->n_style, "st_plan_sliced_directions: index %d out of range (%d style layers)", index, p->n_style);
+    const StyleHead& h = p->head[p->style_op[index]];
+    ST_REQUIRE(p->style_sliced[index] && h.target_set && h.sl_r,
+               "st_plan_sliced_directions: style layer %d holds no directions (st_plan_set_style_sliced, st_plan_set_style_sliced_vectors)", index);
+    *r = h.sl_r;
+    *projections = sliced_projections_of(p, index);
+    *channels = h.n;
+    *epoch = h.sl_epoch;
+    return 0;
+}
+
+int st_plan_sliced_target(st_plan* p, int index, const float** target, int* projections, long long* n) {
+    ST_REQUIRE(p && target && projections && n, "st_plan_sliced_target: null argument");
+    ST_REQUIRE(index >= 0 && index < p->n_style, "st_plan_sliced_target: index %d out of range (%d style layers)", index, p->n_style);
+    const StyleHead& h = p->head[p->style_op[index]];
+    ST_REQUIRE(p->style_sliced[index] && h.target_set && h.sl_t,
+               "st_plan_sliced_target: style layer %d holds no target (st_plan_set_style_sliced, st_plan_set_style_sliced_vectors)", index);
+    *target = h.sl_t;
+    *projections = sliced_projections_of(p, index);
     *n = h.npix_local;
     return 0;
 }

@@ -766,6 +766,35 @@ int launch_nearest_search(const float* feat, int channels, long long n, const Ne
 int nearest_head_run(const float* feat, int channels, long long n, const NearestPrepared& pr, const NearestScratch& sc,
                      const unsigned int* feat_bound, float weight, int* idx_out, float* score_out, float* grad, float* loss_out,
                      hipStream_t s);
+// ---- sliced Wasserstein W2 heads (st_plan_set_style_sliced, st_op_sliced_*; st_sliced.hip) ----
+constexpr int kSlicedMaxImages = 16;              // style images a flagged entry keeps the feature vectors of
+// C a multiple of 32 (the 1x1 step's chunk), P a multiple of 64 in [64, 512], rows of 1 <= n < 2^24 elements
+int sliced_check_shape(const char* who, int channels, int proj, long long n);
+// R [P][C] and R^T [C][P] of (seed, entry, epoch): include/st_amd.h writes the generator down
+int launch_sliced_directions(unsigned long long seed, int entry, unsigned long long epoch, int proj, int channels, float* r, float* rt,
+                             hipStream_t s);
+// per call, sliced_scratch_bytes bytes, 256-byte aligned, for rows of at most n elements (the tap's pixels or a style image's
+// vectors, whichever is more): three bound words (the operand in front of a projection, R, G), Y and G [P][n], the sort's scratch
+long long sliced_scratch_bytes(int proj, long long n);
+struct SlicedScratch {
+    unsigned int *in_bound = nullptr, *r_bound = nullptr, *g_bound = nullptr;
+    float *y = nullptr, *g = nullptr;
+    void* sort = nullptr;               // marginal_scratch_bytes(P, n): its ticket is zero between launches
+};
+SlicedScratch sliced_scratch_of(void* scratch, int proj, long long n);
+// out [Cout][npix] = W in, W given in both layouts: w [Cout][Cin] for the fp16x3 1x1 step, which runs when both bounds are given
+// (in_bound on max |in|, w_bound on max |w|), wt [Cin][Cout] for the exact fp32 MFMA otherwise
+int sliced_product(const float* in, int cin, int cout, long long npix, const float* w, const float* wt, const unsigned int* in_bound,
+                   const unsigned int* w_bound, float* out, hipStream_t s);
+// one style image's share of the target: T [P][n_out] = (accumulate ? T : 0) + weight resample_n_out(sort_rows(R feat)), feat [C][m]
+int sliced_target_add(const float* feat, int channels, long long m, const float* r, const float* rt, int proj, long long n_out,
+                      const SlicedScratch& sc, const unsigned int* feat_bound, const unsigned int* r_bound, float* target, int accumulate,
+                      float weight, hipStream_t s);
+// the head on feat [C][n]: Y = R feat, the sort and the residual pass against target [P][n] (G into the scratch, the weighted term to
+// loss_out[0]), then grad [C][n] = R^T G WRITTEN.  Bounds null: the exact fp32 MFMA for both products
+int sliced_head_run(const float* feat, int channels, long long n, const float* r, const float* rt, int proj, const float* target,
+                    const SlicedScratch& sc, const unsigned int* feat_bound, const unsigned int* r_bound, float weight, float* grad,
+                    float* loss_out, hipStream_t s);
 // ---- Laplacian loss on pooled images (st_plan_set_laplacian, st_op_laplacian_*; st_laplacian.hip) ----
 constexpr int kMaxLapPools = 4;
 constexpr int kLapBlocks = 1024;                  // workgroups of the residual pass at most: its partials

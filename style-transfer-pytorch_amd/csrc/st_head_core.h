@@ -42,7 +42,57 @@ struct StyleHead {
     int* near_idx = nullptr;
     long long near_m = 0;
     size_t near_prep_floats = 0, near_scratch_floats = 0;
+    // a W2 entry matched on sliced projections (st_plan_set_style_sliced): the directions R [P][C] and R^T [C][P] (buffers for
+    // P = 512) of epoch sl_epoch, the target T [P][npix], the style images' feature vectors side by side in image order
+    // (sl_feats: image i is [n][sl_m[i]], blend weight sl_a[i]), the bound words (R's, 1 by construction, then one per image,
+    // measured once by the setter) and the call's scratch (sliced_scratch_bytes: Y, G, the sort's keys, partials and ticket)
+    float *sl_r = nullptr, *sl_rt = nullptr, *sl_t = nullptr, *sl_feats = nullptr, *sl_bounds = nullptr, *sl_scratch = nullptr;
+    int sl_images = 0;
+    long long sl_m[kSlicedMaxImages] = {};
+    float sl_a[kSlicedMaxImages] = {};
+    long long sl_rows = 0;              // the longest row the scratch was sized for: max(npix, max sl_m)
+    unsigned long long sl_epoch = 0;
+    size_t sl_t_floats = 0, sl_feats_floats = 0, sl_scratch_floats = 0;
 };
+
+// what a sliced head needs for P projections and style images of `total` feature vectors in all, the longest row (the tap's
+// pixels or an image's vectors) `rows`.  R, R^T and the bound words are allocated once; T, the vectors and the scratch grow when
+// asked for more than they hold, and an outgrown buffer stays the allocator's until the plan is destroyed, as a nearest head's.
+// R's bound word holds 1.0f; the ticket in front of the sort's scratch is zeroed; both on the null stream, which the caller
+// synchronises
+template <class Alloc>
+int alloc_head_sliced(StyleHead& h, int proj, long long total, long long rows, Alloc&& alloc) {
+    if (alloc(&h.sl_r, (size_t)512 * h.n) || alloc(&h.sl_rt, (size_t)512 * h.n)) return 1;
+    if (!h.sl_bounds) {
+        if (alloc(&h.sl_bounds, (size_t)(1 + kSlicedMaxImages) * kAmaxWordUints)) return 1;
+        ST_HIP(hipMemset(h.sl_bounds, 0, (size_t)(1 + kSlicedMaxImages) * kAmaxWordUints * sizeof(float)));
+        const float one = 1.f;
+        ST_HIP(hipMemcpy(h.sl_bounds, &one, sizeof(float), hipMemcpyHostToDevice));
+    }
+    const size_t t = (size_t)proj * (size_t)h.npix_local, feats = (size_t)h.n * (size_t)total;
+    const size_t scratch = (size_t)(sliced_scratch_bytes(proj, rows) / 4);
+    if (t > h.sl_t_floats) {
+        h.sl_t = nullptr;
+        h.sl_t_floats = 0;
+        if (alloc(&h.sl_t, t)) return 1;
+        h.sl_t_floats = t;
+    }
+    if (feats > h.sl_feats_floats) {
+        h.sl_feats = nullptr;
+        h.sl_feats_floats = 0;
+        if (alloc(&h.sl_feats, feats)) return 1;
+        h.sl_feats_floats = feats;
+    }
+    if (scratch > h.sl_scratch_floats) {
+        h.sl_scratch = nullptr;
+        h.sl_scratch_floats = 0;
+        if (alloc(&h.sl_scratch, scratch)) return 1;
+        h.sl_scratch_floats = scratch;
+    }
+    // (the layout of the scratch depends on (P, rows): the ticket's place is zeroed for this one)
+    ST_HIP(hipMemset(sliced_scratch_of(h.sl_scratch, proj, rows).sort, 0, 16));
+    return 0;
+}
 
 // what a nearest head needs for m style vectors.  Each buffer is sized by its own function of (C, N, m) and grows when that
 // function asks for more than it holds - the split count, hence the scratch, is not monotone in m.  A buffer that is outgrown

@@ -305,6 +305,9 @@ int st_plan_set_style_mask(st_plan* p, const float* mask, void* stream) {
     for (int j = 0; j < p->n_style; ++j)
         ST_REQUIRE(!p->style_near[j], "st_plan_set_style_mask: style layer %d is flagged nearest (st_plan_set_style_nearest), which takes no "
                    "style mask: clear the flag first", j);
+    for (int j = 0; j < p->n_style; ++j)
+        ST_REQUIRE(!p->style_sliced[j], "st_plan_set_style_mask: style layer %d is flagged sliced (st_plan_set_style_sliced), which takes no "
+                   "style mask: clear the flag first", j);
     ST_REQUIRE(!p->n_regions, "st_plan_set_style_mask: %d style regions are in force on this plan (st_plan_set_style_regions): "
                "clear them first", p->n_regions);
     constexpr size_t kPartials = kPyramidPartials;
@@ -415,6 +418,9 @@ int st_plan_set_style_regions(st_plan* p, int n_regions, const float* const* mas
                    "no style regions: clear the flag first", j);
     for (int j = 0; n_regions != 0 && j < p->n_style; ++j)
         ST_REQUIRE(!p->style_near[j], "st_plan_set_style_regions: style layer %d is flagged nearest (st_plan_set_style_nearest), which takes "
+                   "no style regions: clear the flag first", j);
+    for (int j = 0; n_regions != 0 && j < p->n_style; ++j)
+        ST_REQUIRE(!p->style_sliced[j], "st_plan_set_style_regions: style layer %d is flagged sliced (st_plan_set_style_sliced), which takes "
                    "no style regions: clear the flag first", j);
     // no regions are in force until every one of them is accepted
     p->n_regions = 0;

@@ -149,6 +149,16 @@ struct st_plan {
     // together with style_diag, style_marg, a custom eps, a style mask or regions.  Any set flag runs the general closure; either
     // kinds setter and st_plan_set_taps clear them.
     int style_near[16] = {};
+    // A W2 entry matched on sliced projections (st_plan_set_style_sliced, st_sliced.hip): a flag per LISTED style entry, never
+    // together with style_diag, style_marg, style_near, a custom eps, a style mask or regions.  Any set flag runs the general
+    // closure; either kinds setter and st_plan_set_taps clear them.  Per flagged entry: the number of projections (0: the tap's
+    // channels) and whether every closure draws new directions (st_plan_set_sliced_options).  sliced_epoch is the epoch the
+    // NEXT general closure draws its directions at: a host counter, handed to the direction kernel as an argument - the general
+    // closure is never captured into a graph - and advanced once per closure while any flagged entry resamples.
+    int style_sliced[16] = {};
+    int sliced_proj[16] = {};
+    int sliced_resample[16] = {};
+    unsigned long long sliced_seed = 0, sliced_epoch = 0;
     float* kind_scratch = nullptr;                   // non-default kinds: [2 kStreamBlocks] per-block (sum d^2, sum |d|) of the
                                                      // term in flight, then [2] per term: sum d^2, sum |d| + eps (kind_totals)
     st::StyleHead head[st::kNumOps];                 // n / npix / npix_local of all 17 filled at create, buffers on first use;
@@ -391,6 +401,10 @@ int tap_position(int layer);          // kProgram position of features[layer], -
 int closure_top_op(const st_plan* p); // the deepest kProgram position the plan's closure runs
 bool targets_ready(const st_plan* p);
 float* loss_terms(st_plan* p);        // the array the closure's weighted terms go to, in SumLoss order
+int sliced_projections_of(const st_plan* p, int j);      // P of sliced entry j: its option, or the tap's channels
+// sliced entry j's directions at `epoch` and, from its stored style vectors, its target (st_plan_set_style_sliced_vectors, and every
+// general closure while the entry resamples)
+int sliced_refresh(st_plan* p, int j, unsigned long long epoch, hipStream_t s);
 float style_eps_of(const st_plan* p, int j);   // effective eps of style entry j / content entry i (mse: -1)
 float content_eps_of(const st_plan* p, int i);
 int alloc_kind_of(const st_plan* p, int j);    // what ensure_style_alloc is asked for entry j: its kind, 2 for a diagonal W2 entry, 3 for a marginal one, 4 for a nearest one

@@ -67,6 +67,12 @@
 // tap's pixels against the style's feature vectors, reduced to one match per pixel without ever being written - and the finish
 // pass, which writes dF = w (2 / (C N)) (f - s_k*) to the seed buffer and keeps the matches (st_plan_nearest_indices).  Such an
 // entry takes no style mask and no regions either.
+//
+// So does a W2 entry flagged sliced (st_plan_set_style_sliced, st_sliced.hip): with resampling on its head draws new unit
+// directions at the plan's epoch and derives the target again from the stored style vectors - project, sort, resample, blend - and
+// in either case projects the tap, sorts and takes the residual on P rows and writes dF = R^T G to the seed buffer through the
+// 1x1 step.  The epoch is a host counter, advanced at the end of every evaluation of this closure (it is never captured).  Such an
+// entry takes no style mask and no regions either.
 #include <algorithm>
 #include <cmath>
 
@@ -128,6 +134,11 @@ static bool any_nearest(const st_plan* p) {
     for (int j = 0; j < p->n_style; ++j) any = any || p->style_near[j] != 0;
     return any;
 }
+static bool any_sliced(const st_plan* p) {
+    bool any = false;
+    for (int j = 0; j < p->n_style; ++j) any = any || p->style_sliced[j] != 0;
+    return any;
+}
 static bool default_eps(const st_plan* p) {
     bool ok = true;
     for (int i = 0; i < p->n_content; ++i) ok = ok && p->content_eps[i] < 0.f;
@@ -139,7 +150,7 @@ bool general_taps(const st_plan* p) {
     static Option force("ST_GENERAL_TAPS", 0);
     return !p->strip && (!p->reference_taps || !default_kinds(p) || !default_eps(p) || p->style_mask || p->n_regions > 0 ||
                          p->content_mask || p->tv_mask || p->n_lap > 0 || any_diagonal(p) || any_marginal(p) || any_nearest(p) ||
-                         force.get() != 0);
+                         any_sliced(p) || force.get() != 0);
 }
 
 float style_eps_of(const st_plan* p, int j) {
@@ -170,6 +181,28 @@ bool targets_ready(const st_plan* p) {
 
 // the reference's configuration: the 8-float array IS the terms in SumLoss order, whichever closure runs
 float* loss_terms(st_plan* p) { return p->reference_taps ? p->losses : p->terms; }
+
+int sliced_projections_of(const st_plan* p, int j) { return p->sliced_proj[j] ? p->sliced_proj[j] : p->head[p->style_op[j]].n; }
+
+// flagged entry j's directions at `epoch` and its target from the stored style vectors: per image project, sort, unpack, resample
+// to the tap's N, and blend in image order
+int sliced_refresh(st_plan* p, int j, unsigned long long epoch, hipStream_t s) {
+    StyleHead& h = p->head[p->style_op[j]];
+    const int proj = sliced_projections_of(p, j);
+    const bool f16 = p->net->conv_elem == 1;
+    if (launch_sliced_directions(p->sliced_seed, j, epoch, proj, h.n, h.sl_r, h.sl_rt, s)) return 1;
+    h.sl_epoch = epoch;
+    const SlicedScratch sc = sliced_scratch_of(h.sl_scratch, proj, h.sl_rows);
+    const unsigned int* bounds = reinterpret_cast<const unsigned int*>(h.sl_bounds);
+    const float* feat = h.sl_feats;
+    for (int i = 0; i < h.sl_images; ++i) {
+        if (sliced_target_add(feat, h.n, h.sl_m[i], h.sl_r, h.sl_rt, proj, h.npix_local, sc, f16 ? bounds + (size_t)(1 + i) * kAmaxWordUints : nullptr,
+                              f16 ? bounds : nullptr, h.sl_t, i > 0, h.sl_a[i], s))
+            return 1;
+        feat += (size_t)h.n * (size_t)h.sl_m[i];
+    }
+    return 0;
+}
 
 namespace {
 
@@ -239,6 +272,21 @@ int nearest_head(st_plan* p, const HeadSite& at, float* seed, hipStream_t s) {
     return nearest_head_run(at.tap->y, h.n, h.npix_local, pr, sc, bound, at.weight, h.near_idx, nullptr, seed, at.loss, s);
 }
 
+// A W2 entry flagged sliced (st_plan_set_style_sliced, st_sliced.hip).  Resampling on: the directions of the plan's epoch and the
+// target from the stored style vectors, image by image in image order.  Then the head.  No mask, no eps.  fp16x3 trunks: both
+// products in fp16x3 under the tap's bound word, R's (1 by construction), each image's (measured by the setter) and G's (measured
+// here); an fp32 trunk: the exact fp32 MFMA.
+int sliced_head(st_plan* p, int j, const HeadSite& at, float* seed, hipStream_t s) {
+    StyleHead& h = *at.h;
+    const int proj = sliced_projections_of(p, j);
+    const bool f16 = p->net->conv_elem == 1;
+    if (p->sliced_resample[j] && sliced_refresh(p, j, p->sliced_epoch, s)) return 1;
+    const SlicedScratch sc = sliced_scratch_of(h.sl_scratch, proj, h.sl_rows);
+    const unsigned int* rb = reinterpret_cast<const unsigned int*>(h.sl_bounds);
+    return sliced_head_run(at.tap->y, h.n, h.npix_local, h.sl_r, h.sl_rt, proj, h.sl_t, sc, f16 ? at.tap->y_amax : nullptr,
+                           f16 ? rb : nullptr, at.weight, seed, at.loss, s);
+}
+
 // Style regions in force: the heads of every listed entry, in `order`, one per region in region order.  dF_r's pixel columns
 // times m_r: region 0 in place on the seed it wrote (the masked plan's launches), region r >= 1 from the scratch buffer ONTO the
 // seed.  Then each entry's term from its regions' terms.
@@ -253,6 +301,7 @@ int region_heads(st_plan* p, const int* order, bool* styled, hipStream_t s) {
             const HeadSite at = region_head_site(p, j, r);
             ST_REQUIRE(!p->style_marg[j], "style layer %d is flagged marginal (st_plan_set_w2_marginal): it takes no style regions", j);
             ST_REQUIRE(!p->style_near[j], "style layer %d is flagged nearest (st_plan_set_style_nearest): it takes no style regions", j);
+            ST_REQUIRE(!p->style_sliced[j], "style layer %d is flagged sliced (st_plan_set_style_sliced): it takes no style regions", j);
             if (p->style_diag[j]) {            // region 0 writes the seed, region r >= 1 adds onto it: no scratch buffer
                 if (diag_head(p, at, seed, r > 0, s)) return 1;
                 continue;
@@ -319,6 +368,11 @@ int general_loss_and_grad(st_plan* p, const float* image, float* grad_out, float
     } else {
         for (int k = 0; k < ns; ++k) {
             const HeadSite at = general_head_site(p, order[k]);
+            if (p->style_sliced[order[k]]) {
+                if (sliced_head(p, order[k], at, at.grad, s)) return 1;
+                styled[p->style_op[order[k]]] = true;
+                continue;
+            }
             if (p->style_near[order[k]]) {
                 if (nearest_head(p, at, at.grad, s)) return 1;
                 styled[p->style_op[order[k]]] = true;
@@ -399,6 +453,12 @@ int general_loss_and_grad(st_plan* p, const float* image, float* grad_out, float
         // (a step's tail sums the 8-float array once more - the same additions - and fills losses_out)
         return 1;
     }
+    // sliced heads that resample: the next closure draws its directions at the next epoch
+    for (int j = 0, bump = 1; j < ns; ++j)
+        if (bump && p->style_sliced[j] && p->sliced_resample[j]) {
+            ++p->sliced_epoch;
+            bump = 0;
+        }
     const float* seed[kNumOps] = {};
     for (int i = 0; i < nc; ++i) seed[p->content_op[i]] = p->tap_seed[p->content_op[i]];
     for (int j = 0; j < ns; ++j) seed[p->style_op[j]] = p->tap_seed[p->style_op[j]];
@@ -460,7 +520,7 @@ int st_plan_set_taps(st_plan* p, int n_content, const int* content_layers, int n
         p->content_kind[i] = ckind;
         p->style_kind[i] = skind;
         p->content_eps[i] = p->style_eps[i] = -1.f;
-        p->style_diag[i] = p->style_marg[i] = p->style_near[i] = 0;
+        p->style_diag[i] = p->style_marg[i] = p->style_near[i] = p->style_sliced[i] = 0;
         if (keep_weights) continue;
         p->content_weight[i] = i < n_content ? 0.015f / (float)n_content : 0.f;
         p->style_weight[i] = i >= n_style ? 0.f : ref ? kStyleWeight[i] : 1.f / (float)n_style;
@@ -483,7 +543,7 @@ int apply_loss_kinds(st_plan* p, const int* ck, const int* sk) {
         p->content_kind[i] = ck[i];
         p->style_kind[i] = sk[i];
         p->content_eps[i] = p->style_eps[i] = -1.f;      // an eps belongs to a module of one kind: set it after the kinds
-        p->style_diag[i] = p->style_marg[i] = p->style_near[i] = 0;      // ... and so do the diagonal, marginal and nearest flags of a W2 entry
+        p->style_diag[i] = p->style_marg[i] = p->style_near[i] = p->style_sliced[i] = 0;      // ... and so do the diagonal, marginal, nearest and sliced flags of a W2 entry
     }
     // a target is kept in the form its kind reads (a root, or a Gram matrix): as after st_plan_set_taps, every target set
     // before is gone, every bound word is dealt again and nothing built on the former terms survives.  The lists and all
@@ -580,6 +640,9 @@ int st_plan_set_loss_eps(st_plan* p, const float* content_eps, const float* styl
     for (int j = 0; j < p->n_style; ++j)
         ST_REQUIRE(!p->style_near[j] || se[j] < 0.f,
                    "st_plan_set_loss_eps: style layer %d is flagged nearest (st_plan_set_style_nearest), whose term has no eps", j);
+    for (int j = 0; j < p->n_style; ++j)
+        ST_REQUIRE(!p->style_sliced[j] || se[j] < 0.f,
+                   "st_plan_set_loss_eps: style layer %d is flagged sliced (st_plan_set_style_sliced), whose term has no eps", j);
     std::copy(ce, ce + 16, p->content_eps);
     std::copy(se, se + 16, p->style_eps);
     // a W2 target is kept as the root of cov_t + eps I: every target set before is gone
@@ -599,6 +662,8 @@ int st_plan_set_w2_diagonal(st_plan* p, const int* flags) {
                    "st_plan_set_w2_diagonal: style layer %d is flagged marginal (st_plan_set_w2_marginal): a layer takes one of the two", j);
         ST_REQUIRE(flags[j] == 0 || !p->style_near[j],
                    "st_plan_set_w2_diagonal: style layer %d is flagged nearest (st_plan_set_style_nearest): a layer takes one of the two", j);
+        ST_REQUIRE(flags[j] == 0 || !p->style_sliced[j],
+                   "st_plan_set_w2_diagonal: style layer %d is flagged sliced (st_plan_set_style_sliced): a layer takes one of the two", j);
         fl[j] = flags[j];
         any = any || fl[j] != 0;
     }
@@ -633,6 +698,8 @@ int st_plan_set_w2_marginal(st_plan* p, const int* flags) {
                    "st_plan_set_w2_marginal: style layer %d has a custom eps (st_plan_set_loss_eps); the marginal term has no eps", j);
         ST_REQUIRE(flags[j] == 0 || !p->style_near[j],
                    "st_plan_set_w2_marginal: style layer %d is flagged nearest (st_plan_set_style_nearest): a layer takes one of the two", j);
+        ST_REQUIRE(flags[j] == 0 || !p->style_sliced[j],
+                   "st_plan_set_w2_marginal: style layer %d is flagged sliced (st_plan_set_style_sliced): a layer takes one of the two", j);
         fl[j] = flags[j];
         any = any || fl[j] != 0;
     }
@@ -664,6 +731,8 @@ int st_plan_set_style_nearest(st_plan* p, const int* flags) {
                    "st_plan_set_style_nearest: style layer %d is flagged diagonal (st_plan_set_w2_diagonal): a layer takes one of the two", j);
         ST_REQUIRE(flags[j] == 0 || !p->style_marg[j],
                    "st_plan_set_style_nearest: style layer %d is flagged marginal (st_plan_set_w2_marginal): a layer takes one of the two", j);
+        ST_REQUIRE(flags[j] == 0 || !p->style_sliced[j],
+                   "st_plan_set_style_nearest: style layer %d is flagged sliced (st_plan_set_style_sliced): a layer takes one of the two", j);
         ST_REQUIRE(flags[j] == 0 || p->style_eps[j] < 0.f,
                    "st_plan_set_style_nearest: style layer %d has a custom eps (st_plan_set_loss_eps); the nearest term has no eps", j);
         ST_REQUIRE(flags[j] == 0 || p->head[p->style_op[j]].n % kNearestChunk == 0,
@@ -684,6 +753,73 @@ int st_plan_set_style_nearest(st_plan* p, const int* flags) {
 int st_plan_style_nearest(const st_plan* p, int* flags) {
     ST_REQUIRE(p && flags, "st_plan_style_nearest: null argument");
     for (int j = 0; j < p->n_style; ++j) flags[j] = p->style_near[j];
+    return 0;
+}
+
+int st_plan_set_style_sliced(st_plan* p, const int* flags) {
+    ST_REQUIRE(p, "st_plan_set_style_sliced: null plan");
+    int fl[16] = {};
+    bool any = false;
+    for (int j = 0; flags && j < p->n_style; ++j) {
+        ST_REQUIRE(flags[j] == 0 || flags[j] == 1, "st_plan_set_style_sliced: flag %d of style layer %d: 0 or 1", flags[j], j);
+        ST_REQUIRE(flags[j] == 0 || p->style_kind[j] == 0,
+                   "st_plan_set_style_sliced: style layer %d is of kind gram (StyleLoss): only a w2 layer can be matched on sliced projections", j);
+        ST_REQUIRE(flags[j] == 0 || !p->style_diag[j],
+                   "st_plan_set_style_sliced: style layer %d is flagged diagonal (st_plan_set_w2_diagonal): a layer takes one of the two", j);
+        ST_REQUIRE(flags[j] == 0 || !p->style_marg[j],
+                   "st_plan_set_style_sliced: style layer %d is flagged marginal (st_plan_set_w2_marginal): a layer takes one of the two", j);
+        ST_REQUIRE(flags[j] == 0 || !p->style_near[j],
+                   "st_plan_set_style_sliced: style layer %d is flagged nearest (st_plan_set_style_nearest): a layer takes one of the two", j);
+        ST_REQUIRE(flags[j] == 0 || p->style_eps[j] < 0.f,
+                   "st_plan_set_style_sliced: style layer %d has a custom eps (st_plan_set_loss_eps); the sliced term has no eps", j);
+        ST_REQUIRE(flags[j] == 0 || p->head[p->style_op[j]].n % 64 == 0,
+                   "st_plan_set_style_sliced: style layer %d has %d channels: a multiple of 64", j, p->head[p->style_op[j]].n);
+        fl[j] = flags[j];
+        any = any || fl[j] != 0;
+    }
+    ST_REQUIRE(!p->strip || !any, "st_plan_set_style_sliced: strip plans run full W2 heads only");
+    ST_REQUIRE(!any || (!p->style_mask && !p->n_regions),
+               "st_plan_set_style_sliced: a style mask (st_plan_set_style_mask) or style regions (st_plan_set_style_regions) are in force "
+               "on this plan; weighted quantiles are not implemented - clear them first");
+    std::copy(fl, fl + 16, p->style_sliced);
+    // the options return to their defaults - C projections, new directions at every closure - and the epoch to 0
+    for (int j = 0; j < 16; ++j) {
+        p->sliced_proj[j] = 0;
+        p->sliced_resample[j] = fl[j];
+    }
+    p->sliced_epoch = 0;
+    // a target is kept in the form its head reads - stored style vectors, or a root: every target set before is gone
+    drop_targets(p);
+    return 0;
+}
+
+int st_plan_style_sliced(const st_plan* p, int* flags) {
+    ST_REQUIRE(p && flags, "st_plan_style_sliced: null argument");
+    for (int j = 0; j < p->n_style; ++j) flags[j] = p->style_sliced[j];
+    return 0;
+}
+
+int st_plan_set_sliced_options(st_plan* p, int index, int projections, int resample) {
+    ST_REQUIRE(p, "st_plan_set_sliced_options: null plan");
+    ST_REQUIRE(index >= 0 && index < p->n_style, "st_plan_set_sliced_options: index %d out of range (%d style layers)", index, p->n_style);
+    ST_REQUIRE(p->style_sliced[index], "st_plan_set_sliced_options: style layer %d is not flagged sliced (st_plan_set_style_sliced)", index);
+    ST_REQUIRE(projections == 0 || (projections >= 64 && projections <= 512 && projections % 64 == 0),
+               "st_plan_set_sliced_options: %d projections: 0 (the tap's channels) or a multiple of 64 in [64, 512]", projections);
+    ST_REQUIRE(resample == 0 || resample == 1, "st_plan_set_sliced_options: resample %d: 0 or 1", resample);
+    p->sliced_proj[index] = projections;
+    p->sliced_resample[index] = resample;
+    p->head[p->style_op[index]].target_set = false;     // T is [P][N] for the former P, derived under the former rule
+    invalidate_graph(p);
+    return 0;
+}
+
+int st_plan_set_sliced_seed(st_plan* p, unsigned long long seed) {
+    ST_REQUIRE(p, "st_plan_set_sliced_seed: null plan");
+    p->sliced_seed = seed;
+    p->sliced_epoch = 0;
+    // directions and targets drawn under the former seed are gone: set the seed before the style vectors
+    for (int j = 0; j < p->n_style; ++j)
+        if (p->style_sliced[j]) p->head[p->style_op[j]].target_set = false;
     return 0;
 }
 

@@ -97,6 +97,13 @@ def _declare(lib):
         'st_plan_style_nearest': (i32, [vp, ctypes.POINTER(i32)]),
         'st_plan_set_style_vectors': (i32, [vp, i32, vp, i64, vp]),
         'st_plan_nearest_indices': (i32, [vp, i32, pp, ctypes.POINTER(i64)]),
+        'st_plan_set_style_sliced': (i32, [vp, ctypes.POINTER(i32)]),
+        'st_plan_style_sliced': (i32, [vp, ctypes.POINTER(i32)]),
+        'st_plan_set_sliced_options': (i32, [vp, i32, i32, i32]),
+        'st_plan_set_sliced_seed': (i32, [vp, ctypes.c_ulonglong]),
+        'st_plan_set_style_sliced_vectors': (i32, [vp, i32, i32, pp, ctypes.POINTER(i64), ctypes.POINTER(f32), vp]),
+        'st_plan_sliced_directions': (i32, [vp, i32, pp, ip, ip, ctypes.POINTER(ctypes.c_ulonglong)]),
+        'st_plan_sliced_target': (i32, [vp, i32, pp, ip, ctypes.POINTER(i64)]),
         'st_plan_set_content_target_at': (i32, [vp, i32, vp, vp]),
         'st_plan_term_losses': (i32, [vp, pp, ip]),
         'st_plan_loss_and_grad': (i32, [vp, vp, vp, vp, vp]),
@@ -179,6 +186,12 @@ def _declare(lib):
         'st_op_nearest_search': (i32, [vp, i32, i64, vp, i64, vp, vp, vp, vp]),
         'st_op_nearest_loss': (i32, [vp, i32, i64, vp, i64, vp, vp, vp, vp, vp]),
         'st_op_nearest_loss_backward': (i32, [vp, i64, vp, vp, vp]),
+        'st_op_sliced_directions': (i32, [ctypes.c_ulonglong, i32, ctypes.c_ulonglong, i32, i32, vp, vp, vp]),
+        'st_op_sliced_scratch_bytes': (i64, [i32, i32, i64]),
+        'st_op_sliced_target': (i32, [vp, i32, i64, vp, vp, i32, i64, vp, vp, i32, f32, vp]),
+        'st_op_sliced_project': (i32, [vp, i32, i64, vp, vp, i32, vp, vp, vp]),
+        'st_op_sliced_loss': (i32, [vp, i32, i64, vp, vp, i32, vp, vp, vp, vp, vp]),
+        'st_op_sliced_loss_backward': (i32, [vp, i64, vp, vp, vp]),
         'st_op_tv_value': (i32, [vp, i32, i32, vp, vp, vp]),
         'st_op_tv_loss_backward': (i32, [vp, i32, i32, vp, vp, vp]),
         'st_op_laplacian_scratch_floats': (i64, [i32, i32, i32, i32]),
@@ -499,6 +512,47 @@ class Plan:
         _check(self.lib.st_plan_style_nearest(self.handle, fa))
         return tuple(bool(v) for v in fa[:n])
 
+    def set_style_sliced(self, flags=None):
+        """Match a 'w2' style layer on sliced projections (st_plan_set_style_sliced): None or False (no layer), True (every
+        layer of the list - all must be 'w2') or a sequence with one bool per style layer.  A flagged layer's term is the mean
+        over P random unit directions and ranks of ``(sort(R f) - T)^2`` with ``T`` the blended quantile functions of the
+        style's projected feature vectors (``set_style_sliced_vectors``), new directions at every closure: the sliced
+        Wasserstein loss.  Any set flag runs the general closure; drops every target and returns the options
+        (``set_sliced_options``) to their defaults.  Refused together with a diagonal, marginal or nearest flag or a custom
+        eps on the same layer, and while a style mask or regions are set.  Either kinds setter and ``set_taps`` clear the
+        flags: kinds, eps, diagonal, marginal, nearest, then this, its options and seed, then the weights and targets."""
+        n = len(self.style_layers)
+        if flags is None or isinstance(flags, (bool, int)):
+            flags = [bool(flags)] * n
+        flags = list(flags)
+        if len(flags) != n:
+            raise ValueError(f'{len(flags)} sliced flags for {n} style layers: one per layer')
+        for v in flags:
+            if v not in (0, 1, False, True):
+                raise ValueError(f'sliced flag {v!r}: must be a bool')
+        fa = (ctypes.c_int * max(n, 1))(*[int(v) for v in flags])
+        with torch.cuda.device(self.device):
+            _check(self.lib.st_plan_set_style_sliced(self.handle, fa))
+
+    @property
+    def style_sliced(self):
+        """The sliced flag of each style layer, a tuple of bools (st_plan_style_sliced)."""
+        n = len(self.style_layers)
+        fa = (ctypes.c_int * max(n, 1))()
+        _check(self.lib.st_plan_style_sliced(self.handle, fa))
+        return tuple(bool(v) for v in fa[:n])
+
+    def set_sliced_options(self, index, projections=None, resample=True):
+        """Flagged style entry ``index``: the number of directions (None or 0: the tap's channels; else a multiple of 64 in
+        [64, 512]) and whether every closure draws new ones (st_plan_set_sliced_options).  Drops that entry's target."""
+        with torch.cuda.device(self.device):
+            _check(self.lib.st_plan_set_sliced_options(self.handle, int(index), int(projections or 0), int(bool(resample))))
+
+    def set_sliced_seed(self, seed):
+        """The seed of the flagged entries' directions; the epoch returns to 0 and their targets are dropped
+        (st_plan_set_sliced_seed): set it before the style vectors."""
+        _check(self.lib.st_plan_set_sliced_seed(self.handle, int(seed) & 0xffffffffffffffff))
+
     def _layer_values(self, entry, ctype):
         ca, sa = (ctype * max(len(self.content_layers), 1))(), (ctype * max(len(self.style_layers), 1))()
         _check(entry(self.handle, ca, sa))
@@ -668,6 +722,55 @@ class Plan:
         with torch.cuda.device(self.device):
             _copy_d2d(out, data.value)
         return out.to(torch.int64)
+
+    def set_style_sliced_vectors(self, index, vectors, weights=None):
+        """The target of a style layer flagged by ``set_style_sliced``: ``vectors`` is one [C, M] (or [C, h, w]) tensor or a
+        sequence of them, one per style image - each a style tap (``feature(layer)[0]``) - and ``weights`` one non-negative
+        number per image (None: equal).  The plan keeps the vectors and derives the target from them under the directions of
+        every epoch (st_plan_set_style_sliced_vectors).  M need not be this plan's pixel count."""
+        if torch.is_tensor(vectors):
+            vectors = [vectors]
+        kept = []
+        for v in vectors:
+            v = v.to(device=self.device, dtype=torch.float32)
+            if v.ndim == 3:
+                v = v.flatten(1)
+            if v.ndim != 2:
+                raise ValueError(f'style vectors of shape {tuple(v.shape)}: [C, M]')
+            kept.append(v.contiguous())
+        n = len(kept)
+        if weights is not None and len(weights) != n:
+            raise ValueError(f'{len(weights)} weights for {n} style images: one per image')
+        pa = (ctypes.c_void_p * max(n, 1))(*[v.data_ptr() for v in kept])
+        ma = (ctypes.c_longlong * max(n, 1))(*[int(v.shape[1]) for v in kept])
+        wa = (ctypes.c_float * max(n, 1))(*[float(w) for w in weights]) if weights is not None else None
+        with torch.cuda.device(self.device):
+            _check(self.lib.st_plan_set_style_sliced_vectors(self.handle, int(index), n, pa, ma, wa, _stream()))
+
+    def _sliced_index(self, layer):
+        if int(layer) not in self.style_layers:
+            raise ValueError(f'features[{int(layer)}] is not one of the style layers {tuple(self.style_layers)}')
+        return list(self.style_layers).index(int(layer))
+
+    def sliced_directions(self, layer):
+        """(copy of the directions R [P, C] the last closure used for the flagged style layer ``layer`` - a features index of
+        ``style_layers``; before any closure those the setter drew - and their epoch) - st_plan_sliced_directions."""
+        data, proj, c, epoch = ctypes.c_void_p(), ctypes.c_int(), ctypes.c_int(), ctypes.c_ulonglong()
+        _check(self.lib.st_plan_sliced_directions(self.handle, self._sliced_index(layer), ctypes.byref(data), ctypes.byref(proj),
+                                                  ctypes.byref(c), ctypes.byref(epoch)))
+        out = torch.empty((proj.value, c.value), device=self.device, dtype=torch.float32)
+        with torch.cuda.device(self.device):
+            _copy_d2d(out, data.value)
+        return out, int(epoch.value)
+
+    def sliced_target(self, layer):
+        """Copy of the flagged style layer's target under those directions, [P, N] (st_plan_sliced_target)."""
+        data, proj, n = ctypes.c_void_p(), ctypes.c_int(), ctypes.c_longlong()
+        _check(self.lib.st_plan_sliced_target(self.handle, self._sliced_index(layer), ctypes.byref(data), ctypes.byref(proj), ctypes.byref(n)))
+        out = torch.empty((proj.value, n.value), device=self.device, dtype=torch.float32)
+        with torch.cuda.device(self.device):
+            _copy_d2d(out, data.value)
+        return out
 
     def set_style_mask(self, mask):
         """A spatial mask for the style statistics (st_plan_set_style_mask): a [height, width] tensor with values in [0, 1]
@@ -1537,6 +1640,74 @@ def op_nearest_loss_backward(unit_grad, upstream):
     grad = torch.empty(unit_grad.shape, device=unit_grad.device, dtype=torch.float32)
     with torch.cuda.device(unit_grad.device):
         _check(lib.st_op_nearest_loss_backward(_ptr(unit_grad), unit_grad.numel(), _ptr(upstream), _ptr(grad), _stream()))
+    return grad
+
+
+def op_sliced_directions(seed, entry, epoch, projections, channels, device='cuda'):
+    """(R [P, C], R^T [C, P]): P unit directions of (seed, entry, epoch) from the device generator (st_op_sliced_directions)."""
+    lib = load_library()
+    device = torch.device(device)
+    r = torch.empty((int(projections), int(channels)), device=device, dtype=torch.float32)
+    rt = torch.empty((int(channels), int(projections)), device=device, dtype=torch.float32)
+    with torch.cuda.device(device):
+        _check(lib.st_op_sliced_directions(int(seed) & 0xffffffffffffffff, int(entry), int(epoch) & 0xffffffffffffffff, int(projections),
+                                           int(channels), _ptr(r), _ptr(rt), _stream()))
+    return r, rt
+
+
+def _sliced_scratch(x, c, p, n):
+    nbytes = int(load_library().st_op_sliced_scratch_bytes(c, p, n))
+    return torch.empty(max(nbytes, 16), device=x.device, dtype=torch.uint8)
+
+
+def op_sliced_target(vectors, r, rt, n_out, target=None, weight=1.0):
+    """One style image's share of a sliced target (st_op_sliced_target): ``weight`` times the quantile functions of the rows of
+    ``r @ vectors`` ([C, M] -> [P, M]) at n_out midpoints, written to a new [P, n_out] tensor or, with ``target``, added onto it."""
+    lib = load_library()
+    c, m = int(vectors.shape[0]), int(vectors.shape[1])
+    p = int(r.shape[0])
+    scratch = _sliced_scratch(vectors, c, p, max(m, int(n_out)))
+    accumulate = target is not None
+    if target is None:
+        target = torch.empty((p, int(n_out)), device=vectors.device, dtype=torch.float32)
+    with torch.cuda.device(vectors.device):
+        _check(lib.st_op_sliced_target(_ptr(vectors), c, m, _ptr(r), _ptr(rt), p, int(n_out), ctypes.c_void_p(scratch.data_ptr()),
+                                       _ptr(target), int(accumulate), float(weight), _stream()))
+    return target
+
+
+def op_sliced_project(x, r, rt):
+    """Y [P, N] = r @ x as ``op_sliced_loss`` computes and sorts it, bit for bit (st_op_sliced_project)."""
+    lib = load_library()
+    c, n = _rows(x)
+    p = int(r.shape[0])
+    scratch = _sliced_scratch(x, c, p, n)
+    y = torch.empty((p, n), device=x.device, dtype=torch.float32)
+    with torch.cuda.device(x.device):
+        _check(lib.st_op_sliced_project(_ptr(x), c, n, _ptr(r), _ptr(rt), p, ctypes.c_void_p(scratch.data_ptr()), _ptr(y), _stream()))
+    return y
+
+
+def op_sliced_loss(x, r, rt, target):
+    """(the sliced Wasserstein loss [0-dim], its gradient at weight 1, shaped like x) - st_op_sliced_loss; x a [C, N] matrix or a
+    [..., C, h, w] tensor (one image), r [P, C], rt [C, P], target [P, N]."""
+    lib = load_library()
+    c, n = _rows(x)
+    p = int(r.shape[0])
+    scratch = _sliced_scratch(x, c, p, n)
+    loss = torch.empty((), device=x.device, dtype=torch.float32)
+    unit = torch.empty(x.shape, device=x.device, dtype=torch.float32)
+    with torch.cuda.device(x.device):
+        _check(lib.st_op_sliced_loss(_ptr(x), c, n, _ptr(r), _ptr(rt), p, _ptr(target), ctypes.c_void_p(scratch.data_ptr()), _ptr(unit),
+                                     _ptr(loss), _stream()))
+    return loss, unit
+
+
+def op_sliced_loss_backward(unit_grad, upstream):
+    lib = load_library()
+    grad = torch.empty(unit_grad.shape, device=unit_grad.device, dtype=torch.float32)
+    with torch.cuda.device(unit_grad.device):
+        _check(lib.st_op_sliced_loss_backward(_ptr(unit_grad), unit_grad.numel(), _ptr(upstream), _ptr(grad), _stream()))
     return grad
 
 

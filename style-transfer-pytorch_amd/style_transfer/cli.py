@@ -322,6 +322,22 @@ def build_parser():
     p.add_argument('--style-nearest-samples', type=_positive_int, default=None, metavar='INT',
                    help='keep at most INT evenly spaced feature vectors of every style image per --style-nearest layer (the '
                         'search costs 2 C N M flop per iteration: this is what makes a shallow layer affordable; default: all)')
+    p.add_argument('--style-sliced', type=_diagonal_flags, default=False, metavar='{0,1}[,...]',
+                   help="match the 'w2' style layers on sliced projections (the sliced Wasserstein loss: the sorted projections "
+                        "of the iterate's features onto random unit directions against the style's, new directions at every "
+                        "step): 1 for every 'w2' layer, or a comma-separated list with one flag per style layer, e.g. "
+                        "'0,0,0,1,1' (default 0); not together with --style-diagonal, --style-marginal or --style-nearest on the "
+                        "same layer, style masks or regions")
+    p.add_argument('--style-sliced-projections', type=_positive_int, default=None, metavar='INT',
+                   help='directions per --style-sliced layer: a multiple of 64 in [64, 512] (default: the layer\'s channel count)')
+    p.add_argument('--no-style-sliced-resample', dest='style_sliced_resample', action='store_false', default=True,
+                   help="keep the directions of the first step throughout instead of drawing new ones at every step (one fixed "
+                        "objective: needed with --optimizer lbfgs)")
+    p.add_argument('--style-sliced-seed', type=_seed_int, default=0, metavar='INT',
+                   help='seed of the --style-sliced directions (default 0): the same seed gives the same run')
+    p.add_argument('--style-sliced-samples', type=_positive_int, default=None, metavar='INT',
+                   help='keep at most INT evenly spaced feature vectors of every style image per --style-sliced layer (the style '
+                        'side is projected and sorted again at every step; default: all)')
     p.add_argument('--style-mask', type=str, default=None, metavar='PATH',
                    help='an image (read as greyscale, white = 1) saying which pixels of the output take the style; it is '
                         'resized to every scale')
@@ -373,8 +389,19 @@ def _positive_int(text):
     return value
 
 
+def _seed_int(text):
+    """argparse type of --style-sliced-seed: an int >= 0."""
+    try:
+        value = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f'{text!r}: an integer >= 0') from None
+    if value < 0:
+        raise argparse.ArgumentTypeError(f'{text!r}: an integer >= 0')
+    return value
+
+
 def _diagonal_flags(text):
-    """argparse type of --style-diagonal / --style-marginal / --style-nearest: one flag stays the bool, a comma-separated list becomes the list of bools."""
+    """argparse type of --style-diagonal / --style-marginal / --style-nearest / --style-sliced: one flag stays the bool, a comma-separated list becomes the list of bools."""
     items = text.split(',')
     for item in items:
         if item not in ('0', '1'):
@@ -434,12 +461,15 @@ def apply_style_masks(st, args):
 
 
 def apply_loss_kinds(st, args):
-    """--content-loss / --style-loss / --content-eps / --style-eps / --style-diagonal / --style-marginal / --style-nearest / --style-nearest-samples onto the StyleTransfer attributes that stylize() reads."""
+    """--content-loss / --style-loss / --content-eps / --style-eps / --style-diagonal / --style-marginal / --style-nearest / --style-nearest-samples / --style-sliced and its options onto the StyleTransfer attributes that stylize() reads."""
     st.content_loss, st.style_loss = args.content_loss, args.style_loss
     st.content_eps, st.style_eps = args.content_eps, args.style_eps
     st.style_diagonal = args.style_diagonal
     st.style_marginal = args.style_marginal
     st.style_nearest, st.style_nearest_samples = args.style_nearest, args.style_nearest_samples
+    st.style_sliced, st.style_sliced_projections = args.style_sliced, args.style_sliced_projections
+    st.style_sliced_resample, st.style_sliced_seed = args.style_sliced_resample, args.style_sliced_seed
+    st.style_sliced_samples = args.style_sliced_samples
     return st
 
 

@@ -16,6 +16,9 @@ sorted tap - one dense fp32 HIP tensor, any channel count, runs st_op_w2_margina
 ``StyleLossNearest`` is the module form of ``st_plan_set_style_nearest``'s term: every feature vector of the input against the
 closest of the style's feature vectors - one dense fp32 HIP tensor whose channel count is a multiple of 32 runs st_op_nearest_loss /
 st_op_nearest_loss_backward.
+``StyleLossSliced`` is the module form of ``st_plan_set_style_sliced``'s term: the sorted projections of the input onto random unit
+directions against the style's, new directions at every forward in training mode - one dense fp32 HIP tensor whose channel count is
+a multiple of 64 runs st_op_sliced_directions / st_op_sliced_target / st_op_sliced_loss / st_op_sliced_loss_backward.
 
 Native dispatch.  On an ELIGIBLE tensor (``eligible`` below: one dense fp32 tensor on a HIP device, batch 1 or absent, 64 /
 128 / 256 / 512 channels for the style modules, the module's buffers beside it in fp32) the five loss modules run in the
@@ -67,7 +70,7 @@ class native:
         native.enabled, native.precision = self._former
 
 
-# calls that went to the library, by kind ('w2', 'gram', 'mse', 'scaled_mse', 'tv', 'laplacian', 'w2_diag', 'w2_marginal', 'nearest', 'moments'): the native indicator of the
+# calls that went to the library, by kind ('w2', 'gram', 'mse', 'scaled_mse', 'tv', 'laplacian', 'w2_diag', 'w2_marginal', 'nearest', 'sliced', 'moments'): the native indicator of the
 # modules that hold no head
 native_calls = {}
 _prepared_sets = weakref.WeakKeyDictionary()       # StyleLossNearest module -> (target, version, its prepared style set), kept off the module as the heads are
@@ -116,6 +119,12 @@ def eligible(input, kind, buffers=()):
         # (a channel count that is a multiple of the search kernel's K chunk; buffers: none)
         if not (_one_dense_fp32(input, 3) and input.ndim in (3, 4) and input.shape[-3] >= 32 and input.shape[-3] % 32 == 0 and
                 input.shape[-2] * input.shape[-1] < 1 << 31):
+            return False
+        sizes = ()
+    elif kind == 'sliced':
+        # (a channel count that is a multiple of 64; buffers: none)
+        if not (_one_dense_fp32(input, 3) and input.ndim in (3, 4) and input.shape[-3] % 64 == 0 and
+                input.shape[-2] * input.shape[-1] < 1 << 24):
             return False
         sizes = ()
     elif kind == 'tv':
@@ -358,6 +367,30 @@ class _NearestLoss(torch.autograd.Function):
             return _torch_vjp(ctx.torch_forward, input, grad_output), None, None, None
         grad = _hip.op_nearest_loss_backward(unit, grad_output.contiguous())
         return grad.view(input.shape), None, None, None
+
+
+class _SlicedLoss(torch.autograd.Function):
+    """StyleLossSliced.forward: st_op_sliced_loss under the given directions; the gradient at weight 1 - the back-projection of
+    the residual, directions and permutations held constant - stays on the node for st_op_sliced_loss_backward."""
+
+    @staticmethod
+    def forward(ctx, input, module, r, rt, target):
+        from . import _hip
+        loss, unit = _hip.op_sliced_loss(_dense(input), r, rt, target)
+        _count('sliced')
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(input, unit)
+            ctx.torch_forward = lambda x: module._forward_torch(x, r)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        from . import _hip
+        input, unit = ctx.saved_tensors
+        if torch.is_grad_enabled():
+            return _torch_vjp(ctx.torch_forward, input, grad_output), None, None, None, None
+        grad = _hip.op_sliced_loss_backward(unit, grad_output.contiguous())
+        return grad.view(input.shape), None, None, None, None
 
 
 class _TVLoss(torch.autograd.Function):
@@ -738,6 +771,87 @@ class StyleLossNearest(nn.Module):
         matched = self.target.to(feat.dtype)[:, k]              # [C, ..., N]
         matched = matched.movedim(0, -2) if k.ndim > 1 else matched
         return torch.mean((feat - matched) ** 2)
+
+
+class StyleLossSliced(nn.Module):
+    """The sliced Wasserstein loss (Heitz et al., "A Sliced Wasserstein Loss for Neural Texture Synthesis"): the W2 distance
+    between the projections of the input's feature vectors and of a style tap's onto P random unit directions,
+    ``mean_p,k (sort(R f)_p,k - T_p,k)^2`` with ``T = resample_N(sort_rows(R S))`` - ``StyleLossW2Marginal`` along random axes
+    instead of the channel axes, so that over many forwards the whole C-dimensional distribution is matched.  Not in the
+    reference; include/st_amd.h (st_plan_set_style_sliced) fixes the semantics: the directions and the sort are constants of the
+    gradient, ties go by pixel index, there is no eps.  ``target`` = [C, M] (``get_target``), ``projections`` = P (None: C),
+    ``seed``; ``epoch`` counts the direction sets drawn: with ``resample`` every forward in training mode uses the directions of
+    the current epoch and advances it, otherwise (and in eval mode) the epoch stays.  ``directions``: None, or a [P, C] tensor to
+    use instead of generated ones (``R = I`` gives StyleLossW2Marginal's value).  The torch path serves any device, dtype and
+    batch, its directions drawn from a ``torch.Generator`` on the input's device; one dense fp32 HIP tensor whose channel count is
+    a multiple of 64, with P a multiple of 64 in [64, 512], runs in the library, directions from the device generator (the two
+    paths draw different, equally valid, directions)."""
+
+    def __init__(self, target, projections=None, resample=True, seed=0):
+        super().__init__()
+        if target.ndim != 2:
+            raise ValueError(f'target of shape {tuple(target.shape)}: [C, M], the style feature vectors as columns')
+        if projections is not None and (not isinstance(projections, int) or isinstance(projections, bool) or projections < 1):
+            raise ValueError(f'projections {projections!r}: None (the channel count), or an int >= 1')
+        self.register_buffer('target', target)
+        self.projections = int(projections) if projections is not None else int(target.shape[0])
+        self.resample = bool(resample)
+        self.seed = int(seed)
+        self.epoch = 0
+        self.directions = None
+
+    @staticmethod
+    def get_target(target):
+        """The flattened features, [..., C, h w]: every pixel's feature vector as a column."""
+        return target.flatten(-2)
+
+    def draw(self, epoch, device, dtype=torch.float32):
+        """The torch path's directions of ``epoch``: [P, C] standard normals from a generator on ``device`` seeded by (seed,
+        epoch), every row divided by its norm."""
+        gen = torch.Generator(device=device)
+        gen.manual_seed((self.seed * 0x9e3779b1 + int(epoch) * 0x85ebca6b + 1) % (1 << 63))
+        r = torch.randn((self.projections, self.target.shape[0]), generator=gen, device=device, dtype=torch.float32)
+        return (r / r.norm(dim=1, keepdim=True)).to(dtype)
+
+    def _native_ok(self, input):
+        p = self.projections if self.directions is None else int(self.directions.shape[0])
+        return (native.enabled and eligible(input, 'sliced') and self.target.shape[0] == input.shape[-3] and
+                not self.target.requires_grad and self.target.device == input.device and self.target.dtype == torch.float32 and
+                self.target.shape[1] < 1 << 24 and 64 <= p <= 512 and p % 64 == 0 and
+                (self.directions is None or (self.directions.device == input.device and self.directions.dtype == torch.float32 and
+                                             not self.directions.requires_grad)))
+
+    def forward(self, input):
+        epoch = self.epoch
+        if self.resample and self.training and self.directions is None:
+            self.epoch += 1
+        if self._native_ok(input):
+            from . import _hip
+            n = input.shape[-2] * input.shape[-1]
+            target = self.target
+            key = (epoch, n, target._version, None if self.directions is None else self.directions._version)
+            cached = self.__dict__.get('_sliced_cache')
+            if cached is None or cached[0] != key or cached[1] is not target or cached[2] is not self.directions:
+                if self.directions is None:
+                    r, rt = _hip.op_sliced_directions(self.seed, 0, epoch, self.projections, int(target.shape[0]), input.device)
+                else:
+                    r = self.directions.detach().contiguous()
+                    rt = r.t().contiguous()
+                t = _hip.op_sliced_target(target.contiguous(), r, rt, n)
+                cached = self.__dict__['_sliced_cache'] = (key, target, self.directions, r, rt, t)
+            return _SlicedLoss.apply(input, self, cached[3], cached[4], cached[5])
+        r = self.directions if self.directions is not None else self.draw(epoch, input.device, input.dtype)
+        return self._forward_torch(input, r)
+
+    def _forward_torch(self, input, r):
+        feat = input.flatten(-2)
+        r = r.to(feat.dtype)
+        n = feat.shape[-1]
+        with torch.no_grad():
+            q = torch.sort(r @ self.target.to(feat.dtype) + 0.0, dim=-1, stable=True).values
+            target = StyleLossW2Marginal.resample(q, n)
+        values = torch.sort(r @ feat + 0.0, dim=-1, stable=True).values
+        return torch.mean((values - target) ** 2)
 
 
 def _first_argmin(x, dim):

@@ -412,6 +412,68 @@ def _resolve_style_nearest(style_nearest, style_loss, style_diagonal=None, style
     return flags
 
 
+def _resolve_style_sliced(style_sliced, style_loss, style_diagonal=None, style_marginal=None, style_nearest=None, style_eps=None,
+                          masked=False, world=1, projections=None, samples=None, resample=True, seed=0, optimizer='adam'):
+    """``StyleTransfer.style_sliced`` as the fused closure takes it: one bool per entry of ``style_loss`` (the resolved kinds).
+    A bool means every 'w2' layer that is flagged neither diagonal, marginal nor nearest; a sequence holds one bool per entry
+    of style_layers.  ``style_diagonal`` / ``style_marginal`` / ``style_nearest`` / ``style_eps``: the resolved lists (one per
+    layer, eps None = default).  ``projections`` / ``samples`` / ``resample`` / ``seed``: ``StyleTransfer.style_sliced_projections``
+    / ``_samples`` / ``_resample`` / ``_seed``, checked here too.  Raises ``ValueError`` naming the attribute for a wrong length,
+    a value that is no bool, a true flag on a 'gram' layer, on a layer flagged diagonal, marginal or nearest or with a custom
+    eps, for any true flag together with style masks or regions (``masked``) or on several ranks, for projections that are
+    neither None nor a multiple of 64 in [64, 512], samples that are neither None nor an int >= 1, a resample that is no bool,
+    a seed that is no int >= 0, and for ``optimizer='lbfgs'`` with resampling on, before any device work."""
+    def is_int(value):
+        return isinstance(value, (int, np.integer)) and not isinstance(value, (bool, np.bool_))
+    if projections is not None and (not is_int(projections) or projections < 64 or projections > 512 or projections % 64):
+        raise ValueError(f'style_sliced_projections {projections!r}: None (the layer\'s channel count), or a multiple of 64 in [64, 512]')
+    if samples is not None and (not is_int(samples) or samples < 1):
+        raise ValueError(f'style_sliced_samples {samples!r}: None, or an int >= 1 (the style vectors kept per layer and image)')
+    if not isinstance(resample, (bool, np.bool_)):
+        raise ValueError(f'style_sliced_resample {resample!r}: a bool')
+    if not is_int(seed) or seed < 0 or seed >= 1 << 64:
+        raise ValueError(f'style_sliced_seed {seed!r}: an int in [0, 2^64)')
+    n = len(style_loss)
+    diagonal = list(style_diagonal) if style_diagonal is not None else [False] * n
+    marginal = list(style_marginal) if style_marginal is not None else [False] * n
+    nearest = list(style_nearest) if style_nearest is not None else [False] * n
+    epses = list(style_eps) if style_eps is not None else [None] * n
+    if isinstance(style_sliced, (bool, np.bool_)):
+        flags = [bool(style_sliced) and name == _hip.STYLE_LOSSES[0] and not diag and not marg and not near
+                 for name, diag, marg, near in zip(style_loss, diagonal, marginal, nearest)]
+    else:
+        if isinstance(style_sliced, str) or not isinstance(style_sliced, (list, tuple)):
+            raise ValueError(f'style_sliced {style_sliced!r}: give a bool, or a sequence with one bool per entry of style_layers')
+        flags = list(style_sliced)
+        if len(flags) != n:
+            raise ValueError(f'style_sliced {style_sliced!r}: {len(flags)} flags for {n} layers; give one bool, or exactly '
+                             'one per entry of style_layers')
+        for i, (flag, name) in enumerate(zip(flags, style_loss)):
+            if not isinstance(flag, (bool, np.bool_)) and flag not in (0, 1):
+                raise ValueError(f'style_sliced {style_sliced!r}: {flag!r} is not a bool')
+            if flag and name != _hip.STYLE_LOSSES[0]:
+                raise ValueError(f"style_sliced {style_sliced!r}: layer {i} has the loss {name!r} (StyleLoss on Gram "
+                                 "matrices); only a 'w2' layer can be matched on sliced projections")
+            for other, attr in ((diagonal, 'style_diagonal'), (marginal, 'style_marginal'), (nearest, 'style_nearest')):
+                if flag and other[i]:
+                    raise ValueError(f'style_sliced {style_sliced!r}: layer {i} is flagged in {attr} too; a layer takes one of the two')
+        flags = [bool(flag) for flag in flags]
+    for i, flag in enumerate(flags):
+        if flag and epses[i] is not None:
+            raise ValueError(f'style_sliced {style_sliced!r}: layer {i} has the custom style_eps {epses[i]!r}; the sliced '
+                             'term has no eps')
+    if masked and any(flags):
+        raise ValueError(f'style_sliced {style_sliced!r} together with style_mask, style_regions or style_image_masks: '
+                         'weighted quantiles are out of scope - clear one of them')
+    if world > 1 and any(flags):
+        raise ValueError(f'style_sliced {style_sliced!r} on {world} ranks: row strips run full W2 heads only; sliced '
+                         'heads are out of scope for strips - run them on one device')
+    if any(flags) and resample and optimizer == 'lbfgs':
+        raise ValueError("style_sliced with style_sliced_resample=True and optimizer='lbfgs': L-BFGS's history assumes one "
+                         'objective, and new directions at every evaluation change it - set style_sliced_resample = False')
+    return flags
+
+
 def _nearest_sample_columns(m, samples):
     """The columns of a style tap of m pixels that ``style_nearest_samples`` keeps: all of them, or ``floor(t m / K)``,
     t = 0 ... K - 1, when m > K."""
@@ -965,6 +1027,25 @@ class StyleTransfer:
     # per image and flagged layer.  This is what makes a shallow layer affordable: the search costs 2 C N M flop per iteration
     # (relu1_1 at 512^2 has N = M = 262144).
     style_nearest_samples = None
+    # 'w2' layers matched on sliced projections (_hip.Plan.set_style_sliced, losses.StyleLossSliced; the reference has none):
+    # the sliced Wasserstein loss of Heitz et al. - the W2 distance between the projections of the iterate's tap and of the
+    # style's feature vectors onto random unit directions, new directions at every optimiser step, so that over the run the whole
+    # C-dimensional distribution is matched, not two moments of it or its channel marginals.  False, True (every 'w2' layer) or
+    # a sequence with one bool per entry of style_layers.  Several style images blend as their projected quantile functions,
+    # by style_weights (per direction the Wasserstein barycentre); an image of weight 0 is left out.  Not together with
+    # style_diagonal, style_marginal, style_nearest or a custom style_eps on the same layer, nor with style masks or regions.
+    # One device only.
+    style_sliced = False
+    # None (as many directions as the layer has channels) or a multiple of 64 in [64, 512]: the directions per flagged layer.
+    style_sliced_projections = None
+    # True: new directions at every evaluation of the closure.  False: the directions of epoch 0 throughout, one fixed
+    # objective - what optimizer='lbfgs' needs, whose history assumes one.
+    style_sliced_resample = True
+    # the seed of the directions: the same seed and the same run give the same bits
+    style_sliced_seed = 0
+    # None, or an int K >= 1: when a style tap has more than K pixels the host keeps the columns floor(t M / K), t = 0 ... K - 1,
+    # per image and flagged layer (the style side is projected and sorted again at every step while resampling is on).
+    style_sliced_samples = None
     # Spatial masks for the style statistics (read by stylize() too; the reference has none).  style_mask: which pixels of the
     # OUTPUT take the style - a PIL image (read as 'L' / 255) or a 2-D numpy / torch array in [0, 1], resized bilinearly to
     # every scale; the style heads then take mask-weighted moments of the iterate's taps (_hip.Plan.set_style_mask).
@@ -1081,6 +1162,7 @@ class StyleTransfer:
         blends = [{} for _ in range(len(regions[0]) if regions else 1)]
         marginal, quantiles = plan.w2_marginal, {}      # (flagged layers: never with a mask or regions, _resolve_style_marginal)
         nearest, vectors = plan.style_nearest, {}       # (the same, _resolve_style_nearest)
+        sliced, sliced_taps = plan.style_sliced, {}     # (the same, _resolve_style_sliced): layer -> ([taps], [weights])
         for i, image in enumerate(style_images):
             blended = blends[region_of[i]]
             if style_size is None:
@@ -1101,6 +1183,18 @@ class StyleTransfer:
             if image_mask is not None:
                 splan.set_style_mask(_sized_mask(image_mask, sw, sh))
             for idx, layer in enumerate(style_layers):
+                if sliced[idx]:
+                    # a layer matched on sliced projections: the plan keeps every image's feature vectors, in image order with
+                    # the image's weight, and derives the target from them under each epoch's directions
+                    if style_weights[i] != 0:
+                        tap = splan.feature(layer)[0].flatten(1)
+                        columns = _nearest_sample_columns(tap.shape[1], self.style_sliced_samples)
+                        if len(columns) < tap.shape[1]:
+                            tap = tap[:, torch.tensor(columns, device=tap.device)]
+                        taps, weights = sliced_taps.setdefault(layer, ([], []))
+                        taps.append(tap.clone())
+                        weights.append(float(style_weights[i]))
+                    continue
                 if nearest[idx]:
                     # a layer matched on nearest vectors: the union of the images' feature vectors in image order, an image
                     # of weight 0 left out; the weights do not enter otherwise
@@ -1136,7 +1230,12 @@ class StyleTransfer:
             plan.set_region_weights(regions[2])
         for r, blended in enumerate(blends):
             for idx, layer in enumerate(style_layers):
-                if nearest[idx]:
+                if sliced[idx]:
+                    if layer not in sliced_taps:
+                        raise ValueError('style_sliced: every style image has weight 0; a flagged layer needs at least one '
+                                         'style image')
+                    plan.set_style_sliced_vectors(idx, *sliced_taps[layer])
+                elif nearest[idx]:
                     if layer not in vectors:
                         raise ValueError('style_nearest: every style image has weight 0; a flagged layer needs at least one '
                                          'style vector')
@@ -1296,6 +1395,12 @@ class StyleTransfer:
                                                masked=any(value is not None for value in (self.style_mask, self.style_regions,
                                                                                           self.style_image_masks)),
                                                world=max(len(self.devices), _dist_info()[1]), samples=self.style_nearest_samples)
+        style_sliced = _resolve_style_sliced(self.style_sliced, style_loss, style_diagonal, style_marginal, style_nearest, style_eps,
+                                             masked=any(value is not None for value in (self.style_mask, self.style_regions,
+                                                                                        self.style_image_masks)),
+                                             world=max(len(self.devices), _dist_info()[1]),
+                                             projections=self.style_sliced_projections, samples=self.style_sliced_samples,
+                                             resample=self.style_sliced_resample, seed=self.style_sliced_seed, optimizer=optimizer)
         content_map, tv_map = _resolve_weight_maps(self.content_mask, self.tv_mask,
                                                    world=max(len(self.devices), _dist_info()[1]))
         # (the smallest scale's image bounds the pool sizes; a weight of 0 has no term and no size to check)
@@ -1439,6 +1544,12 @@ class StyleTransfer:
                     plan.set_w2_marginal(style_marginal)
                 if any(style_nearest):
                     plan.set_style_nearest(style_nearest)
+                if any(style_sliced):
+                    plan.set_style_sliced(style_sliced)
+                    for idx, flag in enumerate(style_sliced):
+                        if flag:
+                            plan.set_sliced_options(idx, self.style_sliced_projections, bool(self.style_sliced_resample))
+                    plan.set_sliced_seed(int(self.style_sliced_seed))
                 self._build_targets(plan, content.to(device), style_images, style_weights, scale, style_scale_fac,
                                     style_size, style_mask, image_masks, regions)
                 # the content and TV maps at this scale's size, on the iterate's plan only and after the targets (which they
