@@ -12,7 +12,13 @@
  *     on that stream unless stated otherwise;
  *   - return value 0 = success, non-zero = failure with text available from st_last_error();
  *     no C++ exception crosses the boundary;
- *   - handles are opaque and owned by the caller (create/destroy pairs); not thread-safe per handle.
+ *   - handles are opaque and owned by the caller (create/destroy pairs); not thread-safe per handle;
+ *   - alignment: a tensor pointer need only be 4-byte aligned (a dense fp32 tensor: `batch[1]` of a [2][3][45][54] batch is 8
+ *     bytes past a 16-byte boundary) unless its entry says otherwise - the launchers take their 16-byte paths only when the
+ *     shape and every pointer of the launch allow them, and the scalar paths otherwise.  Where an entry demands more - the
+ *     standalone heads' feat / state / grad_feat, the L-BFGS state, the `scratch` of the sort, nearest and sliced entries
+ *     and the nearest entries' `prepared` - a pointer that violates it is refused (non-zero, st_last_error() names the
+ *     argument) before anything is launched or written.  tests/test_caller_buffers_gpu.py holds the entries to this.
  */
 #ifndef ST_AMD_H
 #define ST_AMD_H
@@ -641,6 +647,8 @@ int st_plan_apply_update(st_plan* plan, float* image, const float* grad, float* 
  * rows of the Gram matrix and |g|_1 are one contiguous block of 70 doubles at byte 192 of the state, |g|_inf the double
  * behind them: when the parameter is cut into strips their place is taken by an all-gather of per-rank records, summed in
  * rank order (st_qn_strip_* below).
+ * Alignment: `state` must be 16-byte aligned - st_lbfgs_reset, st_lbfgs_update, st_plan_lbfgs_step and the st_qn_strip_* entries
+ * refuse it otherwise; image, grad and ema_value may be merely 4-byte aligned (the scalar kernels then run).
  */
 long long st_lbfgs_state_bytes(long long count);
 int st_lbfgs_reset(void* state, long long count, void* stream);
@@ -887,7 +895,9 @@ int st_op_pool2x2_backward(const float* in, const float* grad_out, float* grad_i
  * The head owns its workspaces - Gram partials, the 1x1 step's split-K scratch, the scaled (Ssym, b) of a backward, the
  * reduction scratch and ticket of a Gram head, the covariance / chain matrices and Newton-Schulz workspace of a W2 head
  * (a Gram head allocates none of those) - allocated here, freed by st_head_destroy, counted by st_head_device_bytes.
- * Calls on one head are ordered by the stream they are given; a head serves one stream at a time. */
+ * Calls on one head are ordered by the stream they are given; a head serves one stream at a time.
+ * Alignment: feat, state and grad_feat must be 16-byte aligned (st_head_moments, st_head_forward and st_head_backward refuse
+ * them otherwise); mean_out, srm_out, loss_out, upstream and the targets may be merely 4-byte aligned. */
 typedef struct st_head st_head;
 int st_head_create(st_head** out, int kind, int channels, int height, int width, int precision);
 int st_head_destroy(st_head* head);
@@ -950,7 +960,9 @@ int st_op_w2_diag_loss_backward(const float* feat, int channels, long long npix,
  * st_op_sort_chunk(): the keys one workgroup sorts in LDS (a row of at most that many elements needs no merge pass).
  * `scratch`: st_op_sort_scratch_bytes(C, n) bytes of the caller's, 256-byte aligned, per call.
  * st_op_channel_sort: per row the stable ascending order of feat + 0.0f - sorted_out [C][n] the values, perm_out [C][n] the
- * element indices; either may be null.  Two calls on the same data give the same bits. */
+ * element indices; either may be null.  Two calls on the same data give the same bits.
+ * Alignment: `scratch` must be 256-byte aligned (64-bit keys lie behind its header) - st_op_channel_sort and
+ * st_op_w2_marginal_loss refuse it otherwise; every tensor pointer may be merely 4-byte aligned. */
 int st_op_sort_chunk(void);
 long long st_op_sort_scratch_bytes(int channels, long long n);
 int st_op_channel_sort(const float* feat, int channels, long long n, void* scratch, float* sorted_out, unsigned int* perm_out,
@@ -971,7 +983,9 @@ int st_op_w2_marginal_loss_backward(const float* unit_grad, long long count, con
  * S^T, the bias, the bound on max |S|.
  * `scratch`: st_op_nearest_scratch_floats(C, n, m) floats of the caller's, 256-byte aligned, per call.
  * st_op_nearest_search: idx_out [n] = k*(i), score_out [n] (optional) = <f_i, s_k*> - |s_k*|^2 / 2 as the search saw it.
- * Two calls on the same data give the same bits. */
+ * Two calls on the same data give the same bits.
+ * Alignment: `prepared` and `scratch` must be 256-byte aligned - st_op_nearest_prepare, st_op_nearest_search and
+ * st_op_nearest_loss refuse them otherwise; vectors, feat and every output may be merely 4-byte aligned. */
 int st_op_nearest_k_chunk(void);
 int st_op_nearest_pixel_tile(void);
 int st_op_nearest_k_tile(void);
@@ -996,7 +1010,10 @@ int st_op_nearest_loss_backward(const float* unit_grad, long long count, const f
  * `scratch`: st_op_sliced_scratch_bytes(C, P, n) bytes of the caller's, 256-byte aligned, per call, n the longest row of the call
  * (st_op_sliced_target: max(m, n_out)).
  * st_op_sliced_target: one style image's share, target [P][n_out] = (accumulate ? target : 0) + weight resample_n_out(sort_rows(r feat)),
- * feat [C][m].  Two calls on the same data give the same bits. */
+ * feat [C][m].  Two calls on the same data give the same bits.
+ * Alignment: `scratch` must be 256-byte aligned - st_op_sliced_target, st_op_sliced_project and st_op_sliced_loss refuse it
+ * otherwise; feat, r, rt, target and every output may be merely 4-byte aligned (a product whose operands are not 16-byte
+ * aligned runs on the exact fp32 MFMA instead of the fp16x3 kernel). */
 int st_op_sliced_directions(unsigned long long seed, int entry, unsigned long long epoch, int projections, int channels, float* r_out,
                             float* rt_out, void* stream);
 long long st_op_sliced_scratch_bytes(int channels, int projections, long long n);

@@ -365,7 +365,8 @@ int st_head_forward(st_head* h, const float* feat, const float* mean_t, const fl
                     const float* gram_t, float eps, float* loss_out, float* state, void* stream) {
     ST_REQUIRE(h && feat && loss_out, "st_head_forward: null argument");
     ST_REQUIRE(h->kind != 2, "st_head_forward: a moments-only head");
-    ST_REQUIRE(aligned16(feat) && aligned16(state), "st_head_forward: feat and state must be 16-byte aligned");
+    ST_REQUIRE(aligned16(feat), "st_head_forward: feat must be 16-byte aligned");
+    ST_REQUIRE(aligned16(state), "st_head_forward: state must be 16-byte aligned");
     hipStream_t s = static_cast<hipStream_t>(stream);
     StyleHead& w = h->w;
     const int n = w.n;
@@ -396,7 +397,9 @@ int st_head_forward(st_head* h, const float* feat, const float* mean_t, const fl
 int st_head_backward(st_head* h, const float* feat, const float* state, const float* upstream, float* grad_feat, void* stream) {
     ST_REQUIRE(h && feat && state && upstream && grad_feat, "st_head_backward: null argument");
     ST_REQUIRE(h->kind != 2, "st_head_backward: a moments-only head");
-    ST_REQUIRE(aligned16(feat) && aligned16(state) && aligned16(grad_feat), "st_head_backward: feat, state and grad_feat must be 16-byte aligned");
+    ST_REQUIRE(aligned16(feat), "st_head_backward: feat must be 16-byte aligned");
+    ST_REQUIRE(aligned16(state), "st_head_backward: state must be 16-byte aligned");
+    ST_REQUIRE(aligned16(grad_feat), "st_head_backward: grad_feat must be 16-byte aligned");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const StyleHead& w = h->w;
     const int n = w.n;

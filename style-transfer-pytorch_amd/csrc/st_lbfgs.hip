@@ -513,6 +513,7 @@ long long st_lbfgs_state_bytes(long long count) {
 
 int st_lbfgs_reset(void* state, long long count, void* stream) {
     ST_REQUIRE(state && count >= 1, "st_lbfgs_reset: bad argument");
+    ST_REQUIRE((reinterpret_cast<uintptr_t>(state) & 15) == 0, "st_lbfgs_reset: the state buffer must be 16-byte aligned");
     ST_HIP(hipMemsetAsync(state, 0, kCtlBytes, static_cast<hipStream_t>(stream)));
     return 0;
 }

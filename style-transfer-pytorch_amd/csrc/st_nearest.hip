@@ -481,6 +481,7 @@ long long st_op_nearest_scratch_floats(int channels, long long n, long long m) {
 
 int st_op_nearest_prepare(const float* vectors, int channels, long long m, float* prepared, void* stream) {
     ST_REQUIRE(vectors && prepared, "st_op_nearest_prepare: null argument");
+    ST_REQUIRE((reinterpret_cast<uintptr_t>(prepared) & 255) == 0, "st_op_nearest_prepare: prepared must be 256-byte aligned");
     if (nearest_check_shape("st_op_nearest_prepare", channels, 1, m)) return 1;
     return launch_nearest_prepare(vectors, channels, m, nearest_prepared_of(prepared, channels, m), static_cast<hipStream_t>(stream));
 }
@@ -488,6 +489,8 @@ int st_op_nearest_prepare(const float* vectors, int channels, long long m, float
 int st_op_nearest_search(const float* feat, int channels, long long n, const float* prepared, long long m, float* scratch, int* idx_out,
                          float* score_out, void* stream) {
     ST_REQUIRE(feat && prepared && scratch && idx_out, "st_op_nearest_search: null argument");
+    ST_REQUIRE((reinterpret_cast<uintptr_t>(prepared) & 255) == 0, "st_op_nearest_search: prepared must be 256-byte aligned");
+    ST_REQUIRE((reinterpret_cast<uintptr_t>(scratch) & 255) == 0, "st_op_nearest_search: scratch must be 256-byte aligned");
     if (nearest_check_shape("st_op_nearest_search", channels, n, m)) return 1;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const NearestPrepared pr = nearest_prepared_of(const_cast<float*>(prepared), channels, m);
@@ -502,6 +505,8 @@ int st_op_nearest_search(const float* feat, int channels, long long n, const flo
 int st_op_nearest_loss(const float* feat, int channels, long long n, const float* prepared, long long m, float* scratch, int* idx_out,
                        float* unit_grad_out, float* loss_out, void* stream) {
     ST_REQUIRE(feat && prepared && scratch && idx_out && unit_grad_out && loss_out, "st_op_nearest_loss: null argument");
+    ST_REQUIRE((reinterpret_cast<uintptr_t>(prepared) & 255) == 0, "st_op_nearest_loss: prepared must be 256-byte aligned");
+    ST_REQUIRE((reinterpret_cast<uintptr_t>(scratch) & 255) == 0, "st_op_nearest_loss: scratch must be 256-byte aligned");
     if (nearest_check_shape("st_op_nearest_loss", channels, n, m)) return 1;
     hipStream_t s = static_cast<hipStream_t>(stream);
     ST_HIP(hipMemsetAsync(scratch, 0, 16, s));

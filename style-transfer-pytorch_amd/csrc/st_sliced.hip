@@ -198,6 +198,7 @@ static int measure_op_bounds(const float* feat, long long feat_count, const floa
 int st_op_sliced_target(const float* feat, int channels, long long m, const float* r, const float* rt, int projections, long long n_out,
                         void* scratch, float* target, int accumulate, float weight, void* stream) {
     ST_REQUIRE(feat && r && rt && scratch && target, "st_op_sliced_target: null argument");
+    ST_REQUIRE((reinterpret_cast<uintptr_t>(scratch) & 255) == 0, "st_op_sliced_target: scratch must be 256-byte aligned");
     if (sliced_check_shape("st_op_sliced_target", channels, projections, m) ||
         sliced_check_shape("st_op_sliced_target", channels, projections, n_out))
         return 1;
@@ -210,6 +211,7 @@ int st_op_sliced_target(const float* feat, int channels, long long m, const floa
 int st_op_sliced_project(const float* feat, int channels, long long n, const float* r, const float* rt, int projections, void* scratch,
                          float* y_out, void* stream) {
     ST_REQUIRE(feat && r && rt && scratch && y_out, "st_op_sliced_project: null argument");
+    ST_REQUIRE((reinterpret_cast<uintptr_t>(scratch) & 255) == 0, "st_op_sliced_project: scratch must be 256-byte aligned");
     if (sliced_check_shape("st_op_sliced_project", channels, projections, n)) return 1;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const SlicedScratch sc = sliced_scratch_of(scratch, projections, n);
@@ -220,6 +222,7 @@ int st_op_sliced_project(const float* feat, int channels, long long n, const flo
 int st_op_sliced_loss(const float* feat, int channels, long long n, const float* r, const float* rt, int projections, const float* target,
                       void* scratch, float* unit_grad_out, float* loss_out, void* stream) {
     ST_REQUIRE(feat && r && rt && target && scratch && unit_grad_out && loss_out, "st_op_sliced_loss: null argument");
+    ST_REQUIRE((reinterpret_cast<uintptr_t>(scratch) & 255) == 0, "st_op_sliced_loss: scratch must be 256-byte aligned");
     if (sliced_check_shape("st_op_sliced_loss", channels, projections, n)) return 1;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const SlicedScratch sc = sliced_scratch_of(scratch, projections, n);

@@ -297,6 +297,7 @@ long long st_op_sort_scratch_bytes(int channels, long long n) {
 int st_op_channel_sort(const float* feat, int channels, long long n, void* scratch, float* sorted_out, unsigned int* perm_out,
                        void* stream) {
     ST_REQUIRE(feat && scratch, "st_op_channel_sort: null argument");
+    ST_REQUIRE((reinterpret_cast<uintptr_t>(scratch) & 255) == 0, "st_op_channel_sort: scratch must be 256-byte aligned");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const MarginalScratch m = marginal_scratch_of(scratch, channels, n);
     if (launch_channel_sort(feat, channels, n, m, s)) return 1;
@@ -312,6 +313,7 @@ int st_op_resample_quantiles(const float* q, int channels, long long n_in, long 
 int st_op_w2_marginal_loss(const float* feat, int channels, long long n, const float* target, void* scratch, float* unit_grad_out,
                            float* loss_out, void* stream) {
     ST_REQUIRE(feat && target && scratch && unit_grad_out && loss_out, "st_op_w2_marginal_loss: null argument");
+    ST_REQUIRE((reinterpret_cast<uintptr_t>(scratch) & 255) == 0, "st_op_w2_marginal_loss: scratch must be 256-byte aligned");
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (check_sort_shape("st_op_w2_marginal_loss", channels, n)) return 1;
     ST_HIP(hipMemsetAsync(scratch, 0, 16, s));

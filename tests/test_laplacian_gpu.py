@@ -144,9 +144,10 @@ def _oracle(image, content, pooling, decisions, content_layers, style_layers, ct
             grad.detach(), grad_plain.detach())
 
 
-def _judge(tag, plan, img, image, size, pooling, content_layers, style_layers, kinds, pools):
+def _judge(tag, plan, img, image, size, pooling, content_layers, style_layers, kinds, pools, closure=None):
     """One closure of `plan` - which has NO Laplacian yet - without and one with the Laplacian, the latter against the oracle
-    under the plan's own maps.  Returns the failures."""
+    under the plan's own maps.  Returns the failures.  `closure`: the judged closure as a callable returning (losses, gradient)
+    (tests/test_caller_buffers_gpu.py runs it on buffers of its own); default plan.loss_and_grad(img)."""
     from style_transfer import _hip as hip
     deepest = max(content_layers + style_layers)
     plan.forward(img, deepest)
@@ -165,7 +166,7 @@ def _judge(tag, plan, img, image, size, pooling, content_layers, style_layers, k
     tv_alone = plan.term_losses()[-1].clone()
     content = _content(size)
     plan.set_laplacian(content.to(DEV), pools, LAP_WEIGHT)
-    losses, grad = plan.loss_and_grad(img)
+    losses, grad = closure() if closure is not None else plan.loss_and_grad(img)
     torch.cuda.synchronize()
     terms = plan.term_losses().cpu().double().numpy()
     lterms = plan.laplacian_terms().cpu().numpy()
