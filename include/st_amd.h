@@ -45,6 +45,19 @@ const char* st_last_error(void);
 int st_abi_version(void);
 /* Name of the gfx target the kernels were compiled for ("gfx950"). */
 const char* st_compiled_arch(void);
+/* Size limit.  ONE number bounds every map the library is handed: an image, a strip, a tap or a feature map holds at most
+ * st_max_pixels() = 2^24 - 1 = 16 777 215 pixels (height * width, or npix), whatever its channel count - 4095 x 4097 is the
+ * largest near-square image.  It is the size up to which every 32-bit byte offset, buffer-resource size and out-of-range
+ * offset constant of the kernels is proven (profiles/size_limits.md: one row per entry point) and tested
+ * (tests/test_size_limits_gpu.py).  Every entry point that takes a height and a width, or a pixel count - st_plan_create,
+ * st_plan_create_strip (the strip's rows x width), st_head_create, st_op_conv3x3 and its _dgrad / _strip / _strip_ex forms,
+ * st_op_conv1x1, st_op_pool2x2 and its backward, st_op_tv_loss / st_op_tv_value / st_op_tv_loss_backward,
+ * st_op_channel_moments, st_op_w2_diag_loss and its backward, st_op_laplacian_* - refuses a larger map with a message
+ * that names the limit, before it allocates or launches anything.  The calls on a plan (st_plan_forward, _backward,
+ * _loss_and_grad, _step, the mask and region setters) take their size from the plan and inherit its check.  Entries that
+ * take an element COUNT (st_op_mse_loss, st_op_scaled_mse_loss and their backwards) index with 64-bit integers and have no
+ * limit of their own.  Larger images: cut them into row strips (st_plan_create_strip), each strip within the limit. */
+long long st_max_pixels(void);
 /* Build flavour: 1 when the library was built with `build.py --experiments` - it then also holds the code that no default path
  * executes (persistent Newton-Schulz chain kernel, Winograd convolution = conv precision code 5, reproducer and measurement-only
  * kernels) and reads EVERY ST_* switch from the environment; 0 for the default build (the hot path and nothing else). */

@@ -102,6 +102,7 @@ extern "C" {
 const char* st_last_error(void) { return st::get_error(); }
 int st_abi_version(void) { return ST_AMD_ABI_VERSION; }
 const char* st_compiled_arch(void) { return "gfx950"; }
+long long st_max_pixels(void) { return st::kMaxPixels; }
 int st_has_experiments(void) { return st::kExperiments ? 1 : 0; }
 int st_env_switches(const char** names, int capacity) {
     const int n = (int)(sizeof(st::kEnvSwitches) / sizeof(st::kEnvSwitches[0]));
@@ -317,7 +318,7 @@ int st_plan_create(st_plan** out, const st_net* net, int height, int width) {
     ST_REQUIRE(out && net, "st_plan_create: null argument");
     // VGGFeatures.forward size check for taps up to features[29] (style_transfer.py:61-69,81-83)
     ST_REQUIRE(height >= 16 && width >= 16, "Input is %dx%d but must be at least 16x16", height, width);
-    ST_REQUIRE((long long)height * width <= (1ll << 25), "image too large (H*W must be <= 2^25)");
+    ST_REQUIRE_PIXELS("st_plan_create", (long long)height * width);
     return plan_create_common(out, net, height, width, height, 0, false);
 }
 
@@ -330,7 +331,7 @@ int st_plan_create_strip(st_plan** out, const st_net* net, int global_height, in
     ST_REQUIRE(row_begin % 16 == 0 && (row_end % 16 == 0 || row_end == global_height),
                "strip boundaries must be multiples of 16 rows (all four 2x2 poolings stay strip-local)");
     ST_REQUIRE(row_end - row_begin >= 16, "a strip needs at least 16 rows");
-    ST_REQUIRE((long long)(row_end - row_begin) * width <= (1ll << 25), "strip too large");
+    ST_REQUIRE_PIXELS("st_plan_create_strip (the strip)", (long long)(row_end - row_begin) * width);
     return plan_create_common(out, net, row_end - row_begin, width, global_height, row_begin, true);
 }
 

@@ -50,6 +50,20 @@ const char* get_error();
         }                              \
     } while (0)
 
+// ---- the size limit ---------------------------------------------------------------------------------
+// One image, strip, tap or feature map handed to any entry point has at most kMaxPixels = 2^24 - 1 pixels (H * W, or npix).
+// The number comes from the fp16x3 3x3 kernels: they stage 16 input channels through one raw buffer resource of
+// 16 * HW * 4 bytes and give a zero-padded tap the byte offset 2^30 (kOOR), which the hardware answers with 0 only while it
+// lies beyond the resource, i.e. while 64 * HW <= 2^30; and every 3x3 and 1x1 convolution kernel writes through 32-channel
+// output resources of 128 * HW bytes and parks the stores of out-of-tile lanes at the byte offset 0x7FFFFFFF, which is out of
+// range only while 128 * HW <= 2^31 - 1, i.e. HW <= 2^24 - 1.  Every other 32-bit quantity in the library (`int` element
+// counts of up to 64 * HW, 3 * HW) has room to spare at that size; profiles/size_limits.md lists them entry by entry.  st_max_pixels() reports the number; every entry refuses a larger map before it allocates.
+constexpr long long kMaxPixels = (1ll << 24) - 1;
+inline bool pixels_in_range(long long pixels) { return pixels >= 1 && pixels <= kMaxPixels; }
+#define ST_REQUIRE_PIXELS(who, pixels)                                                                                  \
+    ST_REQUIRE(st::pixels_in_range(pixels), "%s: %lld pixels: a map may hold 1 to %lld (2^24 - 1) pixels", who,        \
+               (long long)(pixels), st::kMaxPixels)
+
 // ---- build flavours -----------------------------------------------------------------------------
 // The default libst_amd.so holds the hot path and nothing else.  `build.py --experiments` (-DST_EXPERIMENTS) adds the code
 // that no default path executes - the persistent Newton-Schulz chain kernel (st_nschain.hip), the Winograd convolution

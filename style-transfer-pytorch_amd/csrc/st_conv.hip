@@ -492,7 +492,12 @@ int launch_conv(const ConvProblem& p_in, hipStream_t stream) {
     const int KC = (p.taps == 9) ? kChunk3x3 : kChunk1x1;
     ST_REQUIRE(p.cin % KC == 0 && p.cout % 64 == 0, "conv: Cin %% %d and Cout %% 64 required (got %d, %d)", KC,
                p.cin, p.cout);
-    ST_REQUIRE((long long)p.height * p.width * KC * 4 < (1ll << 31), "conv: image too large for 32-bit tile maps");
+    // staging: byte offsets inside a KC-channel chunk are `int`, and kOutOfRange must lie beyond the chunk's resource; epilogue:
+    // a 32-channel output resource of 32 HW 4 bytes must end below the out-of-range store offset 0x7FFFFFFF (at 4100 x 4096 that
+    // offset lay inside it and out-of-tile lanes overwrote an element of channel 31: profiles/size_limits.md).  kMaxPixels gives both.
+    ST_REQUIRE((long long)p.height * p.width * KC * 4 < (1ll << 31) && (long long)p.height * p.width * 32 * 4 <= 0x7FFFFFFFll &&
+                   (long long)p.height * p.width * (p.taps == 9 ? KC : 0) * 4 <= (long long)kOutOfRange,
+               "conv: %d x %d: image too large for the kernel's 32-bit offsets (at most %lld pixels)", p.height, p.width, kMaxPixels);
     const long long pixels = (long long)p.height * p.width;
     // Workgroup tile candidates (co x pixels): A = 64x256, B = 64x128, C = 128x64 (tiny images).
     // Target >= 512 workgroups (two per CU, i.e. two waves per SIMD to cover each other's barriers):

@@ -822,7 +822,9 @@ int launch_pc_tw(const ConvProblem& p, int ksplit, hipStream_t s, int tw) {
 bool conv_pc_applies(const ConvProblem& p) {
     static Option halo_ok("ST_CONV_PC_HALO", 1);     // A/B knob
     return p.taps == 9 && p.planes == 2 && p.elem == 1 && p.wgt_split && p.amax_word && !p.mask &&
-           (!p.in_halo || halo_ok.get()) && p.cin % SK == 0 && p.cout % 64 == 0;
+           (!p.in_halo || halo_ok.get()) && p.cin % SK == 0 && p.cout % 64 == 0 &&
+           // kOOR must lie beyond a chunk's resource (SK HW 4 bytes) or a zero-padded tap reads an activation: st_common.h, kMaxPixels
+           (long long)SK * p.height * p.width * 4 < (long long)kOOR;
 }
 
 namespace {

@@ -313,8 +313,8 @@ int st_head_create(st_head** out, int kind, int channels, int height, int width,
     ST_REQUIRE(kind >= 0 && kind <= 2, "st_head_create: unknown kind %d (0: w2 - StyleLossW2, 1: gram - StyleLoss, 2: moments only)", kind);
     ST_REQUIRE(channels == 64 || channels == 128 || channels == 256 || channels == 512,
                "st_head_create: %d channels: must be 64, 128, 256 or 512", channels);
-    ST_REQUIRE(height >= 1 && width >= 1 && (long long)height * width < (1ll << 24),
-               "st_head_create: a %d x %d tap: height and width >= 1, fewer than 2^24 pixels", height, width);
+    ST_REQUIRE(height >= 1 && width >= 1, "st_head_create: a %d x %d tap: height and width >= 1", height, width);
+    ST_REQUIRE_PIXELS("st_head_create", (long long)height * width);
     ST_REQUIRE(precision == 0 || precision == 4, "st_head_create: precision must be 0 (fp32) or 4 (fp16x3)");
     st_head* h = new st_head;
     h->kind = kind; h->height = height; h->width = width; h->precision = precision;
@@ -439,7 +439,8 @@ int st_op_scaled_mse_loss_backward(const float* x, const float* target, long lon
 
 int st_op_tv_value(const float* image, int height, int width, float* scratch, float* loss_out, void* stream) {
     ST_REQUIRE(image && scratch && loss_out, "st_op_tv_value: null argument");
-    ST_REQUIRE(height >= 1 && width >= 1 && 3ll * height * width < (1ll << 31), "st_op_tv_value: bad shape %d x %d", height, width);
+    ST_REQUIRE(height >= 1 && width >= 1, "st_op_tv_value: bad shape %d x %d", height, width);
+    ST_REQUIRE_PIXELS("st_op_tv_value", (long long)height * width);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int blocks = stream_grid(3ll * height * width);
     hipLaunchKernelGGL(tv_value_kernel, dim3(blocks), dim3(256), 0, s, image, height, width, scratch);
@@ -452,7 +453,8 @@ int st_op_tv_value(const float* image, int height, int width, float* scratch, fl
 
 int st_op_tv_loss_backward(const float* image, int height, int width, const float* upstream, float* grad, void* stream) {
     ST_REQUIRE(image && upstream && grad, "st_op_tv_loss_backward: null argument");
-    ST_REQUIRE(height >= 1 && width >= 1 && 3ll * height * width < (1ll << 31), "st_op_tv_loss_backward: bad shape %d x %d", height, width);
+    ST_REQUIRE(height >= 1 && width >= 1, "st_op_tv_loss_backward: bad shape %d x %d", height, width);
+    ST_REQUIRE_PIXELS("st_op_tv_loss_backward", (long long)height * width);
     const double n = 3.0 * height * width, n2 = 3.0 * (height + 1) * (width + 1);
     // d loss / d D = 2 * (1/3 or 1/12) * (1/n) * 2 D
     const float c1 = (float)(4.0 / (3.0 * n)), c3 = (float)(4.0 / (12.0 * n2));

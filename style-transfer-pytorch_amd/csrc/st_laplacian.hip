@@ -329,8 +329,10 @@ int st_plan_laplacian_terms(st_plan* p, float** terms, int* count) {
 
 namespace {
 int lap_op_shape(const char* who, int channels, int height, int width, int pool) {
-    ST_REQUIRE(channels >= 1 && height >= 1 && width >= 1 && (long long)channels * height * width < (1ll << 31),
-               "%s: bad shape %d x %d x %d", who, channels, height, width);
+    ST_REQUIRE(channels >= 1 && height >= 1 && width >= 1, "%s: bad shape %d x %d x %d", who, channels, height, width);
+    ST_REQUIRE_PIXELS(who, (long long)height * width);
+    // (the kernels count C * H * W elements in an `int`)
+    ST_REQUIRE((long long)channels * height * width < (1ll << 31), "%s: %d x %d x %d: fewer than 2^31 elements", who, channels, height, width);
     ST_REQUIRE(pool >= 1 && height / pool >= 2 && width / pool >= 2,
                "%s: pool size %d on a %d x %d image: it must be >= 1 and leave a pooled map of at least 2 x 2", who, pool, height, width);
     return 0;

@@ -140,6 +140,8 @@ int st_op_sqrtm_time(int n, int iters, double* fwd_us, double* bwd_us, void* str
 
 int st_op_tv_loss(const float* image, int height, int width, float* loss_out, float* grad_out, void* stream) {
     ST_REQUIRE(image && loss_out && grad_out, "st_op_tv_loss: null argument");
+    ST_REQUIRE(height >= 1 && width >= 1, "st_op_tv_loss: bad shape %d x %d", height, width);
+    ST_REQUIRE_PIXELS("st_op_tv_loss", (long long)height * width);
     hipStream_t s = static_cast<hipStream_t>(stream);
     OpScratch tmp(s);
     float* partials = nullptr;
@@ -157,6 +159,8 @@ static int conv_op(const float* in, const float* mask, const float* weight, cons
     const bool wino5 = precision == 5;
     if (wino5) precision = 4;
     ST_REQUIRE(conv_precision_valid(precision), "conv precision must be 0, 2, 3 or 4");
+    ST_REQUIRE(height >= 1 && width >= 1, "st_op_conv3x3: bad shape %d x %d", height, width);
+    ST_REQUIRE_PIXELS("st_op_conv3x3", (long long)height * width);        // (all four st_op_conv3x3* entries)
     OpScratch tmp(s);
     float* wl = nullptr;
     float* scratch = nullptr;
@@ -212,7 +216,8 @@ int st_op_conv1x1(const float* in, const float* weight, const float* bias, float
                   long long npix, int precision, void* stream) {
     ST_REQUIRE(in && weight && out, "st_op_conv1x1: null argument");
     ST_REQUIRE(precision == 0 || precision == 4, "st_op_conv1x1: precision must be 0 (fp32) or 4 (fp16x3)");
-    ST_REQUIRE(cin % 32 == 0 && cout % 64 == 0 && npix > 0 && npix < (1ll << 31), "st_op_conv1x1: bad shape");
+    ST_REQUIRE(cin > 0 && cout > 0 && cin % 32 == 0 && cout % 64 == 0, "st_op_conv1x1: bad shape");
+    ST_REQUIRE_PIXELS("st_op_conv1x1", npix);
     hipStream_t s = static_cast<hipStream_t>(stream);
     OpScratch tmp(s);
     unsigned int* amax = nullptr;
@@ -234,6 +239,7 @@ int st_op_pool2x2(const float* in, float* out, int channels, int height, int wid
     ST_REQUIRE(in && out, "st_op_pool2x2: null argument");
     ST_REQUIRE(mode >= 0 && mode <= 2, "st_op_pool2x2: mode must be 0 (max), 1 (average) or 2 (l2)");
     ST_REQUIRE(channels > 0 && height >= 2 && width >= 2, "st_op_pool2x2: C >= 1 and H, W >= 2 required");
+    ST_REQUIRE_PIXELS("st_op_pool2x2", (long long)height * width);
     return launch_pool_fwd(in, out, channels, height, width, mode, static_cast<hipStream_t>(stream));
 }
 
@@ -242,6 +248,7 @@ int st_op_pool2x2_backward(const float* in, const float* grad_out, float* grad_i
     ST_REQUIRE(in && grad_out && grad_in, "st_op_pool2x2_backward: null argument");
     ST_REQUIRE(mode >= 0 && mode <= 2, "st_op_pool2x2_backward: mode must be 0 (max), 1 (average) or 2 (l2)");
     ST_REQUIRE(channels > 0 && height >= 2 && width >= 2, "st_op_pool2x2_backward: C >= 1 and H, W >= 2 required");
+    ST_REQUIRE_PIXELS("st_op_pool2x2_backward", (long long)height * width);
     return launch_pool_bwd(in, grad_out, grad_in, channels, height, width, mode, static_cast<hipStream_t>(stream));
 }
 

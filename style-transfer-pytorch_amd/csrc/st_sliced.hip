@@ -93,7 +93,7 @@ bool force_fp32() {
 int sliced_check_shape(const char* who, int channels, int proj, long long n) {
     ST_REQUIRE(channels >= 32 && channels % 32 == 0, "%s: %d channels: a positive multiple of 32", who, channels);
     ST_REQUIRE(proj >= 64 && proj <= 512 && proj % 64 == 0, "%s: %d projections: a multiple of 64 in [64, 512]", who, proj);
-    ST_REQUIRE(n >= 1 && n < (1ll << 24), "%s: rows of %lld elements: 1 to 2^24 - 1", who, n);
+    ST_REQUIRE(pixels_in_range(n), "%s: rows of %lld elements: 1 to 2^24 - 1", who, n);      // (kMaxPixels, st_common.h)
     return 0;
 }
 

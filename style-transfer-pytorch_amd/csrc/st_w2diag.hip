@@ -173,6 +173,7 @@ bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 
 int check_shape(const char* who, int channels, long long npix) {
     ST_REQUIRE(channels >= 1 && channels <= 65535 && npix >= 1 && (long long)channels * kStatsMaxSplits < (1ll << 30),
                "%s: %d channels of %lld pixels: 1 to 65535 channels of at least one pixel", who, channels, npix);
+    ST_REQUIRE_PIXELS(who, npix);
     return 0;
 }
 
@@ -238,6 +239,7 @@ long long st_op_channel_stats_scratch_floats(int channels, long long npix) {
 int st_op_channel_moments(const float* feat, int channels, long long npix, float* scratch, float* mean_out, float* srm_diag_out,
                           void* stream) {
     ST_REQUIRE(feat && scratch && mean_out && srm_diag_out, "st_op_channel_moments: null argument");
+    if (check_shape("st_op_channel_moments", channels, npix)) return 1;
     hipStream_t s = static_cast<hipStream_t>(stream);
     ChannelStatsFinish fin;
     fin.norm = (double)npix;

@@ -46,6 +46,7 @@ def _declare(lib):
         'st_last_error': (ctypes.c_char_p, []),
         'st_abi_version': (i32, []),
         'st_compiled_arch': (ctypes.c_char_p, []),
+        'st_max_pixels': (ctypes.c_longlong, []),
         'st_has_experiments': (i32, []),
         'st_env_switches': (i32, [ctypes.POINTER(ctypes.c_char_p), i32]),
         'st_set_option': (i32, [ctypes.c_char_p, i32, i32]),
@@ -225,6 +226,12 @@ def load_library(require_gpu=True):
     if require_gpu and not torch.cuda.is_available():
         raise HipLibraryError('no HIP device visible: the MI355X hot path cannot run (no CPU fallback)')
     return _lib
+
+
+def max_pixels():
+    """The most pixels (H * W, or npix) one image, strip, tap or feature map may hold at any entry point of the library
+    (st_max_pixels: 2^24 - 1; include/st_amd.h, "Size limit")."""
+    return int(load_library(require_gpu=False).st_max_pixels())
 
 
 def has_experiments():

@@ -94,6 +94,16 @@ def _buffer_ok(b, like, numel):
             and b.is_contiguous() and b.data_ptr() % 16 == 0 and not b.requires_grad)
 
 
+def _max_pixels():
+    """The library's one size limit (include/st_amd.h, "Size limit"; st_max_pixels): the pixels a map may hold."""
+    from . import _hip
+    return _hip.max_pixels()
+
+
+def _pixels_ok(input):
+    return input.shape[-2] * input.shape[-1] <= _max_pixels()
+
+
 def eligible(input, kind, buffers=()):
     """Can ``input`` take the native path of ``kind`` ('w2', 'gram', 'mse', 'scaled_mse', 'tv', 'laplacian', 'moments')?  ``buffers``: the
     module's tensors that the library would read in place - (mean, cov, cov_sqrt), (gram target,) or (target,).  Says nothing
@@ -101,13 +111,13 @@ def eligible(input, kind, buffers=()):
     if kind in ('w2', 'gram', 'moments'):
         if not (_one_dense_fp32(input, 3) and input.ndim in (3, 4) and input.shape[-3] in HEAD_CHANNELS):
             return False
-        if input.shape[-2] * input.shape[-1] >= 1 << 24:
+        if not _pixels_ok(input):
             return False
         c = input.shape[-3]
         sizes = {'w2': (c, c * c, c * c), 'gram': (c * c,), 'moments': ()}[kind]
     elif kind == 'w2_diag':
         # (any channel count the launch's grid takes; buffers: none, or the module's (mean, std))
-        if not (_one_dense_fp32(input, 3) and input.ndim in (3, 4) and input.shape[-3] <= 65535):
+        if not (_one_dense_fp32(input, 3) and input.ndim in (3, 4) and input.shape[-3] <= 65535 and _pixels_ok(input)):
             return False
         sizes = (input.shape[-3],) * len(buffers)
     elif kind == 'w2_marginal':
@@ -124,16 +134,16 @@ def eligible(input, kind, buffers=()):
     elif kind == 'sliced':
         # (a channel count that is a multiple of 64; buffers: none)
         if not (_one_dense_fp32(input, 3) and input.ndim in (3, 4) and input.shape[-3] % 64 == 0 and
-                input.shape[-2] * input.shape[-1] < 1 << 24):
+                _pixels_ok(input)):
             return False
         sizes = ()
     elif kind == 'tv':
-        if not (_one_dense_fp32(input, 3) and input.ndim in (3, 4) and input.shape[-3] == 3 and input.numel() < 1 << 31):
+        if not (_one_dense_fp32(input, 3) and input.ndim in (3, 4) and input.shape[-3] == 3 and _pixels_ok(input)):
             return False
         sizes = ()
     elif kind == 'laplacian':
         # (buffers: one target per pool size, each of its own size - checked by the module, which knows the pools)
-        return _one_dense_fp32(input, 3) and input.ndim in (3, 4) and input.numel() < 1 << 31 and \
+        return _one_dense_fp32(input, 3) and input.ndim in (3, 4) and _pixels_ok(input) and input.numel() < 1 << 31 and \
             all(_buffer_ok(b, input, b.numel()) for b in buffers)
     else:
         if not (torch.is_tensor(input) and _one_dense_fp32(input, min(input.ndim, 3))):
@@ -817,7 +827,7 @@ class StyleLossSliced(nn.Module):
         p = self.projections if self.directions is None else int(self.directions.shape[0])
         return (native.enabled and eligible(input, 'sliced') and self.target.shape[0] == input.shape[-3] and
                 not self.target.requires_grad and self.target.device == input.device and self.target.dtype == torch.float32 and
-                self.target.shape[1] < 1 << 24 and 64 <= p <= 512 and p % 64 == 0 and
+                self.target.shape[1] <= _max_pixels() and 64 <= p <= 512 and p % 64 == 0 and
                 (self.directions is None or (self.directions.device == input.device and self.directions.dtype == torch.float32 and
                                              not self.directions.requires_grad)))
 
