@@ -922,6 +922,12 @@ long long st_head_state_floats(const st_head* head);
 /* StyleLossW2.get_target (style_transfer.py:162-168): mean_out [C] (may be NULL) and srm_out [C*C] = F F^T / (h w), exactly
  * symmetric; srm_out alone is StyleLoss.get_target (:135-138).  Either kind of head. */
 int st_head_moments(st_head* head, const float* feat, float* mean_out, float* srm_out, void* stream);
+/* How st_head_create + st_head_moments split the pixel range of a [channels][npix] tap in `precision` (0 or 4), by the shape and
+ * the process's switches alone - no device call: *splits partial Grams (the launch's grid, what the head's workspace is sized
+ * for), split s over the pixels [s * *per_split, min((s + 1) * *per_split, npix)) - *per_split is a multiple of 4, so the last
+ * splits may be short or empty - and *wide = 1 where the pass runs its 128 x 128-tile kernel (fp16x3 only).  Any output may be
+ * NULL.  Refuses the shapes st_head_create refuses. */
+int st_op_gram_split_plan(int channels, long long npix, int precision, int* splits, long long* per_split, int* wide);
 /* The module's forward, UNWEIGHTED, into loss_out[0] (device).  Targets are read in place - the module's own buffers:
  * kind 0: mean_t [C], cov_t [C*C] (eps I included, :156), root_t [C*C] = sqrtm(cov_t); kind 1: gram_t [C*C]; the other
  * kind's pointers are ignored.  eps: StyleLossW2's covariance eps (:152) or ScaledMSELoss's (:97).  state != NULL: also

@@ -437,6 +437,11 @@ struct GramWorkspace {
     int max_splits;
 };
 int gram_choose_splits(int channels, long long npix, int max_splits);
+// the pixels of one split, split s owns [s per_split, min((s + 1) per_split, npix)): the even share rounded up to a multiple of
+// 4, so the last splits of the grid may be short or empty
+long long gram_per_split(long long npix, int splits);
+// does the fp16x3 pass (a bound is there) run its 128 x 128-tile kernel on this shape?  (ST_GRAM_WIDE)
+bool gram_wide_tiles(int channels, long long npix);
 // partial[s] = F[:, ks:ke] F[:, ks:ke]^T, partial_sum[s] = row sums; F is [C][npix]
 // bound != nullptr: fp16x3 arithmetic, scaled by the device bound on max |feat| (see ConvProblem::amax_word)
 // sqrt_mask (optional, [npix]): s = sqrt(m) of a spatial mask m - the staged values become F diag(s), the partials

@@ -152,9 +152,13 @@ __global__ __launch_bounds__(256) void gram_partial_kernel(const float* __restri
         }
     };
 
-    f32x16 acc;
+    // Two levels of summation: `acc` is the matrix pipe's chain over ONE stage (64 true FMAs), `total` adds the stages.  A
+    // split is up to ~1000 pixels long where the workspace caps the split count, and one fp32 chain of that length is biased
+    // on a channel that repeats a value exactly (a flat region: the same product added at every step rounds the same way
+    // for a whole binade of the sum) - the error then grows with the chain's length and has the same sign in every split.
+    f32x16 acc, total;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    for (int r = 0; r < 16; ++r) acc[r] = total[r] = 0.f;
 
     const long long span = k_end - k_begin;
     const int nstages = (int)((span + GK - 1) / GK);
@@ -177,10 +181,15 @@ __global__ __launch_bounds__(256) void gram_partial_kernel(const float* __restri
             for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[e], b[e], acc, 0, 0, 0);
         }
         if (more) store_tile(buf ^ 1);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            total[r] += acc[r];
+            acc[r] = 0.f;
+        }
         __syncthreads();
     }
 
-    store_tile_pair(partial + (size_t)split * C * C, C, ti, tj, wi, wj, l31, half, acc);
+    store_tile_pair(partial + (size_t)split * C * C, C, ti, tj, wi, wj, l31, half, total);
     // row sums: the 16 threads sharing a staging row are 16 consecutive lanes of one wave
     if (diag) {
 #pragma unroll
@@ -564,7 +573,6 @@ __global__ __launch_bounds__(256) void gram_finalize_kernel(const float* __restr
 
 }  // namespace
 
-namespace {
 // Measured (tools/gram_bench.py, isolated): 2048^2 relu3_1 (C = 256, 262 144 px) 212 -> 153 us, relu4_1 (C = 512,
 // 65 536 px) 194 -> 129 us; but relu5_1 there (16 384 px) 58 -> 63 us, every tap of a 512^2 image 25 % slower (too
 // few workgroups), C = 256 with 65 536 px (1024^2) neutral, and C = 128 unchanged or slower (one tile pair, a quarter of
@@ -575,7 +583,6 @@ bool gram_wide_tiles(int channels, long long npix) {
     if (mode == 0 || channels % 128 != 0) return false;
     return mode == 2 || (channels >= 256 && npix >= 65536);
 }
-}  // namespace
 
 int gram_choose_splits(int channels, long long npix, int max_splits) {
     const int side = gram_wide_tiles(channels, npix) ? 128 : GT;
@@ -588,12 +595,16 @@ int gram_choose_splits(int channels, long long npix, int max_splits) {
     return (int)want;
 }
 
+long long gram_per_split(long long npix, int splits) {
+    const long long per_split = (npix + splits - 1) / splits;
+    return (per_split + 3) & ~3ll;                               // keep 16-byte alignment of the splits
+}
+
 int launch_gram_partial(const float* feat, int channels, long long npix, int splits, GramWorkspace ws,
                         hipStream_t s, const unsigned int* bound, const float* sqrt_mask) {
     ST_REQUIRE(channels % GT == 0, "gram: channel count must be a multiple of 64");
     ST_REQUIRE(splits >= 1 && splits <= ws.max_splits, "gram: bad split count %d", splits);
-    long long per_split = (npix + splits - 1) / splits;
-    per_split = (per_split + 3) & ~3ll;                          // keep 16-byte alignment of the splits
+    const long long per_split = gram_per_split(npix, splits);
     static Option remap_opt("ST_XCD_REMAP", 1);            // 0: plain workgroup order (A/B runs)
     const int remap = remap_opt.get();
     if (bound && gram_wide_tiles(channels, npix)) {

@@ -344,6 +344,19 @@ int st_head_create(st_head** out, int kind, int channels, int height, int width,
     return 0;
 }
 
+int st_op_gram_split_plan(int channels, long long npix, int precision, int* splits, long long* per_split, int* wide) {
+    ST_REQUIRE(channels == 64 || channels == 128 || channels == 256 || channels == 512,
+               "st_op_gram_split_plan: %d channels: must be 64, 128, 256 or 512", channels);
+    ST_REQUIRE_PIXELS("st_op_gram_split_plan", npix);
+    ST_REQUIRE(precision == 0 || precision == 4, "st_op_gram_split_plan: precision must be 0 (fp32) or 4 (fp16x3)");
+    // st_head_create sizes the workspace by this pick, and head_moments picks again under that size: the same number
+    const int n = gram_choose_splits(channels, npix, head_gram_split_cap(channels));
+    if (splits) *splits = n;
+    if (per_split) *per_split = gram_per_split(npix, n);
+    if (wide) *wide = (precision == 4 && gram_wide_tiles(channels, npix)) ? 1 : 0;
+    return 0;
+}
+
 int st_head_destroy(st_head* h) {
     if (!h) return 0;
     for (void* p : h->allocations) hipFree(p);

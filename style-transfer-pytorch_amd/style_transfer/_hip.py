@@ -160,6 +160,7 @@ def _declare(lib):
         'st_head_device_bytes': (i64, [vp]),
         'st_head_state_floats': (i64, [vp]),
         'st_head_moments': (i32, [vp, vp, vp, vp, vp]),
+        'st_op_gram_split_plan': (i32, [i32, i64, i32, ip, ctypes.POINTER(i64), ip]),
         'st_head_forward': (i32, [vp, vp, vp, vp, vp, vp, f32, vp, vp, vp]),
         'st_head_backward': (i32, [vp, vp, vp, vp, vp, vp]),
         'st_op_reduce_scratch_floats': (i64, []),
@@ -1528,6 +1529,16 @@ def op_w2_diag_loss_backward(x, coeffs, upstream):
 def sort_chunk():
     """The keys one workgroup of the segmented sort orders in LDS (st_op_sort_chunk): rows up to this length need no merge pass."""
     return int(load_library().st_op_sort_chunk())
+
+
+def gram_split_plan(channels, npix, precision='fp16x3'):
+    """(splits, per_split, wide) of the Gram moments of a [channels, npix] tap as ``Head(..., precision).moments`` runs them
+    (st_op_gram_split_plan; no device call): split s owns the pixels [s per_split, min((s + 1) per_split, npix))."""
+    lib = load_library(require_gpu=False)
+    splits, per_split, wide = ctypes.c_int(), ctypes.c_longlong(), ctypes.c_int()
+    _check(lib.st_op_gram_split_plan(int(channels), int(npix), Net.PRECISIONS[precision], ctypes.byref(splits),
+                                     ctypes.byref(per_split), ctypes.byref(wide)))
+    return splits.value, per_split.value, bool(wide.value)
 
 
 def _rows(x):
