@@ -1053,6 +1053,19 @@ int st_op_sliced_loss_backward(const float* unit_grad, long long count, const fl
 int st_op_tv_value(const float* image, int height, int width, float* scratch, float* loss_out, void* stream);
 /* ... and grad [3][H][W] = upstream[0] * d TVLoss / d image. */
 int st_op_tv_loss_backward(const float* image, int height, int width, const float* upstream, float* grad, void* stream);
+/* The closure's ONE-launch forms of the content MSE and TV terms (value and gradient in the launch that streams the data;
+ * the last workgroup by ticket adds the per-workgroup partial sums in index order), by the plan's own kernels:
+ *   st_op_mse_term:  loss_out[0] = weight sum (x - t)^2 / count, grad_out[i] = weight 2 (x - t)[i] / count; x, target and
+ *                    grad_out 16-byte aligned
+ *   st_op_tv_term:   loss_out[0] = weight TVLoss(image), grad_out [3][H][W] = weight d TVLoss / d image
+ * `scratch`: st_op_reduce_scratch_floats() floats of the caller's; `ticket`: ONE device word of the caller's that is zero
+ * before the first call - every call leaves it zero, so calls on one stream may share scratch and ticket back to back.
+ * ST_LAST_BLOCK_FENCE (st_set_option) chooses how the partial sums are handed to the last workgroup; the bits do not depend
+ * on it. */
+int st_op_mse_term(const float* x, const float* target, long long count, float weight, float* scratch, unsigned int* ticket,
+                   float* loss_out, float* grad_out, void* stream);
+int st_op_tv_term(const float* image, int height, int width, float weight, float* scratch, unsigned int* ticket, float* loss_out,
+                  float* grad_out, void* stream);
 /* The Laplacian loss of st_plan_set_laplacian for ONE pool size on a [C][H][W] image, C >= 1, at weight 1, by the same
  * kernels.  `scratch`: st_op_laplacian_scratch_floats(C, H, W, pool) floats of the caller's, per call.  The target
  * [C][H / pool][W / pool] = L(Q(image)) ... */

@@ -844,6 +844,11 @@ int loss_and_grad(st_plan* p, const float* image, float* grad_out, float* losses
         return 0;
     };
     if (p->aux_stream && content(p->aux_stream)) return 1;
+    // ST_CONTENT_SLOT=1 (A/B, profiles/last_block.md): the content MSE on the caller's stream right behind the forward trunk,
+    // in front of relu5_1's head, instead of the tail of relu4_1's head stream
+    static Option content_slot_opt("ST_CONTENT_SLOT", 0);
+    const bool content_on_caller = content_slot_opt.get() == 1 && !p->aux_stream;
+    if (content_on_caller && content(s)) return 1;
     // style heads: one side stream each, gated on their tap's event, enqueued in the order the backward pass needs
     // them: relu5_1's chain gates the whole backward, relu1_1's is needed last - the host must not spend ~1 ms
     // enqueueing the other heads before the critical one
@@ -865,7 +870,7 @@ int loss_and_grad(st_plan* p, const float* image, float* grad_out, float* losses
         if (style_head(p, head_site(p, k), hs)) return 1;
         ST_HIP(hipEventRecord(p->head_done[k], hs));
         if (p->timeline) ST_HIP(hipEventRecord(p->tl_head[k], hs));
-        if (k == 3 && !p->aux_stream && content(p->head_stream[3])) return 1;
+        if (k == 3 && !p->aux_stream && !content_on_caller && content(p->head_stream[3])) return 1;
     }
     if (lockstep) {
         // (tried, round 4: relu3_1's head on a stream of its own and only relu2_1 / relu1_1 sharing launches, because at 128^2

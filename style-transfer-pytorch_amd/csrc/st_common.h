@@ -121,13 +121,36 @@ __device__ __forceinline__ float block_sum_256(float v, float* scratch) {
 
 // In-kernel final reduction ("last block") of the streaming value kernels (st_pointwise.hip, st_laplacian.hip): every block writes
 // its partial sums, then takes a ticket; the block that draws the last one sums all partials in index order.
+// The hand-off: thread 0 stores the block's N partial sums WRITE-THROUGH (agent-scope relaxed atomic stores: sc1), waits for
+// them (the asm waitcnt; the compiler's own may be dropped) and only then takes the ticket - no release fence, which on gfx950
+// writes back ALL of the XCD L2's dirty lines (the gradient the block has just streamed out) once per workgroup to publish
+// four to sixteen bytes (profiles/last_block.md).  The helper does the stores itself, so no caller can leave a plain store in
+// front of the fence-free ticket; storing, waiting and taking the ticket are one wave's (thread 0's) business.  The consumer
+// side is an agent-scope acquire in every thread of the last block, then plain loads.
+// release_fence (ST_LAST_BLOCK_FENCE=1, A/B and tests): the former hand-off - plain stores, an agent-scope release fence.
 struct LastBlock {
     unsigned int* ticket;     // device word, zero between launches (the last block resets it); nullptr = two-launch form
+    int release_fence;
 };
-__device__ __forceinline__ bool last_block_arrives(const LastBlock& lb, bool* shared_flag) {
-    if (lb.ticket == nullptr) return false;
+LastBlock last_block(unsigned int* ticket);       // st_pointwise.hip: the flavour the switch selects
+// every thread of the block calls it; `mine` = where the block's N partials go, v = their values (thread 0's are stored)
+template <int N>
+__device__ __forceinline__ bool last_block_arrives(const LastBlock& lb, bool* shared_flag, float* mine, const float (&v)[N]) {
+    if (lb.ticket == nullptr) {       // the next launch on the stream reads them
+        if (threadIdx.x == 0)
+#pragma unroll
+            for (int k = 0; k < N; ++k) mine[k] = v[k];
+        return false;
+    }
     if (threadIdx.x == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        if (lb.release_fence) {
+#pragma unroll
+            for (int k = 0; k < N; ++k) mine[k] = v[k];
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        } else {
+#pragma unroll
+            for (int k = 0; k < N; ++k) __hip_atomic_store(mine + k, v[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         const unsigned int prev = atomicAdd(lb.ticket, 1u);
         const bool last = (prev == gridDim.x - 1);

@@ -477,4 +477,20 @@ int st_op_tv_loss_backward(const float* image, int height, int width, const floa
     return 0;
 }
 
+// the closure's one-launch forms (launch_content_mse / launch_tv with a ticket) on the caller's scratch and ticket word
+int st_op_mse_term(const float* x, const float* target, long long count, float weight, float* scratch, unsigned int* ticket,
+                   float* loss_out, float* grad_out, void* stream) {
+    ST_REQUIRE(x && target && scratch && ticket && loss_out && grad_out && count > 0, "st_op_mse_term: null argument or empty tensor");
+    ST_REQUIRE(aligned16(x) && aligned16(target) && aligned16(grad_out), "st_op_mse_term: x, target and grad_out must be 16-byte aligned");
+    return launch_content_mse(x, target, count, weight, grad_out, scratch, loss_out, static_cast<hipStream_t>(stream), ticket);
+}
+
+int st_op_tv_term(const float* image, int height, int width, float weight, float* scratch, unsigned int* ticket, float* loss_out,
+                  float* grad_out, void* stream) {
+    ST_REQUIRE(image && scratch && ticket && loss_out && grad_out, "st_op_tv_term: null argument");
+    ST_REQUIRE(height >= 1 && width >= 1, "st_op_tv_term: bad shape %d x %d", height, width);
+    ST_REQUIRE_PIXELS("st_op_tv_term", (long long)height * width);
+    return launch_tv(image, height, width, weight, grad_out, scratch, loss_out, static_cast<hipStream_t>(stream), ticket);
+}
+
 }  // extern "C"

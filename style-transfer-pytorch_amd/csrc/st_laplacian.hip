@@ -99,8 +99,8 @@ __global__ __launch_bounds__(256) void lap_residual_kernel(const float* __restri
     }
     if (target == nullptr) return;
     s = block_sum_256(s, scratch);
-    if (threadIdx.x == 0) partials[blockIdx.x] = s;
-    if (!last_block_arrives(lb, &is_last)) return;
+    const float mine[1] = {s};
+    if (!last_block_arrives(lb, &is_last, partials + blockIdx.x, mine)) return;
     float t = 0.f;
     for (int i = threadIdx.x; i < (int)gridDim.x; i += 256) t += partials[i];
     t = block_sum_256(t, scratch);
@@ -203,7 +203,7 @@ int launch_lap_residual(const float* Q, const float* target, int C, int h, int w
                         unsigned int* ticket, float* term_out, float* tv_out, float* slot, hipStream_t s) {
     const int blocks = lap_grid((long long)C * h * w);
     const float count = (float)((double)C * h * w);
-    hipLaunchKernelGGL(lap_residual_kernel, dim3(blocks), dim3(256), 0, s, Q, target, C, h, w, out, partials, LastBlock{ticket},
+    hipLaunchKernelGGL(lap_residual_kernel, dim3(blocks), dim3(256), 0, s, Q, target, C, h, w, out, partials, last_block(ticket),
                        count, weight, term_out, tv_out, slot);
     ST_LAUNCH_CHECK();
     if (target && !ticket) {

@@ -323,8 +323,8 @@ __global__ __launch_bounds__(256) void nearest_finish_kernel(const float* __rest
         __syncthreads();
     }
     acc = block_sum_256(acc, scratch);
-    if (tid == 0) partials[blockIdx.x] = acc;
-    if (!last_block_arrives(lb, &is_last)) return;
+    const float part[1] = {acc};
+    if (!last_block_arrives(lb, &is_last, partials + blockIdx.x, part)) return;
     // the last block: thread t adds partials [t per, (t + 1) per) in index order, thread 0 the 256 sums in thread order
     const long long blocks = gridDim.x, per = (blocks + 255) / 256;
     double mine = 0.0;
@@ -442,7 +442,7 @@ int launch_nearest_finish(const float* feat, int channels, long long n, const Ne
     fin.loss_out = loss_out;
     const int cgroups = (channels / KC + FCH - 1) / FCH;
     hipLaunchKernelGGL(nearest_finish_kernel, dim3((unsigned)finish_blocks(channels, n)), dim3(256), 0, s, feat, pr.st_t, sc.part_score,
-                       sc.part_k, sc.splits, n, channels, pr.m, cgroups, idx_out, score_out, grad, sc.partials, LastBlock{sc.ticket}, fin);
+                       sc.part_k, sc.splits, n, channels, pr.m, cgroups, idx_out, score_out, grad, sc.partials, last_block(sc.ticket), fin);
     ST_LAUNCH_CHECK();
     return 0;
 }

@@ -115,9 +115,10 @@ __global__ __launch_bounds__(256) void ns_prepare_kernel(const float* __restrict
 // In-kernel final reduction ("last block"): every block writes its partial sums, then takes a ticket; the block
 // that draws the last one sums all partials in index order (deterministic for a given grid) and writes the loss.
 // Saves the second launch - a single wave that, next to the trunk's persistent convolution workgroups, used to
-// wait up to 0.7 ms for a free CU at 2048^2.  Release / acquire at agent scope as MI355X_MICROARCH.md prescribes
-// (the asm waitcnt keeps the ticket behind the write-back of the partials).
-// (LastBlock / last_block_arrives: st_common.h, shared with st_laplacian.hip)
+// wait up to 0.7 ms for a free CU at 2048^2.  The partials are handed over write-through: sc1 stores, a wait, the ticket - no
+// release fence, whose write-back of the XCD L2 (the 4 KB of gradient each of the 2048 workgroups has just dirtied) was most of
+// this kernel's time at 512^2; the last block acquires at agent scope (LastBlock / last_block_arrives, st_common.h, which
+// every kernel with such a sum shares; profiles/last_block.md).
 // ACC (general closure, st_taps.hip): the layer is a style layer as well, whose head has WRITTEN grad - this term's is added.
 template <bool ACC>
 __global__ __launch_bounds__(256) void content_mse_kernel(const float* __restrict__ feat,
@@ -156,8 +157,8 @@ __global__ __launch_bounds__(256) void content_mse_kernel(const float* __restric
         }
     }
     s = block_sum_256(s, scratch);
-    if (threadIdx.x == 0) partials[blockIdx.x] = s;
-    if (!last_block_arrives(lb, &is_last)) return;
+    const float mine[1] = {s};
+    if (!last_block_arrives(lb, &is_last, partials + blockIdx.x, mine)) return;
     float t = 0.f;
     for (int i = threadIdx.x; i < (int)gridDim.x; i += 256) t += partials[i];
     t = block_sum_256(t, scratch);
@@ -222,11 +223,8 @@ __global__ __launch_bounds__(256) void scaled_mse_sums_kernel(const float* __res
     }
     s2 = block_sum_256(s2, scratch);
     s1 = block_sum_256(s1, scratch);
-    if (threadIdx.x == 0) {
-        partials[2 * blockIdx.x] = s2;
-        partials[2 * blockIdx.x + 1] = s1;
-    }
-    if (!last_block_arrives(lb, &is_last)) return;
+    const float mine[2] = {s2, s1};
+    if (!last_block_arrives(lb, &is_last, partials + 2 * blockIdx.x, mine)) return;
     float t2 = 0.f, t1 = 0.f;
     for (int i = threadIdx.x; i < (int)gridDim.x; i += 256) {
         t2 += partials[2 * i];
@@ -332,8 +330,8 @@ __global__ __launch_bounds__(256) void content_mse_w_kernel(const float* __restr
         }
     }
     s = block_sum_256(s, scratch);
-    if (threadIdx.x == 0) partials[blockIdx.x] = s;
-    if (!last_block_arrives(lb, &is_last)) return;
+    const float mine[1] = {s};
+    if (!last_block_arrives(lb, &is_last, partials + blockIdx.x, mine)) return;
     float t = 0.f;
     for (int i = threadIdx.x; i < (int)gridDim.x; i += 256) t += partials[i];
     t = block_sum_256(t, scratch);
@@ -374,11 +372,8 @@ __global__ __launch_bounds__(256) void scaled_mse_sums_w_kernel(const float* __r
     }
     s2 = block_sum_256(s2, scratch);
     s1 = block_sum_256(s1, scratch);
-    if (threadIdx.x == 0) {
-        partials[2 * blockIdx.x] = s2;
-        partials[2 * blockIdx.x + 1] = s1;
-    }
-    if (!last_block_arrives(lb, &is_last)) return;
+    const float mine[2] = {s2, s1};
+    if (!last_block_arrives(lb, &is_last, partials + 2 * blockIdx.x, mine)) return;
     float t2 = 0.f, t1 = 0.f;
     for (int i = threadIdx.x; i < (int)gridDim.x; i += 256) {
         t2 += partials[2 * i];
@@ -755,11 +750,8 @@ __global__ __launch_bounds__(256) void tv_border_kernel(const float* __restrict_
     s2 = block_sum_256(s2, scratch);
     s3 = block_sum_256(s3, scratch);
     s4 = block_sum_256(s4, scratch);
-    if (threadIdx.x == 0) {
-        float* mine = partials + (size_t)(first + blockIdx.x) * 4;
-        mine[0] = s1; mine[1] = s2; mine[2] = s3; mine[3] = s4;
-    }
-    if (!last_block_arrives(lb, &is_last)) return;
+    const float mine[4] = {s1, s2, s3, s4};
+    if (!last_block_arrives(lb, &is_last, partials + (size_t)(first + blockIdx.x) * 4, mine)) return;
     const int nparts = first + (int)gridDim.x;
     float t[4] = {0.f, 0.f, 0.f, 0.f};
     for (int i = threadIdx.x; i < nparts; i += 256)
@@ -958,11 +950,8 @@ __global__ __launch_bounds__(256) void tv_border_w_kernel(const float* __restric
     s2 = block_sum_256(s2, scratch);
     s3 = block_sum_256(s3, scratch);
     s4 = block_sum_256(s4, scratch);
-    if (threadIdx.x == 0) {
-        float* mine = partials + (size_t)(first + blockIdx.x) * 4;
-        mine[0] = s1; mine[1] = s2; mine[2] = s3; mine[3] = s4;
-    }
-    if (!last_block_arrives(lb, &is_last)) return;
+    const float mine[4] = {s1, s2, s3, s4};
+    if (!last_block_arrives(lb, &is_last, partials + (size_t)(first + blockIdx.x) * 4, mine)) return;
     const int nparts = first + (int)gridDim.x;
     float t[4] = {0.f, 0.f, 0.f, 0.f};
     for (int i = threadIdx.x; i < nparts; i += 256)
@@ -1147,16 +1136,23 @@ int launch_scaled_identity_div(const float* diag_value, const float* scalar, flo
 // streaming kernels with a two-level sum: up to kStreamBlocks workgroups (8 waves per SIMD chip-wide) of 256 threads
 static int stream_blocks(long long work_items) { return grid_for(work_items, kStreamBlocks); }
 
+// ST_LAST_BLOCK_FENCE=1: the partials' former hand-off (plain stores behind an agent-scope release fence), for A/B runs and
+// tests/test_last_block_gpu.py; both flavours give the same bits
+LastBlock last_block(unsigned int* ticket) {
+    static Option fence_opt("ST_LAST_BLOCK_FENCE", 0);
+    return LastBlock{ticket, ticket != nullptr && fence_opt.get() != 0 ? 1 : 0};
+}
+
 int launch_content_mse(const float* feat, const float* target, long long count, float weight, float* grad,
                        float* partials, float* loss_out, hipStream_t s, unsigned int* ticket, int accumulate) {
     const int blocks = stream_blocks((count & 3) == 0 ? count / 4 : count);
     const float norm = (float)(2.0 / (double)count);
     if (accumulate)
         hipLaunchKernelGGL(content_mse_kernel<true>, dim3(blocks), dim3(256), 0, s, feat, target, count, weight, norm,
-                           grad, partials, LastBlock{ticket}, (float)count, loss_out);
+                           grad, partials, last_block(ticket), (float)count, loss_out);
     else
         hipLaunchKernelGGL(content_mse_kernel<false>, dim3(blocks), dim3(256), 0, s, feat, target, count, weight, norm,
-                           grad, partials, LastBlock{ticket}, (float)count, loss_out);
+                           grad, partials, last_block(ticket), (float)count, loss_out);
     ST_LAUNCH_CHECK();
     if (ticket) return 0;                 // the last block wrote the loss
     hipLaunchKernelGGL(content_mse_final_kernel, dim3(1), dim3(64), 0, s, partials, blocks, (float)count,
@@ -1170,7 +1166,7 @@ int launch_scaled_mse_sums(const float* x, const float* target, long long count,
     ST_REQUIRE(ticket, "scaled MSE sums: the last block finishes the sum, a ticket word is needed");
     const int blocks = stream_blocks((count & 3) == 0 ? count / 4 : count);
     hipLaunchKernelGGL(scaled_mse_sums_kernel, dim3(blocks), dim3(256), 0, s, x, target, count, weight, eps, partials,
-                       LastBlock{ticket}, totals, loss_out);
+                       last_block(ticket), totals, loss_out);
     ST_LAUNCH_CHECK();
     return 0;
 }
@@ -1195,10 +1191,10 @@ int launch_content_mse_weighted(const float* feat, const float* target, const fl
     const float norm = (float)(2.0 / (double)count);
     if (accumulate)
         hipLaunchKernelGGL(content_mse_w_kernel<true>, dim3(blocks), dim3(256), 0, s, feat, target, wmap, count, npix, weight, norm,
-                           grad, partials, LastBlock{ticket}, (float)count, loss_out);
+                           grad, partials, last_block(ticket), (float)count, loss_out);
     else
         hipLaunchKernelGGL(content_mse_w_kernel<false>, dim3(blocks), dim3(256), 0, s, feat, target, wmap, count, npix, weight, norm,
-                           grad, partials, LastBlock{ticket}, (float)count, loss_out);
+                           grad, partials, last_block(ticket), (float)count, loss_out);
     ST_LAUNCH_CHECK();
     return 0;
 }
@@ -1209,7 +1205,7 @@ int launch_scaled_mse_sums_weighted(const float* x, const float* target, const f
     ST_REQUIRE(wmap && ticket && npix > 0 && count % npix == 0, "weighted scaled MSE sums: bad argument");
     const int blocks = stream_blocks((npix & 3) == 0 ? count / 4 : count);
     hipLaunchKernelGGL(scaled_mse_sums_w_kernel, dim3(blocks), dim3(256), 0, s, x, target, wmap, count, npix, weight, eps, partials,
-                       LastBlock{ticket}, totals, loss_out);
+                       last_block(ticket), totals, loss_out);
     ST_LAUNCH_CHECK();
     return 0;
 }
@@ -1327,7 +1323,7 @@ int launch_tv(const float* image, int height, int width, float weight, float* gr
     const float k3 = (float)(weight * 4.0 / (12.0 * n2));
     StripInfo whole{0, height, 0, 0, nullptr};
     int nparts = 0;
-    if (launch_tv_kernels(image, height, width, whole, k1, k3, grad, partials, LastBlock{ticket}, (float)n, (float)n2,
+    if (launch_tv_kernels(image, height, width, whole, k1, k3, grad, partials, last_block(ticket), (float)n, (float)n2,
                           weight, loss_out, s, &nparts, wmap))
         return 1;
     if (ticket) return 0;                 // the border kernel's last block wrote the loss
@@ -1343,7 +1339,7 @@ int launch_tv_strip(const float* image, int height, int width, StripInfo strip, 
     const float k1 = (float)(weight * 4.0 / (3.0 * n));
     const float k3 = (float)(weight * 4.0 / (12.0 * n2));
     int nparts = 0;
-    if (launch_tv_kernels(image, height, width, strip, k1, k3, grad, partials, LastBlock{nullptr}, 0.f, 0.f, 0.f,
+    if (launch_tv_kernels(image, height, width, strip, k1, k3, grad, partials, last_block(nullptr), 0.f, 0.f, 0.f,
                           nullptr, s, &nparts))
         return 1;
     hipLaunchKernelGGL(reduce_partials_kernel, dim3(1), dim3(64), 0, s, partials, nparts, 4, sums4);
@@ -1365,7 +1361,7 @@ int launch_content_mse_strip(const float* feat, const float* target, long long l
     const int blocks = stream_blocks((local_count & 3) == 0 ? local_count / 4 : local_count);
     const float norm = (float)(2.0 / (double)global_count);
     hipLaunchKernelGGL(content_mse_kernel<false>, dim3(blocks), dim3(256), 0, s, feat, target, local_count, weight, norm,
-                       grad, partials, LastBlock{nullptr}, 0.f, static_cast<float*>(nullptr));
+                       grad, partials, last_block(nullptr), 0.f, static_cast<float*>(nullptr));
     ST_LAUNCH_CHECK();
     hipLaunchKernelGGL(reduce_partials_kernel, dim3(1), dim3(64), 0, s, partials, blocks, 1, sum_out);
     ST_LAUNCH_CHECK();

@@ -158,8 +158,8 @@ __global__ __launch_bounds__(256) void marginal_residual_kernel(const u64* __res
         acc += d * d;
     }
     acc = block_sum_256(acc, scratch);
-    if (threadIdx.x == 0) partials[blockIdx.x] = acc;
-    if (!last_block_arrives(lb, &is_last)) return;
+    const float part[1] = {acc};
+    if (!last_block_arrives(lb, &is_last, partials + blockIdx.x, part)) return;
     // the last block: thread t adds partials [t per, (t + 1) per) in index order, thread 0 the 256 sums in thread order
     const int blocks = (int)gridDim.x, per = (blocks + 255) / 256;
     double mine = 0.0;
@@ -269,7 +269,7 @@ int launch_marginal_residual(const MarginalScratch& m, const float* target, int 
     fin.coef = (float)((double)weight * 2.0 / (double)count);
     fin.loss_out = loss_out;
     hipLaunchKernelGGL(marginal_residual_kernel, dim3(stream_blocks(count)), dim3(256), 0, s, m.keys_a, target, n, count, grad, m.partials,
-                       LastBlock{m.ticket}, fin);
+                       last_block(m.ticket), fin);
     ST_LAUNCH_CHECK();
     return 0;
 }

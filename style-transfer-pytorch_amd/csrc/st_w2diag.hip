@@ -66,11 +66,8 @@ __global__ __launch_bounds__(256) void channel_stats_kernel(const float* __restr
     }
     s1 = block_sum_256(s1, scratch);
     s2 = block_sum_256(s2, scratch);
-    if (threadIdx.x == 0) {           // [c][split][2]
-        partials[2 * blockIdx.x] = s1;
-        partials[2 * blockIdx.x + 1] = s2;
-    }
-    if (!last_block_arrives(lb, &is_last)) return;
+    const float mine[2] = {s1, s2};   // [c][split][2]
+    if (!last_block_arrives(lb, &is_last, partials + 2 * blockIdx.x, mine)) return;
     // the last block: a thread per channel, 256 channels at a time; thread 0 adds their contributions in channel order
     double t_mean = 0.0, t_std = 0.0;
     for (int base = 0; base < channels; base += 256) {
@@ -190,7 +187,7 @@ int launch_channel_stats(const float* feat, const float* sqrt_mask, int channels
     if (check_shape("launch_channel_stats", channels, npix)) return 1;
     const int splits = channel_stats_splits(npix);
     const int vec = (npix & 3) == 0 && aligned16(feat) && (!sqrt_mask || aligned16(sqrt_mask));
-    const LastBlock lb{reinterpret_cast<unsigned int*>(scratch)};
+    const LastBlock lb = last_block(reinterpret_cast<unsigned int*>(scratch));
     const dim3 grid((unsigned)(channels * splits));
     if (sqrt_mask)
         hipLaunchKernelGGL(channel_stats_kernel<true>, grid, dim3(256), 0, s, feat, sqrt_mask, channels, npix, splits, vec, scratch + 4, lb, fin);

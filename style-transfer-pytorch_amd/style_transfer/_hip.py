@@ -196,6 +196,8 @@ def _declare(lib):
         'st_op_sliced_loss_backward': (i32, [vp, i64, vp, vp, vp]),
         'st_op_tv_value': (i32, [vp, i32, i32, vp, vp, vp]),
         'st_op_tv_loss_backward': (i32, [vp, i32, i32, vp, vp, vp]),
+        'st_op_mse_term': (i32, [vp, vp, i64, f32, vp, vp, vp, vp, vp]),
+        'st_op_tv_term': (i32, [vp, i32, i32, f32, vp, vp, vp, vp, vp]),
         'st_op_laplacian_scratch_floats': (i64, [i32, i32, i32, i32]),
         'st_op_laplacian_target': (i32, [vp, i32, i32, i32, i32, vp, vp, vp]),
         'st_op_laplacian_value': (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
@@ -1330,6 +1332,37 @@ def op_tv_loss(image):
     grad = torch.empty_like(image)
     with torch.cuda.device(image.device):
         _check(lib.st_op_tv_loss(_ptr(image.contiguous()), h, w, _ptr(loss), _ptr(grad), _stream()))
+    return loss, grad
+
+
+def term_scratch(device):
+    """(scratch, ticket) for op_mse_term / op_tv_term: the reduction scratch and ONE zeroed ticket word, which every call leaves
+    zero - calls on one stream may share the pair back to back."""
+    return _reduce_scratch(device), torch.zeros(4, device=device, dtype=torch.int32)
+
+
+def op_mse_term(x, target, weight=1.0, scratch=None, loss=None, grad=None):
+    """The closure's one-launch content MSE (st_op_mse_term): (loss [1], grad) by the plan's own kernel, the value finished by
+    the launch's last workgroup.  scratch: a ``term_scratch`` pair to share between calls; loss / grad: outputs to write into."""
+    lib = load_library()
+    partials, ticket = scratch if scratch is not None else term_scratch(x.device)
+    loss = torch.zeros(1, device=x.device, dtype=torch.float32) if loss is None else loss
+    grad = torch.empty_like(x) if grad is None else grad
+    with torch.cuda.device(x.device):
+        _check(lib.st_op_mse_term(_ptr(x), _ptr(target), x.numel(), float(weight), _ptr(partials), ctypes.c_void_p(ticket.data_ptr()), _ptr(loss),
+                                  _ptr(grad), _stream()))
+    return loss, grad
+
+
+def op_tv_term(image, weight=1.0, scratch=None, loss=None, grad=None):
+    """The closure's TV term (st_op_tv_term): (loss [1], grad) with the value finished by the border launch's last workgroup."""
+    lib = load_library()
+    h, w = image.shape[-2:]
+    partials, ticket = scratch if scratch is not None else term_scratch(image.device)
+    loss = torch.zeros(1, device=image.device, dtype=torch.float32) if loss is None else loss
+    grad = torch.empty_like(image) if grad is None else grad
+    with torch.cuda.device(image.device):
+        _check(lib.st_op_tv_term(_ptr(image), h, w, float(weight), _ptr(partials), ctypes.c_void_p(ticket.data_ptr()), _ptr(loss), _ptr(grad), _stream()))
     return loss, grad
 
 
