@@ -475,8 +475,9 @@ int st_plan_style_quantiles(st_plan* plan, int index, float** target, int* chann
  *   term_j = w_j sum_i |f_i - s_k*(i)|^2 / (C N)
  *   dF_ci  = w_j (2 / (C N)) (f_ci - s_c,k*(i))
  * The match is a constant of the gradient: the a.e. derivative of min_k, so the gradient is the true gradient of the term.  The
- * matching is L2, not cosine, for that reason: the term is the quantity the search minimises - the one-sided Chamfer distance
- * from the tap to the style set.  There is no eps.  Inputs are finite; with a NaN the result is unspecified, but every launch
+ * term is the quantity the search minimises - the one-sided Chamfer distance from the tap to the style set - under the default
+ * L2 metric and, with its own term, under the cosine and centred-cosine metrics of st_plan_set_nearest_metric below.  There is
+ * no eps.  Inputs are finite; with a NaN the result is unspecified, but every launch
  * ends (no loop's trip count depends on a comparison of values, and an index is clamped into [0, M) before it is an address).
  * bias_k = -|s_k|^2 / 2 is formed once by st_plan_set_style_vectors, in double, and rounded to fp32.  The search
  * (csrc/st_nearest.hip) runs in the trunk's fp16x3 arithmetic with fp32 accumulation - S^T [M_pad][C] against the tap, both
@@ -513,6 +514,48 @@ int st_plan_set_style_vectors(st_plan* plan, int index, const float* feat, long 
 /* Borrows the matches of the last closure for flagged entry `index`: *idx [n] ints of the plan's (device memory), k*(i) in
  * [0, m), valid until the plan is destroyed and rewritten by every closure. */
 int st_plan_nearest_indices(st_plan* plan, int index, const int** idx, long long* n);
+/*
+ * What a flagged entry is matched on: metrics[n_style] in list order, a null pointer means all 0.
+ *   0 'l2'               the head above, bit for bit
+ *   1 'cosine'           the neural-neighbour family's own metric (the contextual loss, STROTSS): a ReLU tap's vectors differ in
+ *                        length by an order of magnitude across a picture, and under L2 a dim region is pulled to the style's
+ *                        shortest vectors whatever their direction
+ *   2 'centered_cosine'  cosine after subtracting the style set's mean feature (NNST)
+ * The reference has no such module, so the semantics are fixed here.  eps = 1e-8, under both square roots below (as ContentLoss's
+ * 1e-8, it is not an argument).  For metrics 1 and 2, with the style vectors S [C][M] handed to st_plan_set_style_vectors (after
+ * any selection the caller made) and the tap F [C][N]:
+ *   mu     = 0 (metric 1), or mu_c = (1/M) sum_k s_ck (metric 2): summed in double in ascending k, rounded to fp32 once
+ *   s^_k   = (s_k - mu) / sqrt(|s_k - mu|^2 + eps): formed in double by the setter and rounded to fp32 once; a zero vector stays zero
+ *   b_k    = -<mu, s^_k>: from the rounded s^_k and the rounded mu, summed in double in channel order, rounded once (0 for metric
+ *            1); in the padding rows b_k = -inf and the row is zero
+ *   g_i    = f_i - mu,   p_i(k) = <g_i, s^_k>,   r_i = sqrt(|g_i|^2 + eps)
+ *   k*(i)  = argmax_k p_i(k) = argmax_k (<f_i, s^_k> + b_k),   ties: the lowest k
+ *   term_j = w_j sum_i (1 - p_i(k*(i)) / r_i) / N            (divided by N, not by C; in [0, 2 w_j])
+ *   dF_ci  = (w_j / N) (-s^_c,k*(i) / r_i + p_i(k*(i)) g_ci / r_i^3)
+ * r_i > 0 does not depend on k, so k*(i) also maximises the cosine p_i(k) / r_i: the term is exactly what the search minimises.
+ * The match and mu are constants of the gradient, which is the true gradient of the term almost everywhere.  At a tap pixel that
+ * equals mu exactly the gradient is -(w_j / N) s^_k* / sqrt(eps).
+ * The search is the L2 head's, unchanged, on the rows s^^T [M_pad][C] and the bias b: the prepared buffer is laid out as L2's -
+ * bound word (max |s^|, measured, at most 1), bias, rows - with mu [C], padded to 64 floats, behind it.  The finish pass
+ * (csrc/st_nearest.hip) is its own: one launch in which a workgroup owns 64 pixels and all their channels, merges the splits,
+ * gathers s^_k*, recomputes p_i and |g_i|^2 in fp32 from g = f - mu (never the search's score) in a fixed channel order, WRITES
+ * dF and the indices and reduces the term as every head does (per-block fp32 partials, the write-through hand-over to the last
+ * block, its index-order sum in double).  No floating-point atomics: two closures give the same bits, indices included.  A match
+ * is optimal up to the search's arithmetic (tests/test_nearest_cosine_gpu.py derives the bound on p_i(k_best) - p_i(k*)).
+ * There is no user eps: an entry with a custom style eps cannot be flagged, as above.  Several style images give the union of
+ * their vectors, and mu is the mean of that union.  Inputs are finite; with a NaN the result is unspecified, but every launch
+ * ends and an index is clamped into [0, M) before it is an address.
+ * Call it after st_plan_set_style_nearest - which resets every metric to 0, so existing callers see no change - and before the
+ * weights and targets: st_plan_set_style_vectors prepares by the entry's metric and sizes the prepared and scratch buffers by it
+ * (st_plan_device_bytes counts them).  Like the other option setters the call drops every target set before and invalidates a
+ * captured graph; either kinds setter and st_plan_set_taps clear the metrics, as they clear the flags.  Metrics that are all 0, or
+ * set and then cleared, leave, bit for bit, the plan with the same flags and no metric call.
+ * Fails for a value outside 0..2 and for a non-zero metric on an entry that is not flagged.
+ * Order of configuration, in full: layers, kinds, eps, diagonal, marginal, nearest, nearest metric, sliced (flags, options, seed),
+ * weights, then the targets.
+ */
+int st_plan_set_nearest_metric(st_plan* plan, const int* metrics);
+int st_plan_nearest_metric(const st_plan* plan, int* metrics);
 
 /*
  * The sliced Wasserstein option of a W2 style layer: flags[n_style], 0 or 1 in list order; a null pointer clears all.  The
@@ -1018,6 +1061,21 @@ int st_op_nearest_search(const float* feat, int channels, long long n, const flo
  * (autograd: saved on the node) ... */
 int st_op_nearest_loss(const float* feat, int channels, long long n, const float* prepared, long long m, float* scratch, int* idx_out,
                        float* unit_grad_out, float* loss_out, void* stream);
+/* The cosine (centered = 0) and centred-cosine (centered = 1) metrics of st_plan_set_nearest_metric on ONE dense fp32 tensor, by
+ * the same kernels and for the same shapes: C a multiple of 32, n >= 1 pixels against m >= 1 style vectors, n and m at most
+ * st_max_pixels() (refused before any work).  st_op_nearest_cosine_prepare: vectors [C][m] -> prepared,
+ * st_op_nearest_cosine_prepared_floats(C, m) floats of the caller's: L2's layout with the unit rows, b and the bound on max |s^|,
+ * then mu [C] padded to 64 floats - so st_op_nearest_search runs on it as on an L2 one and serves all three metrics (its score
+ * is then <f_i, s^_k*> + b_k*).  `scratch`: st_op_nearest_cosine_scratch_floats(C, n, m) floats, per call.
+ * st_op_nearest_cosine_loss: loss_out[0] = sum_i (1 - p_i(k*(i)) / r_i) / n at weight 1; idx_out [n] the matches;
+ * unit_grad_out [C][n] = d loss / d feat.  st_op_nearest_loss_backward serves the backward.  Two calls give the same bits.
+ * Alignment: `prepared` and `scratch` must be 256-byte aligned (refused otherwise); every other buffer may be merely 4-byte
+ * aligned. */
+long long st_op_nearest_cosine_prepared_floats(int channels, long long m);
+long long st_op_nearest_cosine_scratch_floats(int channels, long long n, long long m);
+int st_op_nearest_cosine_prepare(const float* vectors, int channels, long long m, int centered, float* prepared, void* stream);
+int st_op_nearest_cosine_loss(const float* feat, int channels, long long n, const float* prepared, long long m, float* scratch,
+                              int* idx_out, float* unit_grad_out, float* loss_out, void* stream);
 /* ... grad[i] = upstream[0] * unit_grad[i], i < count; upstream: a DEVICE scalar. */
 int st_op_nearest_loss_backward(const float* unit_grad, long long count, const float* upstream, float* grad, void* stream);
 /* The sliced head of st_plan_set_style_sliced on ONE dense fp32 tensor feat [C][n], by the same kernels: C a multiple of 32, P a

@@ -529,9 +529,13 @@ int st_plan_set_style_vectors(st_plan* p, int index, const float* feat, long lon
     // the entry holds no target until the new set is written
     h.target_set = false;
     invalidate_graph(p);
-    if (alloc_head_nearest(h, m, PlanAlloc{p})) return 1;
+    const int metric = p->style_near_metric[index];      // (st_plan_set_nearest_metric: the buffers and the prepare pass go by it)
+    if (alloc_head_nearest(h, m, PlanAlloc{p}, metric)) return 1;
     ST_HIP(hipStreamSynchronize(nullptr));
-    if (launch_nearest_prepare(feat, h.n, m, nearest_prepared_of(h.near_prep, h.n, m), static_cast<hipStream_t>(stream))) return 1;
+    const NearestPrepared pr = nearest_prepared_of(h.near_prep, h.n, m);
+    if (metric ? launch_nearest_cosine_prepare(feat, h.n, m, metric == 2, pr, static_cast<hipStream_t>(stream))
+               : launch_nearest_prepare(feat, h.n, m, pr, static_cast<hipStream_t>(stream)))
+        return 1;
     h.near_m = m;
     h.target_set = true;
     return 0;

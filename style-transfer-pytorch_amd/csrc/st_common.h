@@ -787,6 +787,7 @@ struct NearestPrepared {
     long long m = 0, m_pad = 0;
     unsigned int* bound = nullptr;
     float *bias = nullptr, *st_t = nullptr;
+    float* mu = nullptr;                // cosine metrics only: the centre [C] behind the rows (nearest_cosine_prepared_floats)
 };
 NearestPrepared nearest_prepared_of(float* prepared, int channels, long long m);
 // per call, nearest_scratch_floats floats, 256-byte aligned: the ticket (zero between launches), a bound for a tap no trunk kernel
@@ -808,6 +809,18 @@ int launch_nearest_search(const float* feat, int channels, long long n, const Ne
 int nearest_head_run(const float* feat, int channels, long long n, const NearestPrepared& pr, const NearestScratch& sc,
                      const unsigned int* feat_bound, float weight, int* idx_out, float* score_out, float* grad, float* loss_out,
                      hipStream_t s);
+// ---- cosine and centred-cosine matching of a nearest head (st_plan_set_nearest_metric, st_op_nearest_cosine_*; st_nearest.hip) ----
+constexpr float kNearestCosineEps = 1e-8f;        // under both square roots: |s_k - mu|^2 + eps, |f_i - mu|^2 + eps (include/st_amd.h)
+// L2's layout - the bound on max |s^| (at most 1), b [M_pad], s^T [M_pad][C] - and behind it mu [C], padded to 64 floats
+long long nearest_cosine_prepared_floats(int channels, long long m);
+// L2's layout (the finish pass has one block per 64 pixels: never more partials than L2's)
+long long nearest_cosine_scratch_floats(int channels, long long n, long long m);
+// vectors [C][m] -> pr: mu (0, or the mean over k in double in ascending k), s^_k = (s_k - mu) / sqrt(|s_k - mu|^2 + eps) and
+// b_k = -<mu, s^_k> in double in channel order, each rounded once; zero rows and -inf in the padding; the bound
+int launch_nearest_cosine_prepare(const float* vectors, int channels, long long m, int centered, const NearestPrepared& pr, hipStream_t s);
+// the search (launch_nearest_search, unchanged), then the cosine finish pass: idx_out [n], grad [C][n] WRITTEN, loss_out[0] the weighted term
+int nearest_cosine_head_run(const float* feat, int channels, long long n, const NearestPrepared& pr, const NearestScratch& sc,
+                            const unsigned int* feat_bound, float weight, int* idx_out, float* grad, float* loss_out, hipStream_t s);
 // ---- sliced Wasserstein W2 heads (st_plan_set_style_sliced, st_op_sliced_*; st_sliced.hip) ----
 constexpr int kSlicedMaxImages = 16;              // style images a flagged entry keeps the feature vectors of
 // C a multiple of 32 (the 1x1 step's chunk), P a multiple of 64 in [64, 512], rows of 1 <= n < 2^24 elements

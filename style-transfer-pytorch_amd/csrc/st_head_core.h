@@ -98,15 +98,17 @@ int alloc_head_sliced(StyleHead& h, int proj, long long total, long long rows, A
 // function asks for more than it holds - the split count, hence the scratch, is not monotone in m.  A buffer that is outgrown
 // stays the allocator's until the plan is destroyed (plans free nothing before that), so a style set that keeps growing
 // accumulates dead device memory; one that shrinks or repeats allocates nothing.  The ticket in front of the scratch is zeroed on
-// the null stream, which the caller synchronises
+// the null stream, which the caller synchronises.  metric != 0 (st_plan_set_nearest_metric): the prepared buffer also holds the
+// centre, and both buffers are sized by the cosine entries' functions
 template <class Alloc>
-int alloc_head_nearest(StyleHead& h, long long m, Alloc&& alloc) {
+int alloc_head_nearest(StyleHead& h, long long m, Alloc&& alloc, int metric = 0) {
     if (!h.near_idx) {
         float* idx = nullptr;
         if (alloc(&idx, (size_t)h.npix_local)) return 1;
         h.near_idx = reinterpret_cast<int*>(idx);
     }
-    const size_t prep = (size_t)nearest_prepared_floats(h.n, m), scratch = (size_t)nearest_scratch_floats(h.n, h.npix_local, m);
+    const size_t prep = (size_t)(metric ? nearest_cosine_prepared_floats(h.n, m) : nearest_prepared_floats(h.n, m));
+    const size_t scratch = (size_t)(metric ? nearest_cosine_scratch_floats(h.n, h.npix_local, m) : nearest_scratch_floats(h.n, h.npix_local, m));
     if (prep > h.near_prep_floats) {
         h.near_prep = nullptr;
         h.near_prep_floats = 0;

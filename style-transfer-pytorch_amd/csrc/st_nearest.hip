@@ -24,6 +24,14 @@
 //                             ticket and the last block's index-order sum in double
 //   nearest_merge_kernel      the search entry's ending: the merge alone, indices and best scores
 //   nearest_scale_kernel      grad = upstream[0] unit_grad (the module's backward)
+// Cosine and centred-cosine matching (st_plan_set_nearest_metric; include/st_amd.h fixes the semantics) is the same search on
+// unit rows: W = s^^T with s^_k = (s_k - mu) / sqrt(|s_k - mu|^2 + eps), b_k = -<mu, s^_k>, mu = 0 or the style set's mean.
+//   cosine_mean_kernel            mu in double in ascending k, rounded once (the setter, once)
+//   cosine_rows_kernel            s^^T [M_pad][C] and b, formed in double and rounded once; zero rows and -inf in the padding
+//   nearest_cosine_finish_kernel  a workgroup owns 64 pixels and ALL their channels: it merges the splits, gathers s^_k*, recomputes
+//                                 p_i = <f_i - mu, s^_k*> and |f_i - mu|^2 in fp32 in a fixed channel order (first read of the
+//                                 tap), writes dF = (w / N) (-s^_k* / r_i + p_i g_i / r_i^3) (second read) and the indices, and
+//                                 reduces sum_i (1 - p_i / r_i) as nearest_finish_kernel does
 // No floating-point atomics: two runs give the same bits, indices included.  No loop's trip count depends on a comparison of
 // values, so every launch ends on any input; an index is clamped into [0, M) before it is used as an address.
 #include <algorithm>
@@ -344,6 +352,206 @@ __global__ __launch_bounds__(256) void nearest_scale_kernel(const float* __restr
     for (long long i = blockIdx.x * 256ll + threadIdx.x; i < count; i += (long long)gridDim.x * 256) out[i] = a * x[i];
 }
 
+// ---- cosine and centred-cosine matching (st_plan_set_nearest_metric): the prepare kernels and the finish pass ----
+constexpr int CPX = 64;                   // cosine finish: pixels per workgroup, which owns ALL their channels
+constexpr int CTP = 68;                   // pitch of its gathered tile in floats: rows stay 16-byte aligned
+constexpr double kCosEps = 1e-8;          // kNearestCosineEps where the sums are double
+
+// mu_c = (1/M) sum_k s_ck, in double in ascending k, rounded once (0 for the plain cosine and in the padding behind C).  One wave
+// per channel: 64 coalesced loads, then every lane adds the 64 values in lane order
+__global__ __launch_bounds__(64) void cosine_mean_kernel(const float* __restrict__ s, int cin, long long m, int centered,
+                                                         float* __restrict__ mu) {
+    const int c = blockIdx.x, lane = threadIdx.x;
+    if (!centered || c >= cin) {
+        if (lane == 0) mu[c] = 0.f;
+        return;
+    }
+    double sum = 0.0;
+    for (long long k0 = 0; k0 < m; k0 += 64) {
+        const float v = k0 + lane < m ? s[(size_t)c * m + k0 + lane] : 0.f;
+        const int cnt = (int)min(64ll, m - k0);
+        for (int j = 0; j < cnt; ++j) sum += (double)__shfl(v, j, 64);
+    }
+    if (lane == 0) mu[c] = (float)(sum / (double)m);
+}
+
+// thread = style vector k: |s_k - mu|^2 in double in channel order, then s^_k = (s_k - mu) / sqrt(|s_k - mu|^2 + eps) rounded once
+// (a zero vector stays zero), transposed through LDS into rows of s^T, and b_k = -<mu, s^_k> from the ROUNDED s^_k and mu, in
+// double in channel order, rounded once.  Padding rows are zero and their bias -inf.  The grid covers M_pad
+__global__ __launch_bounds__(64) void cosine_rows_kernel(const float* __restrict__ s, const float* __restrict__ mu, int cin, long long m,
+                                                         float* __restrict__ st_t, float* __restrict__ bias) {
+    __shared__ float tile[64][33];
+    const int lane = threadIdx.x;
+    const long long k0 = blockIdx.x * 64ll, k = k0 + lane;
+    const bool live = k < m;
+    double nrm = 0.0;
+    for (int c = 0; c < cin; ++c) {
+        const double d = live ? (double)s[(size_t)c * m + k] - (double)mu[c] : 0.0;
+        nrm += d * d;
+    }
+    const double root = sqrt(nrm + kCosEps);
+    double b = 0.0;
+    for (int c0 = 0; c0 < cin; c0 += 32) {
+        for (int j = 0; j < 32; ++j) {
+            const double mc = (double)mu[c0 + j];
+            const float v = live ? (float)(((double)s[(size_t)(c0 + j) * m + k] - mc) / root) : 0.f;
+            b += mc * (double)v;
+            tile[lane][j] = v;
+        }
+        __syncthreads();
+        for (int r = lane >> 5; r < 64; r += 2) st_t[(size_t)(k0 + r) * cin + c0 + (lane & 31)] = tile[r][lane & 31];
+        __syncthreads();
+    }
+    bias[k] = live ? (float)(0.0 - b) : -INFINITY;
+}
+
+struct CosineFinish {
+    double weight = 1.0, count = 1.0;   // w and N
+    float coef = 0.f;                   // w / N, rounded once
+    float* loss_out = nullptr;
+};
+
+// blockIdx.x: a tile of CPX pixels, ALL channels - a gradient element needs p_i = <g_i, s^_k*> and |g_i|^2 over all C, so the tap
+// and the gathered rows are read twice (the tap is L2-resident): once for the two sums, once for dF.
+// Thread (row = tid >> 4, quad = tid & 15) owns pixels 4 quad .. 4 quad + 3 and channels row, row + 16 of every 32-channel chunk:
+// it adds its channels in ascending order, then the 16 rows' sums are added in row order - the 16-byte and the scalar path do the
+// same arithmetic in the same order, so a pixel's sums depend on C alone.
+__global__ __launch_bounds__(256) void nearest_cosine_finish_kernel(const float* __restrict__ feat, const float* __restrict__ st_t,
+                                                                    const float* __restrict__ mu, const float* __restrict__ part_score,
+                                                                    const int* __restrict__ part_k, int splits, long long npix, int cin,
+                                                                    long long m, int* __restrict__ idx_out, float* __restrict__ grad,
+                                                                    float* __restrict__ partials, LastBlock lb, CosineFinish fin, int vec_ok) {
+#pragma clang fp contract(off)
+    __shared__ int ksel[CPX];
+    __shared__ __attribute__((aligned(16))) float tile[32][CTP];
+    __shared__ float psum[16][CPX], qsum[16][CPX];
+    __shared__ float pfin[CPX], ifin[CPX];
+    __shared__ float scratch[4];
+    __shared__ bool is_last;
+    __shared__ double sums[256];
+    const int tid = threadIdx.x;
+    const long long px0 = (long long)blockIdx.x * CPX;
+    if (tid < CPX) {
+        const long long px = px0 + tid;
+        int k = 0;
+        if (px < npix) {
+            merge_splits(part_score, part_k, splits, npix, m, px, &k);
+            idx_out[px] = k;
+        }
+        ksel[tid] = k;
+    }
+    __syncthreads();
+    const int quad = tid & 15, row = tid >> 4;
+    const long long px = px0 + 4 * quad;
+    const bool wide = vec_ok && px + 3 < npix;
+    const int nchunks = cin / KC;
+    // thread (pixel tid >> 2, quarter tid & 3) reads 8 consecutive channels of its pixel's row of s^T
+    auto gather = [&](int c0) {
+        const int gp = tid >> 2, gq = tid & 3;
+        const float* src = st_t + (size_t)ksel[gp] * cin + c0 + gq * 8;
+        const f32x4 lo = *reinterpret_cast<const f32x4*>(src), hi = *reinterpret_cast<const f32x4*>(src + 4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            tile[gq * 8 + e][gp] = lo[e];
+            tile[gq * 8 + 4 + e][gp] = hi[e];
+        }
+    };
+    auto load4 = [&](const float* at) {
+        f32x4 v;
+        if (wide) {
+            v = *reinterpret_cast<const f32x4*>(at);
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = (px + e < npix) ? at[e] : 0.f;
+        }
+        return v;
+    };
+    float p[4] = {0.f, 0.f, 0.f, 0.f}, q[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int ch = 0; ch < nchunks; ++ch) {
+        const int c0 = ch * KC;
+        gather(c0);
+        __syncthreads();
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const int cl = row + 16 * e;
+            const f32x4 f = load4(feat + (size_t)(c0 + cl) * npix + px);
+            const float mc = mu[c0 + cl];
+            const f32x4 sv = *reinterpret_cast<const f32x4*>(&tile[cl][4 * quad]);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float g = f[j] - mc;
+                p[j] += g * sv[j];
+                q[j] += g * g;
+            }
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        psum[row][4 * quad + j] = p[j];
+        qsum[row][4 * quad + j] = q[j];
+    }
+    __syncthreads();
+    float acc = 0.f;
+    if (tid < CPX) {
+        float ps = 0.f, qs = 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            ps += psum[r][tid];
+            qs += qsum[r][tid];
+        }
+        const float r = sqrtf(qs + kNearestCosineEps);
+        pfin[tid] = ps;
+        ifin[tid] = 1.f / r;
+        if (px0 + tid < npix) acc = 1.f - ps / r;
+    }
+    __syncthreads();
+    float ir[4], a[4];                    // 1 / r and p / r^3
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        ir[j] = ifin[4 * quad + j];
+        a[j] = pfin[4 * quad + j] * ir[j] * ir[j] * ir[j];
+    }
+    for (int ch = 0; ch < nchunks; ++ch) {
+        const int c0 = ch * KC;
+        gather(c0);
+        __syncthreads();
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const int cl = row + 16 * e;
+            float* out = grad + (size_t)(c0 + cl) * npix + px;
+            const f32x4 f = load4(feat + (size_t)(c0 + cl) * npix + px);
+            const float mc = mu[c0 + cl];
+            const f32x4 sv = *reinterpret_cast<const f32x4*>(&tile[cl][4 * quad]);
+            f32x4 d;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) d[j] = fin.coef * (a[j] * (f[j] - mc) - sv[j] * ir[j]);
+            if (wide) {
+                *reinterpret_cast<f32x4*>(out) = d;
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (px + j < npix) out[j] = d[j];
+            }
+        }
+        __syncthreads();
+    }
+    acc = block_sum_256(acc, scratch);
+    const float part[1] = {acc};
+    if (!last_block_arrives(lb, &is_last, partials + blockIdx.x, part)) return;
+    // the last block: thread t adds partials [t per, (t + 1) per) in index order, thread 0 the 256 sums in thread order
+    const long long blocks = gridDim.x, per = (blocks + 255) / 256;
+    double mine = 0.0;
+    for (long long i = tid * per; i < blocks && i < (tid + 1) * per; ++i) mine += (double)partials[i];
+    sums[tid] = mine;
+    __syncthreads();
+    if (tid == 0) {
+        double total = 0.0;
+        for (int i = 0; i < 256; ++i) total += sums[i];
+        fin.loss_out[0] = (float)(fin.weight * total / fin.count);
+    }
+}
+
 long long round_up(long long v, long long to) { return (v + to - 1) / to * to; }
 
 long long finish_blocks(int channels, long long n) {
@@ -384,7 +592,7 @@ NearestPrepared nearest_prepared_of(float* prepared, int channels, long long m) 
     pr.bound = reinterpret_cast<unsigned int*>(prepared);
     pr.bias = prepared + kAmaxWordUints;
     pr.st_t = pr.bias + pr.m_pad;
-    (void)channels;
+    pr.mu = pr.st_t + pr.m_pad * channels;      // inside the buffer only for nearest_cosine_prepared_floats; L2 never reads it
     return pr;
 }
 
@@ -454,6 +662,36 @@ int nearest_head_run(const float* feat, int channels, long long n, const Nearest
     return launch_nearest_finish(feat, channels, n, pr, sc, weight, idx_out, score_out, grad, loss_out, s);
 }
 
+long long nearest_cosine_prepared_floats(int channels, long long m) { return nearest_prepared_floats(channels, m) + round_up(channels, 64); }
+
+long long nearest_cosine_scratch_floats(int channels, long long n, long long m) { return nearest_scratch_floats(channels, n, m); }
+
+int launch_nearest_cosine_prepare(const float* vectors, int channels, long long m, int centered, const NearestPrepared& pr, hipStream_t s) {
+    if (nearest_check_shape("launch_nearest_cosine_prepare", channels, 1, m)) return 1;
+    ST_REQUIRE((reinterpret_cast<uintptr_t>(pr.st_t) & 15) == 0, "launch_nearest_cosine_prepare: the prepared buffer is not 16-byte aligned");
+    hipLaunchKernelGGL(cosine_mean_kernel, dim3((unsigned)round_up(channels, 64)), dim3(64), 0, s, vectors, channels, m, centered, pr.mu);
+    ST_LAUNCH_CHECK();
+    hipLaunchKernelGGL(cosine_rows_kernel, dim3((unsigned)(pr.m_pad / 64)), dim3(64), 0, s, vectors, pr.mu, channels, m, pr.st_t, pr.bias);
+    ST_LAUNCH_CHECK();
+    ST_HIP(hipMemsetAsync(pr.bound, 0, kAmaxWordUints * sizeof(unsigned int), s));
+    return launch_amax(pr.st_t, pr.m_pad * channels, pr.bound, 0, s);
+}
+
+int nearest_cosine_head_run(const float* feat, int channels, long long n, const NearestPrepared& pr, const NearestScratch& sc,
+                            const unsigned int* feat_bound, float weight, int* idx_out, float* grad, float* loss_out, hipStream_t s) {
+    if (launch_nearest_search(feat, channels, n, pr, sc, feat_bound, s)) return 1;
+    CosineFinish fin;
+    fin.weight = (double)weight;
+    fin.count = (double)n;
+    fin.coef = (float)((double)weight / (double)n);
+    fin.loss_out = loss_out;
+    const int vec_ok = n % 4 == 0 && ((reinterpret_cast<uintptr_t>(feat) | reinterpret_cast<uintptr_t>(grad)) & 15) == 0;
+    hipLaunchKernelGGL(nearest_cosine_finish_kernel, dim3((unsigned)((n + CPX - 1) / CPX)), dim3(256), 0, s, feat, pr.st_t, pr.mu,
+                       sc.part_score, sc.part_k, sc.splits, n, channels, pr.m, idx_out, grad, sc.partials, last_block(sc.ticket), fin, vec_ok);
+    ST_LAUNCH_CHECK();
+    return 0;
+}
+
 }  // namespace st
 
 using namespace st;
@@ -512,6 +750,40 @@ int st_op_nearest_loss(const float* feat, int channels, long long n, const float
     ST_HIP(hipMemsetAsync(scratch, 0, 16, s));
     return nearest_head_run(feat, channels, n, nearest_prepared_of(const_cast<float*>(prepared), channels, m),
                             nearest_scratch_of(scratch, channels, n, m), nullptr, 1.f, idx_out, nullptr, unit_grad_out, loss_out, s);
+}
+
+long long st_op_nearest_cosine_prepared_floats(int channels, long long m) {
+    if (channels < 1 || m < 1) return 0;
+    return nearest_cosine_prepared_floats(channels, m);
+}
+
+long long st_op_nearest_cosine_scratch_floats(int channels, long long n, long long m) {
+    if (channels < 1 || n < 1 || m < 1) return 0;
+    return nearest_cosine_scratch_floats(channels, n, m);
+}
+
+int st_op_nearest_cosine_prepare(const float* vectors, int channels, long long m, int centered, float* prepared, void* stream) {
+    ST_REQUIRE(vectors && prepared, "st_op_nearest_cosine_prepare: null argument");
+    ST_REQUIRE(centered == 0 || centered == 1, "st_op_nearest_cosine_prepare: centered %d: 0 (cosine) or 1 (centered_cosine)", centered);
+    ST_REQUIRE((reinterpret_cast<uintptr_t>(prepared) & 255) == 0, "st_op_nearest_cosine_prepare: prepared must be 256-byte aligned");
+    if (nearest_check_shape("st_op_nearest_cosine_prepare", channels, 1, m)) return 1;
+    ST_REQUIRE_PIXELS("st_op_nearest_cosine_prepare (style vectors)", m);
+    return launch_nearest_cosine_prepare(vectors, channels, m, centered, nearest_prepared_of(prepared, channels, m),
+                                         static_cast<hipStream_t>(stream));
+}
+
+int st_op_nearest_cosine_loss(const float* feat, int channels, long long n, const float* prepared, long long m, float* scratch, int* idx_out,
+                              float* unit_grad_out, float* loss_out, void* stream) {
+    ST_REQUIRE(feat && prepared && scratch && idx_out && unit_grad_out && loss_out, "st_op_nearest_cosine_loss: null argument");
+    ST_REQUIRE((reinterpret_cast<uintptr_t>(prepared) & 255) == 0, "st_op_nearest_cosine_loss: prepared must be 256-byte aligned");
+    ST_REQUIRE((reinterpret_cast<uintptr_t>(scratch) & 255) == 0, "st_op_nearest_cosine_loss: scratch must be 256-byte aligned");
+    if (nearest_check_shape("st_op_nearest_cosine_loss", channels, n, m)) return 1;
+    ST_REQUIRE_PIXELS("st_op_nearest_cosine_loss", n);
+    ST_REQUIRE_PIXELS("st_op_nearest_cosine_loss (style vectors)", m);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    ST_HIP(hipMemsetAsync(scratch, 0, 16, s));
+    return nearest_cosine_head_run(feat, channels, n, nearest_prepared_of(const_cast<float*>(prepared), channels, m),
+                                   nearest_scratch_of(scratch, channels, n, m), nullptr, 1.f, idx_out, unit_grad_out, loss_out, s);
 }
 
 int st_op_nearest_loss_backward(const float* unit_grad, long long count, const float* upstream, float* grad, void* stream) {

@@ -149,6 +149,9 @@ struct st_plan {
     // together with style_diag, style_marg, a custom eps, a style mask or regions.  Any set flag runs the general closure; either
     // kinds setter and st_plan_set_taps clear them.
     int style_near[16] = {};
+    // ... and what a flagged entry is matched on (st_plan_set_nearest_metric): 0 l2, 1 cosine, 2 centred cosine.  Non-zero only on
+    // a flagged entry; st_plan_set_style_nearest, either kinds setter and st_plan_set_taps reset them to 0.
+    int style_near_metric[16] = {};
     // A W2 entry matched on sliced projections (st_plan_set_style_sliced, st_sliced.hip): a flag per LISTED style entry, never
     // together with style_diag, style_marg, style_near, a custom eps, a style mask or regions.  Any set flag runs the general
     // closure; either kinds setter and st_plan_set_taps clear them.  Per flagged entry: the number of projections (0: the tap's

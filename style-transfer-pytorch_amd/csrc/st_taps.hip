@@ -264,11 +264,15 @@ int marginal_head(st_plan* p, const HeadSite& at, float* seed, hipStream_t s) {
 // A W2 entry flagged nearest (st_plan_set_style_nearest, st_nearest.hip): the search against the style set, then the finish pass,
 // which writes dF to the seed, the matches to the head and the weighted term to the entry's slot.  No mask, no eps.  The tap's
 // bound word where the producing convolution leaves one (fp16x3 trunks), otherwise measured by the search's launcher.
-int nearest_head(st_plan* p, const HeadSite& at, float* seed, hipStream_t s) {
+// Entry j's metric (st_plan_set_nearest_metric) picks the finish pass: cosine and centred cosine run the same search on the unit
+// rows and the bias the setter prepared, then the cosine finish (st_nearest.hip).
+int nearest_head(st_plan* p, int j, const HeadSite& at, float* seed, hipStream_t s) {
     const StyleHead& h = *at.h;
     const NearestPrepared pr = nearest_prepared_of(h.near_prep, h.n, h.near_m);
     const NearestScratch sc = nearest_scratch_of(h.near_scratch, h.n, h.npix_local, h.near_m);
     const unsigned int* bound = p->net->conv_elem == 1 ? at.tap->y_amax : nullptr;
+    if (p->style_near_metric[j])
+        return nearest_cosine_head_run(at.tap->y, h.n, h.npix_local, pr, sc, bound, at.weight, h.near_idx, seed, at.loss, s);
     return nearest_head_run(at.tap->y, h.n, h.npix_local, pr, sc, bound, at.weight, h.near_idx, nullptr, seed, at.loss, s);
 }
 
@@ -374,7 +378,7 @@ int general_loss_and_grad(st_plan* p, const float* image, float* grad_out, float
                 continue;
             }
             if (p->style_near[order[k]]) {
-                if (nearest_head(p, at, at.grad, s)) return 1;
+                if (nearest_head(p, order[k], at, at.grad, s)) return 1;
                 styled[p->style_op[order[k]]] = true;
                 continue;
             }
@@ -520,7 +524,7 @@ int st_plan_set_taps(st_plan* p, int n_content, const int* content_layers, int n
         p->content_kind[i] = ckind;
         p->style_kind[i] = skind;
         p->content_eps[i] = p->style_eps[i] = -1.f;
-        p->style_diag[i] = p->style_marg[i] = p->style_near[i] = p->style_sliced[i] = 0;
+        p->style_diag[i] = p->style_marg[i] = p->style_near[i] = p->style_near_metric[i] = p->style_sliced[i] = 0;
         if (keep_weights) continue;
         p->content_weight[i] = i < n_content ? 0.015f / (float)n_content : 0.f;
         p->style_weight[i] = i >= n_style ? 0.f : ref ? kStyleWeight[i] : 1.f / (float)n_style;
@@ -543,7 +547,7 @@ int apply_loss_kinds(st_plan* p, const int* ck, const int* sk) {
         p->content_kind[i] = ck[i];
         p->style_kind[i] = sk[i];
         p->content_eps[i] = p->style_eps[i] = -1.f;      // an eps belongs to a module of one kind: set it after the kinds
-        p->style_diag[i] = p->style_marg[i] = p->style_near[i] = p->style_sliced[i] = 0;      // ... and so do the diagonal, marginal, nearest and sliced flags of a W2 entry
+        p->style_diag[i] = p->style_marg[i] = p->style_near[i] = p->style_near_metric[i] = p->style_sliced[i] = 0;      // ... and so do the diagonal, marginal, nearest and sliced flags of a W2 entry
     }
     // a target is kept in the form its kind reads (a root, or a Gram matrix): as after st_plan_set_taps, every target set
     // before is gone, every bound word is dealt again and nothing built on the former terms survives.  The lists and all
@@ -745,6 +749,7 @@ int st_plan_set_style_nearest(st_plan* p, const int* flags) {
                "st_plan_set_style_nearest: a style mask or style regions are in force on this plan; masked matching is not implemented - "
                "clear them first");
     std::copy(fl, fl + 16, p->style_near);
+    std::fill(p->style_near_metric, p->style_near_metric + 16, 0);      // l2 until st_plan_set_nearest_metric says otherwise
     // a target is kept in the form its head reads - a set of style vectors, or a root: every target set before is gone
     drop_targets(p);
     return 0;
@@ -753,6 +758,29 @@ int st_plan_set_style_nearest(st_plan* p, const int* flags) {
 int st_plan_style_nearest(const st_plan* p, int* flags) {
     ST_REQUIRE(p && flags, "st_plan_style_nearest: null argument");
     for (int j = 0; j < p->n_style; ++j) flags[j] = p->style_near[j];
+    return 0;
+}
+
+int st_plan_set_nearest_metric(st_plan* p, const int* metrics) {
+    ST_REQUIRE(p, "st_plan_set_nearest_metric: null plan");
+    int mt[16] = {};
+    for (int j = 0; metrics && j < p->n_style; ++j) {
+        ST_REQUIRE(metrics[j] >= 0 && metrics[j] <= 2,
+                   "st_plan_set_nearest_metric: metric %d of style layer %d: 0 (l2), 1 (cosine) or 2 (centered_cosine)", metrics[j], j);
+        ST_REQUIRE(metrics[j] == 0 || p->style_near[j],
+                   "st_plan_set_nearest_metric: style layer %d is not flagged nearest (st_plan_set_style_nearest): only a flagged layer "
+                   "takes a metric", j);
+        mt[j] = metrics[j];
+    }
+    std::copy(mt, mt + 16, p->style_near_metric);
+    // a style set is kept as its metric's search reads it - unit rows and a centre, or S^T: every target set before is gone
+    drop_targets(p);
+    return 0;
+}
+
+int st_plan_nearest_metric(const st_plan* p, int* metrics) {
+    ST_REQUIRE(p && metrics, "st_plan_nearest_metric: null argument");
+    for (int j = 0; j < p->n_style; ++j) metrics[j] = p->style_near_metric[j];
     return 0;
 }
 

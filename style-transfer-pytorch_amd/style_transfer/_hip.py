@@ -23,6 +23,8 @@ TAPS = (1, 3, 4, 6, 8, 9, 11, 13, 15, 17, 18, 20, 22, 24, 26, 27, 29)
 DEFAULT_CONTENT_LAYERS, DEFAULT_STYLE_LAYERS = (22,), (1, 6, 11, 20, 29)
 # the loss kind of each list (st_plan_set_loss_kinds), by the library's code: ContentLossMSE / ContentLoss, StyleLossW2 / StyleLoss
 CONTENT_LOSSES, STYLE_LOSSES = ('mse', 'scaled_mse'), ('w2', 'gram')
+# what a nearest head is matched on (st_plan_set_nearest_metric's codes 0, 1, 2; include/st_amd.h)
+NEAREST_METRICS = ('l2', 'cosine', 'centered_cosine')
 _lib = None
 
 
@@ -98,6 +100,8 @@ def _declare(lib):
         'st_plan_style_nearest': (i32, [vp, ctypes.POINTER(i32)]),
         'st_plan_set_style_vectors': (i32, [vp, i32, vp, i64, vp]),
         'st_plan_nearest_indices': (i32, [vp, i32, pp, ctypes.POINTER(i64)]),
+        'st_plan_set_nearest_metric': (i32, [vp, ctypes.POINTER(i32)]),
+        'st_plan_nearest_metric': (i32, [vp, ctypes.POINTER(i32)]),
         'st_plan_set_style_sliced': (i32, [vp, ctypes.POINTER(i32)]),
         'st_plan_style_sliced': (i32, [vp, ctypes.POINTER(i32)]),
         'st_plan_set_sliced_options': (i32, [vp, i32, i32, i32]),
@@ -188,6 +192,10 @@ def _declare(lib):
         'st_op_nearest_search': (i32, [vp, i32, i64, vp, i64, vp, vp, vp, vp]),
         'st_op_nearest_loss': (i32, [vp, i32, i64, vp, i64, vp, vp, vp, vp, vp]),
         'st_op_nearest_loss_backward': (i32, [vp, i64, vp, vp, vp]),
+        'st_op_nearest_cosine_prepared_floats': (i64, [i32, i64]),
+        'st_op_nearest_cosine_scratch_floats': (i64, [i32, i64, i64]),
+        'st_op_nearest_cosine_prepare': (i32, [vp, i32, i64, i32, vp, vp]),
+        'st_op_nearest_cosine_loss': (i32, [vp, i32, i64, vp, i64, vp, vp, vp, vp, vp]),
         'st_op_sliced_directions': (i32, [ctypes.c_ulonglong, i32, ctypes.c_ulonglong, i32, i32, vp, vp, vp]),
         'st_op_sliced_scratch_bytes': (i64, [i32, i32, i64]),
         'st_op_sliced_target': (i32, [vp, i32, i64, vp, vp, i32, i64, vp, vp, i32, f32, vp]),
@@ -521,6 +529,37 @@ class Plan:
         fa = (ctypes.c_int * max(n, 1))()
         _check(self.lib.st_plan_style_nearest(self.handle, fa))
         return tuple(bool(v) for v in fa[:n])
+
+    def set_nearest_metric(self, names=None):
+        """What the layers flagged by ``set_style_nearest`` are matched on (st_plan_set_nearest_metric): None (every layer
+        'l2'), one name of ``NEAREST_METRICS`` for every flagged layer, or a sequence with one name per style layer.  'cosine':
+        ``k*(i) = argmax_k <f_i, s^_k>`` on the style's unit vectors and the term ``mean_i (1 - cos(f_i, s_k*))``;
+        'centered_cosine': the same after subtracting the style set's mean feature from both.  Call it after
+        ``set_style_nearest`` (which resets every layer to 'l2') and before the weights and targets; drops every target.  A
+        name other than 'l2' on a layer that is not flagged is refused."""
+        n = len(self.style_layers)
+        if names is None:
+            names = [NEAREST_METRICS[0]] * n
+        elif isinstance(names, str):
+            flagged = self.style_nearest
+            names = [names if flagged[j] else NEAREST_METRICS[0] for j in range(n)]
+        names = list(names)
+        if len(names) != n:
+            raise ValueError(f'{len(names)} nearest metrics for {n} style layers: one per layer')
+        for v in names:
+            if v not in NEAREST_METRICS:
+                raise ValueError(f'nearest metric {v!r}: one of {NEAREST_METRICS}')
+        ma = (ctypes.c_int * max(n, 1))(*[NEAREST_METRICS.index(v) for v in names])
+        with torch.cuda.device(self.device):
+            _check(self.lib.st_plan_set_nearest_metric(self.handle, ma))
+
+    @property
+    def nearest_metric(self):
+        """The metric of each style layer, a tuple of names of ``NEAREST_METRICS`` (st_plan_nearest_metric)."""
+        n = len(self.style_layers)
+        ma = (ctypes.c_int * max(n, 1))()
+        _check(self.lib.st_plan_nearest_metric(self.handle, ma))
+        return tuple(NEAREST_METRICS[v] for v in ma[:n])
 
     def set_style_sliced(self, flags=None):
         """Match a 'w2' style layer on sliced projections (st_plan_set_style_sliced): None or False (no layer), True (every
@@ -1683,6 +1722,33 @@ def op_nearest_loss(x, prepared, m):
     with torch.cuda.device(x.device):
         _check(lib.st_op_nearest_loss(_ptr(x), c, n, _ptr(prepared), int(m), _ptr(scratch), ctypes.c_void_p(idx.data_ptr()), _ptr(unit),
                                       _ptr(loss), _stream()))
+    return loss, unit, idx.to(torch.int64)
+
+
+def op_nearest_cosine_prepare(vectors, centered=False):
+    """The style set [C, M] as the search and the cosine finish read it (st_op_nearest_cosine_prepare): unit rows, the bias
+    ``-<mu, s^_k>`` and the centre ``mu`` (0, or with ``centered`` the set's mean) - an opaque fp32 buffer for
+    ``op_nearest_cosine_loss`` and ``op_nearest_search``."""
+    lib = load_library()
+    c, m = int(vectors.shape[0]), int(vectors.shape[1])
+    prepared = torch.empty(max(int(lib.st_op_nearest_cosine_prepared_floats(c, m)), 1), device=vectors.device, dtype=torch.float32)
+    with torch.cuda.device(vectors.device):
+        _check(lib.st_op_nearest_cosine_prepare(_ptr(vectors), c, m, int(centered), _ptr(prepared), _stream()))
+    return prepared
+
+
+def op_nearest_cosine_loss(x, prepared, m):
+    """(the cosine nearest-neighbour loss [0-dim], its gradient at weight 1 shaped like x, the matches [N] int64) -
+    st_op_nearest_cosine_loss."""
+    lib = load_library()
+    c, n = _rows(x)
+    scratch = torch.empty(max(int(lib.st_op_nearest_cosine_scratch_floats(c, n, m)), 4), device=x.device, dtype=torch.float32)
+    idx = torch.empty((n,), device=x.device, dtype=torch.int32)
+    loss = torch.empty((), device=x.device, dtype=torch.float32)
+    unit = torch.empty(x.shape, device=x.device, dtype=torch.float32)
+    with torch.cuda.device(x.device):
+        _check(lib.st_op_nearest_cosine_loss(_ptr(x), c, n, _ptr(prepared), int(m), _ptr(scratch), ctypes.c_void_p(idx.data_ptr()),
+                                             _ptr(unit), _ptr(loss), _stream()))
     return loss, unit, idx.to(torch.int64)
 
 

@@ -319,6 +319,10 @@ def build_parser():
                         "and iteration): 1 for every 'w2' layer, or a comma-separated list with one flag per style layer, e.g. "
                         "'0,0,0,1,1' (default 0); not together with --style-diagonal or --style-marginal on the same layer, "
                         "style masks or regions")
+    p.add_argument('--style-nearest-metric', type=_nearest_metric, default='l2', metavar='NAME[,...]',
+                   help="what the --style-nearest layers are matched on: l2, cosine or centered_cosine (cosine after subtracting "
+                        "the style vectors' mean; the neural-neighbour methods' own metric): one name for every flagged layer, or a "
+                        "comma-separated list with one name per style layer, e.g. 'l2,l2,l2,cosine,cosine' (default l2)")
     p.add_argument('--style-nearest-samples', type=_positive_int, default=None, metavar='INT',
                    help='keep at most INT evenly spaced feature vectors of every style image per --style-nearest layer (the '
                         'search costs 2 C N M flop per iteration: this is what makes a shallow layer affordable; default: all)')
@@ -400,6 +404,16 @@ def _seed_int(text):
     return value
 
 
+def _nearest_metric(text):
+    """argparse type of --style-nearest-metric: one name stays the name, a comma-separated list becomes the list of names."""
+    from . import _hip
+    items = text.split(',')
+    for item in items:
+        if item not in _hip.NEAREST_METRICS:
+            raise argparse.ArgumentTypeError(f'{item!r}: one of {", ".join(_hip.NEAREST_METRICS)}')
+    return items[0] if len(items) == 1 else items
+
+
 def _diagonal_flags(text):
     """argparse type of --style-diagonal / --style-marginal / --style-nearest / --style-sliced: one flag stays the bool, a comma-separated list becomes the list of bools."""
     items = text.split(',')
@@ -461,12 +475,13 @@ def apply_style_masks(st, args):
 
 
 def apply_loss_kinds(st, args):
-    """--content-loss / --style-loss / --content-eps / --style-eps / --style-diagonal / --style-marginal / --style-nearest / --style-nearest-samples / --style-sliced and its options onto the StyleTransfer attributes that stylize() reads."""
+    """--content-loss / --style-loss / --content-eps / --style-eps / --style-diagonal / --style-marginal / --style-nearest / --style-nearest-metric / --style-nearest-samples / --style-sliced and its options onto the StyleTransfer attributes that stylize() reads."""
     st.content_loss, st.style_loss = args.content_loss, args.style_loss
     st.content_eps, st.style_eps = args.content_eps, args.style_eps
     st.style_diagonal = args.style_diagonal
     st.style_marginal = args.style_marginal
     st.style_nearest, st.style_nearest_samples = args.style_nearest, args.style_nearest_samples
+    st.style_nearest_metric = args.style_nearest_metric
     st.style_sliced, st.style_sliced_projections = args.style_sliced, args.style_sliced_projections
     st.style_sliced_resample, st.style_sliced_seed = args.style_sliced_resample, args.style_sliced_seed
     st.style_sliced_samples = args.style_sliced_samples

@@ -70,7 +70,7 @@ class native:
         native.enabled, native.precision = self._former
 
 
-# calls that went to the library, by kind ('w2', 'gram', 'mse', 'scaled_mse', 'tv', 'laplacian', 'w2_diag', 'w2_marginal', 'nearest', 'sliced', 'moments'): the native indicator of the
+# calls that went to the library, by kind ('w2', 'gram', 'mse', 'scaled_mse', 'tv', 'laplacian', 'w2_diag', 'w2_marginal', 'nearest', 'nearest_cosine', 'sliced', 'moments'): the native indicator of the
 # modules that hold no head
 native_calls = {}
 _prepared_sets = weakref.WeakKeyDictionary()       # StyleLossNearest module -> (target, version, its prepared style set), kept off the module as the heads are
@@ -377,6 +377,21 @@ class _NearestLoss(torch.autograd.Function):
             return _torch_vjp(ctx.torch_forward, input, grad_output), None, None, None
         grad = _hip.op_nearest_loss_backward(unit, grad_output.contiguous())
         return grad.view(input.shape), None, None, None
+
+
+class _NearestCosineLoss(_NearestLoss):
+    """StyleLossNearest.forward under the 'cosine' and 'centered_cosine' metrics: st_op_nearest_cosine_loss; the backward is
+    _NearestLoss's."""
+
+    @staticmethod
+    def forward(ctx, input, module, prepared, m):
+        from . import _hip
+        loss, unit, _ = _hip.op_nearest_cosine_loss(_dense(input), prepared, m)
+        _count('nearest_cosine')
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(input, unit)
+            ctx.torch_forward = module._forward_torch
+        return loss
 
 
 class _SlicedLoss(torch.autograd.Function):
@@ -731,14 +746,24 @@ class StyleLossNearest(nn.Module):
     resampled - ``target`` = [C, M] with any M (``get_target``).  The cost is ``2 C N M`` flop per call.  The torch path serves
     any device, dtype and batch, chunked over the pixels so that no N x M matrix exists; one dense fp32 HIP tensor whose channel
     count is a multiple of 32 runs in the library (st_nearest.hip: one fused search, which writes no score, and one finish
-    pass; the search runs in fp16x3, so a match is optimal up to that arithmetic)."""
+    pass; the search runs in fp16x3, so a match is optimal up to that arithmetic).
+    ``metric``: 'l2' (the above), 'cosine' or 'centered_cosine' - the metrics the family is named after
+    (st_plan_set_nearest_metric): with ``mu`` = 0 or the mean of the target's columns, ``s^_k = (s_k - mu) / sqrt(|s_k - mu|^2 +
+    1e-8)``, ``g_i = f_i - mu`` and ``k*(i) = argmax_k <g_i, s^_k>`` (the first maximum), the term is ``mean_i (1 - <g_i, s^_k*> /
+    sqrt(|g_i|^2 + 1e-8))``: one minus the cosine to the best-matching style vector, which is what that search minimises.  The
+    match and ``mu`` are constants of the gradient.  On the device these calls count under 'nearest_cosine'."""
 
     chunk = 4096        # pixels per block of the torch path's distance matrix
+    eps = 1e-8          # of the cosine metrics; not an argument (include/st_amd.h)
 
-    def __init__(self, target):
+    def __init__(self, target, metric='l2'):
         super().__init__()
         if target.ndim != 2:
             raise ValueError(f'target of shape {tuple(target.shape)}: [C, M], the style feature vectors as columns')
+        from . import _hip
+        if metric not in _hip.NEAREST_METRICS:
+            raise ValueError(f'metric {metric!r}: one of {_hip.NEAREST_METRICS}')
+        self.metric = metric
         self.register_buffer('target', target)
 
     @staticmethod
@@ -765,17 +790,49 @@ class StyleLossNearest(nn.Module):
         cached = _prepared_sets.get(self)
         if cached is None or cached[0] is not target or cached[1] != target._version:
             from . import _hip
-            cached = _prepared_sets[self] = (target, target._version, _hip.op_nearest_prepare(target.contiguous()))
+            if self.metric == 'l2':
+                prepared = _hip.op_nearest_prepare(target.contiguous())
+            else:
+                prepared = _hip.op_nearest_cosine_prepare(target.contiguous(), centered=self.metric == 'centered_cosine')
+            cached = _prepared_sets[self] = (target, target._version, prepared)
         return cached[2]
 
     def forward(self, input):
         if native.enabled and eligible(input, 'nearest') and self.target.shape[0] == input.shape[-3] and \
                 not self.target.requires_grad and self.target.device == input.device and self.target.dtype == torch.float32:
-            return _NearestLoss.apply(input, self, self._prepared(), int(self.target.shape[1]))
+            if self.metric == 'l2':
+                return _NearestLoss.apply(input, self, self._prepared(), int(self.target.shape[1]))
+            if _pixels_ok(input) and self.target.shape[1] <= _max_pixels():
+                return _NearestCosineLoss.apply(input, self, self._prepared(), int(self.target.shape[1]))
         return self._forward_torch(input)
+
+    def cosine_parts(self, dtype):
+        """(mu [C], the unit vectors s^ [C, M]) of the cosine metrics, from ``target`` in ``dtype``."""
+        s = self.target.to(dtype)
+        mu = s.mean(1) if self.metric == 'centered_cosine' else torch.zeros_like(s[:, 0])
+        d = s - mu[:, None]
+        return mu, d / torch.sqrt((d * d).sum(0) + self.eps)
+
+    @staticmethod
+    def match_cosine(g, unit, chunk=4096):
+        """k*(i) for the centred features g [..., C, N] against the unit vectors [C, M], [..., N] int64: the first maximum of
+        ``<g_i, s^_k>``."""
+        out = []
+        for start in range(0, g.shape[-1], chunk):
+            out.append(_first_argmin(-torch.einsum('ck,...cn->...kn', unit, g[..., start:start + chunk]), dim=-2))
+        return torch.cat(out, dim=-1)
 
     def _forward_torch(self, input):
         feat = input.flatten(-2)
+        if self.metric != 'l2':
+            mu, unit = self.cosine_parts(feat.dtype)
+            g = feat - mu[:, None]
+            with torch.no_grad():
+                k = self.match_cosine(g, unit, self.chunk)
+            matched = unit[:, k]                                # [C, ..., N]
+            matched = matched.movedim(0, -2) if k.ndim > 1 else matched
+            p = (g * matched).sum(-2)
+            return torch.mean(1 - p / torch.sqrt((g * g).sum(-2) + self.eps))
         with torch.no_grad():
             k = self.match(feat, self.target.to(feat.dtype), self.chunk)
         matched = self.target.to(feat.dtype)[:, k]              # [C, ..., N]

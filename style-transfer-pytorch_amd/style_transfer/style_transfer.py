@@ -412,6 +412,37 @@ def _resolve_style_nearest(style_nearest, style_loss, style_diagonal=None, style
     return flags
 
 
+def _resolve_style_nearest_metric(style_nearest_metric, style_nearest, world=1):
+    """``StyleTransfer.style_nearest_metric`` as the fused closure takes it: one name of ``_hip.NEAREST_METRICS`` per entry of
+    ``style_nearest`` (the resolved flags).  A name means that metric on every flagged layer ('l2' on the others); a sequence
+    holds one name per entry of style_layers.  Raises ``ValueError`` naming the attribute for a wrong length, an unknown name,
+    a name other than 'l2' on a layer that is not flagged, and for a metric other than 'l2' on several ranks, before any device
+    work."""
+    names, n = _hip.NEAREST_METRICS, len(style_nearest)
+    if isinstance(style_nearest_metric, str):
+        if style_nearest_metric not in names:
+            raise ValueError(f'style_nearest_metric {style_nearest_metric!r}: one of {names}')
+        metrics = [style_nearest_metric if flag else names[0] for flag in style_nearest]
+    else:
+        if not isinstance(style_nearest_metric, (list, tuple)):
+            raise ValueError(f'style_nearest_metric {style_nearest_metric!r}: give one of {names}, or a sequence with one name per '
+                             'entry of style_layers')
+        metrics = list(style_nearest_metric)
+        if len(metrics) != n:
+            raise ValueError(f'style_nearest_metric {style_nearest_metric!r}: {len(metrics)} names for {n} layers; give one name, '
+                             'or exactly one per entry of style_layers')
+        for i, (name, flag) in enumerate(zip(metrics, style_nearest)):
+            if not isinstance(name, str) or name not in names:
+                raise ValueError(f'style_nearest_metric {style_nearest_metric!r}: {name!r} is none of {names}')
+            if name != names[0] and not flag:
+                raise ValueError(f'style_nearest_metric {style_nearest_metric!r}: layer {i} is not flagged in style_nearest; only '
+                                 f'a layer matched on nearest style vectors takes the metric {name!r}')
+    if world > 1 and any(name != names[0] for name in metrics):
+        raise ValueError(f'style_nearest_metric {style_nearest_metric!r} on {world} ranks: nearest heads are out of scope for '
+                         'strips - run them on one device')
+    return metrics
+
+
 def _resolve_style_sliced(style_sliced, style_loss, style_diagonal=None, style_marginal=None, style_nearest=None, style_eps=None,
                           masked=False, world=1, projections=None, samples=None, resample=True, seed=0, optimizer='adam'):
     """``StyleTransfer.style_sliced`` as the fused closure takes it: one bool per entry of ``style_loss`` (the resolved kinds).
@@ -1023,6 +1054,12 @@ class StyleTransfer:
     # image order; an image of weight 0 is left out, otherwise style_weights do not enter such a layer.  Not together with
     # style_diagonal, style_marginal or a custom style_eps on the same layer, nor with style masks or regions.  One device only.
     style_nearest = False
+    # What the style_nearest layers are matched on: 'l2' (the term above), 'cosine' or 'centered_cosine' - the metrics the
+    # family is named after (_hip.Plan.set_nearest_metric).  A ReLU tap's vectors differ in length by an order of magnitude across
+    # a picture, and a vector's direction is what carries which texture it is: the term is the mean over pixels of one minus the
+    # cosine to the best-matching style vector, 'centered_cosine' after subtracting the mean of the style vectors kept (NNST).
+    # One name for every flagged layer, or a sequence with one name per entry of style_layers ('l2' on the layers not flagged).
+    style_nearest_metric = 'l2'
     # None, or an int K >= 1: when a style tap has more than K pixels the host keeps the columns floor(t M / K), t = 0 ... K - 1,
     # per image and flagged layer.  This is what makes a shallow layer affordable: the search costs 2 C N M flop per iteration
     # (relu1_1 at 512^2 has N = M = 262144).
@@ -1395,6 +1432,8 @@ class StyleTransfer:
                                                masked=any(value is not None for value in (self.style_mask, self.style_regions,
                                                                                           self.style_image_masks)),
                                                world=max(len(self.devices), _dist_info()[1]), samples=self.style_nearest_samples)
+        style_nearest_metric = _resolve_style_nearest_metric(self.style_nearest_metric, style_nearest,
+                                                             world=max(len(self.devices), _dist_info()[1]))
         style_sliced = _resolve_style_sliced(self.style_sliced, style_loss, style_diagonal, style_marginal, style_nearest, style_eps,
                                              masked=any(value is not None for value in (self.style_mask, self.style_regions,
                                                                                         self.style_image_masks)),
@@ -1544,6 +1583,8 @@ class StyleTransfer:
                     plan.set_w2_marginal(style_marginal)
                 if any(style_nearest):
                     plan.set_style_nearest(style_nearest)
+                    if any(name != _hip.NEAREST_METRICS[0] for name in style_nearest_metric):
+                        plan.set_nearest_metric(style_nearest_metric)
                 if any(style_sliced):
                     plan.set_style_sliced(style_sliced)
                     for idx, flag in enumerate(style_sliced):
